@@ -10,9 +10,22 @@ roofline.  Workload = BASELINE.json configs[1] ("C2"):
 A "step" = one pass of the fused hot path over the GPU's shard.  With --gpus N>1 the
 stream is N shards of 2^26 samples, one rank per GPU: rank r re-filters the 256 samples
 before its shard as a lead-in of the same launch (absolute-index state, no halo exchange)
-and no collective sits on the data path (weak scaling).  With more than one rank the run ALSO assembles the decoded
+and no collective sits on the data path (weak scaling).  With more than one rank, a --full run ALSO assembles the decoded
 stream and times an RCCL all_gather of the decoded output per step (BASELINE north_star: "trivial RCCL/xGMI gather of
 decoded output"), reported in "extra" (never in `value`); `--no-gather` skips that leg.
+
+Plain run and --full.  A plain run (`bench.py --gpus 1 --steps K --warmup W`) does what its headline figure needs: set-up,
+the clock pre-roll and the W warm-up steps, the K timed steps, the output dump if asked for, the JSON line.  `--full` adds
+everything else the benchmark measures or checks: the process's first steps (`extra.first_step_ms`, `extra.cold_ms_per_step`),
+the steady-state check (`extra.steady_check`), the output sanity figure (`extra.output_rms_rad`), the gather leg with more
+than one rank, the side configurations (`extra.side`, N = 1) and the CPU baselines (`cpu_baseline`, N = 1);
+`--no-side` / `--no-cpu-baseline` leave the last two out of a --full run.
+
+Outputs.  `--dump-outputs DIR` writes what the timed path handed its caller in the last timed step -- the decoded angles of
+the shard, float32 radians -- as DIR/<name>.npy right after the timed steps (before anything in a --full run reuses the
+output buffer): the first and last DUMP_EDGE outputs, a fixed seeded sample of the outputs in between with its positions
+(float64), and the output count.  The input is generated from fixed seeds, so two builds run with the same arguments can
+be compared output for output.
 
 Launching.  Under torch.distributed.run (WORLD_SIZE set) this process is one rank.  Started
 plainly with --gpus N>1 it is the *launcher*: it builds the extension once (in a child
@@ -24,9 +37,9 @@ Timing.  `value` and `ms_per_step` are wall clock around the K timed steps (barr
 device sync on both sides, max over ranks), and `roofline.achieved` / `roofline.frac` are computed from that
 same interval (one basis for the whole line).  `roofline.kernel_ms_events` is HIP-event time on the
 launch stream around the same K launches / K (one kernel launch per step), kept beside it.  20 steps are
-only ~4 ms of device time, so the same step is also run for >= 100 ms right after the
-timed region (`extra.steady_check`); the process's first step (one-off costs) and the 19 after it,
-before the pre-roll, are reported in `extra.first_step_ms` / `extra.cold_ms_per_step`.
+only ~4 ms of device time, so a --full run also runs the same step for >= 100 ms right after the
+timed region (`extra.steady_check`) and reports the process's first step (one-off costs) and the 19 after it,
+before the pre-roll, in `extra.first_step_ms` / `extra.cold_ms_per_step`.
 
 Prints ONE JSON line on rank 0.
 """
@@ -190,9 +203,12 @@ def launch(n_gpus, argv):
 
 def build_once_per_node():
     """Ranks started directly by torch.distributed.run: one rank at a time looks at the build (file lock),
-    so N ranks never compile the same objects concurrently; a finished build is a few stat() calls."""
+    so N ranks never compile the same objects concurrently; a finished build is a few stat() calls and writes nothing (the
+    tree may belong to another user than the one running the benchmark)."""
     import fcntl
     import __graft_entry__ as ge
+    if os.path.exists(ge.LIB):
+        return
     os.makedirs(os.path.join(ROOT, "build"), exist_ok=True)
     with open(os.path.join(ROOT, "build", ".lock"), "w") as lk:
         fcntl.flock(lk, fcntl.LOCK_EX)
@@ -832,6 +848,38 @@ def side_c4_end_to_end(dur=60.0):
     return [warm, cold]
 
 
+# ----------------------------------------------------------------------------- --dump-outputs
+DUMP_EDGE = 1 << 16            # outputs kept whole at each end of the shard (the stream start / end and their edge tiles)
+DUMP_SAMPLE = 1 << 21          # seeded sample positions per GPU in between: 8 MB of float32 angles + 16 MB of float64 positions
+DUMP_SEED = 20261016
+
+
+def dump_outputs(eng, path, rank, world):
+    """--dump-outputs: this rank's decoded angles as the last timed step left them (float32 radians, the count the call returned).
+    Files, prefixed rank<r>_ with more than one rank: fm_angle_head / fm_angle_tail (the first / last DUMP_EDGE outputs),
+    fm_angle_sample + fm_angle_sample_index (the outputs at sorted positions drawn from a fixed seed, DUMP_SAMPLE per GPU shared
+    among the ranks; every output when there are no more than that), fm_angle_count.  24 MB + 0.5 MB per rank in all."""
+    torch = eng.torch
+    out, cnt = eng.shard_output()
+    out = out[:cnt]
+    k = max(1, DUMP_SAMPLE // world)
+    if cnt <= k:
+        idx = np.arange(cnt, dtype=np.int64)
+    else:
+        idx = np.unique(np.random.default_rng(DUMP_SEED + rank).integers(0, cnt, size=k, dtype=np.int64))
+    arrays = {
+        "fm_angle_head": out[:DUMP_EDGE],
+        "fm_angle_tail": out[max(0, cnt - DUMP_EDGE):],
+        "fm_angle_sample": out[torch.from_numpy(idx).to(out.device)],
+    }
+    os.makedirs(path, exist_ok=True)
+    pre = "rank%d_" % rank if world > 1 else ""
+    for name, t in arrays.items():
+        np.save(os.path.join(path, pre + name + ".npy"), t.detach().cpu().numpy().astype(np.float32))
+    np.save(os.path.join(path, pre + "fm_angle_sample_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(path, pre + "fm_angle_count.npy"), np.array([cnt], dtype=np.float64))
+
+
 def run_rank(args):
     import torch
     import torch.distributed as dist
@@ -899,20 +947,22 @@ def run_rank(args):
             dist.barrier()
         eng.sync()
 
-    # cold figures: the first step this process runs (one-off costs: code object load, the taps' spectrum, tables) and the 19
-    # steps after it, before any pre-roll (HIP events on the launch stream).  tools/debug/cold_steps.py shows the profile: launch 1
+    # --full: cold figures: the first step this process runs (one-off costs: code object load, the taps' spectrum, tables) and the
+    # 19 steps after it, before any pre-roll (HIP events on the launch stream).  tools/debug/cold_steps.py shows the profile: launch 1
     # ~8 ms, launches 2-6 at the steady time, then 15-35 % slower for ~80 launches while the power controller settles
-    cold_steps = 20
-    f0, c0, c1 = eng.events() + (eng.events()[0],)
-    f0.record()
-    step()
-    c0.record()
-    for _ in range(cold_steps - 1):
+    first_ms = cold_ms = 0.0
+    if args.full:
+        cold_steps = 20
+        f0, c0, c1 = eng.events() + (eng.events()[0],)
+        f0.record()
         step()
-    c1.record()
-    eng.sync()
-    first_ms = f0.elapsed_time(c0)
-    cold_ms = c0.elapsed_time(c1) / (cold_steps - 1)
+        c0.record()
+        for _ in range(cold_steps - 1):
+            step()
+        c1.record()
+        eng.sync()
+        first_ms = f0.elapsed_time(c0)
+        cold_ms = c0.elapsed_time(c1) / (cold_steps - 1)
 
     ramp_steps = 0
     t_ramp = time.perf_counter()
@@ -936,17 +986,21 @@ def run_rank(args):
     barrier()
     dt = time.perf_counter() - t0
     kern_ms = ev0.elapsed_time(ev1) / args.steps
+    if args.dump_outputs:
+        dump_outputs(eng, args.dump_outputs, rank, world)
 
-    # the same step for >= --steady-ms of device time (20 steps are ~3 ms; the default 6 s also makes the run visible to an
+    # --full: the same step for >= --steady-ms of device time (20 steps are ~3 ms; the default 6 s also makes the run visible to an
     # activity sampler that looks every few seconds): consistency check of the short region
-    long_steps = max(args.steps, int(np.ceil((min(args.steady_ms, 50.0) if stub else args.steady_ms) / max(kern_ms, 1e-3))))
-    l0, l1 = eng.events()
-    l0.record()
-    for i in range(long_steps):
-        step()
-    l1.record()
-    barrier()
-    long_ms = l0.elapsed_time(l1) / long_steps
+    long_steps, long_ms = 0, 0.0
+    if args.full:
+        long_steps = max(args.steps, int(np.ceil((min(args.steady_ms, 50.0) if stub else args.steady_ms) / max(kern_ms, 1e-3))))
+        l0, l1 = eng.events()
+        l0.record()
+        for i in range(long_steps):
+            step()
+        l1.record()
+        barrier()
+        long_ms = l0.elapsed_time(l1) / long_steps
 
     tmax = torch.tensor([dt, kern_ms, long_ms, cold_ms, first_ms], dtype=torch.float64, device=cdev)
     per_rank = None
@@ -964,7 +1018,7 @@ def run_rank(args):
         ri = torch.tensor([rccl_init_s], dtype=torch.float64, device=cdev)
         dist.all_reduce(ri, op=dist.ReduceOp.MAX)
         extra["rccl_init_s"] = round(float(ri[0]), 3)          # rendezvous + process group + first collective, slowest rank
-    if dist_on and not args.no_gather:
+    if dist_on and args.full and not args.no_gather:
         from directdemod_amd import shard
         shard_out, cnt = eng.shard_output()                 # this rank's outputs (a view) and how many are valid
         if one_device:
@@ -989,14 +1043,15 @@ def run_rank(args):
         extra["all_gather_ms_per_step"] = round(float(tg[0]) / args.steps * 1e3, 4)
         extra["gathered_outputs"] = total_out
 
-    if not stub:
+    if args.full and not stub:
         # sanity: the output is a demodulated 1 kHz tone of deviation 5 rad * 2 pi * 1 kHz / fs
         chk = eng.out[eng.first + 1000:eng.first + 1000 + 4096].double().cpu().numpy()
         extra["output_rms_rad"] = float(np.sqrt(np.mean(chk ** 2)))
     extra["clock_preroll"] = {"ms": args.ramp_ms, "steps": ramp_steps}
-    extra["first_step_ms"] = round(first_ms_max, 4)             # one-off: code object load, tap spectrum, tables
-    extra["cold_ms_per_step"] = round(cold_ms_max, 4)          # steps 2..20 of the process
-    extra["steady_check"] = {"steps": long_steps, "kernel_ms": round(long_ms_max, 4)}
+    if args.full:
+        extra["first_step_ms"] = round(first_ms_max, 4)             # one-off: code object load, tap spectrum, tables
+        extra["cold_ms_per_step"] = round(cold_ms_max, 4)          # steps 2..20 of the process
+        extra["steady_check"] = {"steps": long_steps, "kernel_ms": round(long_ms_max, 4)}
     if per_rank is not None:
         extra["kernel_ms_per_rank"] = per_rank
 
@@ -1026,7 +1081,7 @@ def run_rank(args):
                 power = json.load(open(pf)).get("kernels", {}).get(kname)
             except Exception:
                 power = None
-        if world == 1 and not stub and not args.no_side:
+        if args.full and world == 1 and not stub and not args.no_side:
             try:
                 extra["side"] = side_configs(eng)
             except Exception as e:                        # side lines never cost the headline line
@@ -1058,7 +1113,7 @@ def run_rank(args):
                          "power": power},      # (profiles/power.json: not measured in this run; says at which git revision it was)
             "extra": extra,
         }
-        if not args.no_cpu_baseline and world == 1 and not stub:
+        if args.full and not args.no_cpu_baseline and world == 1 and not stub:
             res["cpu_baseline"] = cpu_baseline(1 << args.cpu_log2n)
         print(json.dumps(res), flush=True)
     eng.close()
@@ -1076,17 +1131,25 @@ def parse_args(argv=None):
                          "chip holds under sustained load (the board's power controller takes ~20 ms to settle on it; "
                          "in between the kernel runs 15-35 %% slower)")
     ap.add_argument("--steady-ms", type=float, default=6000.0,
-                    help="device time of the steady-state check that follows the timed region (extra.steady_check)")
+                    help="--full: device time of the steady-state check that follows the timed region (extra.steady_check)")
     ap.add_argument("--log2n", type=int, default=26, help="samples per GPU = 2^log2n")
-    ap.add_argument("--gather", action="store_true", help="(default with more than one rank; kept for old command lines)")
-    ap.add_argument("--no-gather", action="store_true", help="more than one rank: skip the RCCL all_gather leg of the decoded output")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: first steps, steady-state check, "
+                         "output sanity figure, the gather leg with more than one rank, side configurations and CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the decoded output of the last timed step (edges, a fixed seeded sample, the count) as DIR/<name>.npy")
+    ap.add_argument("--gather", action="store_true", help="(default in a --full run with more than one rank; kept for old command lines)")
+    ap.add_argument("--no-gather", action="store_true", help="--full with more than one rank: skip the RCCL all_gather leg of the decoded output")
     ap.add_argument("--force-direct", action="store_true", help="f32 direct-form kernel instead of the MFMA path")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-side", action="store_true", help="skip the C3/C4 side lines (extra.side)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines (cpu_baseline)")
+    ap.add_argument("--no-side", action="store_true", help="--full: skip the C3/C4 side lines (extra.side)")
     ap.add_argument("--cpu-log2n", type=int, default=24)
     ap.add_argument("--simulate-rank", type=int, default=None,
                     help="debug: run this rank's shard (halo priming path) on one GPU without torch.distributed")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def main():

@@ -12,10 +12,11 @@ if ROOT not in sys.path:
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 # `-m gpu` runs the hot path FIRST (the chain kernels' parity against the oracle and the golden vectors, then the full-size
-# properties, then determinism), the audio-rate stages after it, and the two tests that start bench.py as child processes
-# (torch.distributed rendezvous, RCCL) LAST: whatever a box does to a rendezvous, the kernels' parity has been reported by then.
+# properties, then determinism), the audio-rate stages after it, and the tests that start bench.py as child processes (its
+# dumped outputs, then torch.distributed rendezvous, RCCL) LAST: whatever a box does to a rendezvous, the kernels' parity has been
+# reported by then.
 _ORDER = ("test_gpu_parity.py", "test_gpu_fullsize.py", "test_gpu_determinism.py", "test_gpu_audio.py",
-          "test_gpu_bench_ranks.py", "test_gpu_bench_nccl.py")
+          "test_gpu_bench_outputs.py", "test_gpu_bench_ranks.py", "test_gpu_bench_nccl.py")
 
 # one test may not hold the session longer than this (pytest-timeout's 120 s ends a test whose Python code is waiting; a
 # native call that never returns does not see the signal), and the session as a whole ends itself before a 1200 s outer limit

@@ -3,7 +3,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}; cd $R
 mkdir -p gpurun_out
 {
-  echo "== bench.py (headline, C2)";            python bench.py 2>/dev/null | tail -1
+  echo "== bench.py --full (headline, C2, side)"; python bench.py --full 2>/dev/null | tail -1
   echo "== tools/bench_configs.py";             timeout 600 python tools/bench_configs.py 2>/dev/null | tail -12
   echo "== tools/bench_u8.py";                  timeout 600 python tools/bench_u8.py 2>/dev/null | tail -6
   echo "== tools/bench_c3.py";                  timeout 600 python tools/bench_c3.py 2>/dev/null | tail -2

@@ -1,6 +1,6 @@
 #!/bin/bash
 # soak: many launches of the persistent kernels (barrier / LDS-counter hand-overs), bounded by timeouts
-timeout 120 python bench.py --no-cpu-baseline --steps 20000 --warmup 10 --ramp-ms 0 --steady-ms 100 --no-side | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['config']['kernel'], '20000 steps:', d['value'], d['ms_per_step'], d['extra']['output_rms_rad'])"
+timeout 120 python bench.py --full --no-cpu-baseline --steps 20000 --warmup 10 --ramp-ms 0 --steady-ms 100 --no-side | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['config']['kernel'], '20000 steps:', d['value'], d['ms_per_step'], d['extra']['output_rms_rad'])"
 timeout 600 python - <<'PY'
 # the three M = 1 FM kernels (k_chain_cos1k, the default for Hamming 255 since round 5, k_chain_fft1k and k_chain_mfma_ab): the whole output must be bit-identical
 # from launch to launch (no atomics on the data path: a race in the LDS hand-overs -- exchange images, boundary tables, range
