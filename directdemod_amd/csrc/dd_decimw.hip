@@ -174,10 +174,18 @@ struct DWMap {
     int c0m;           // (first window's start) mod M, minus M
     uint32_t minv;     // 2^32 / M + 1: x / M = umulhi(x, minv) for the x met here
 };
+// (host and device: dd_debug_decimb_lds_check evaluates the block-sum form's layout with the kernel's own address arithmetic)
+__host__ __device__ __forceinline__ uint32_t dw_umulhi(uint32_t a, uint32_t b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __umulhi(a, b);
+#else
+    return (uint32_t)(((uint64_t)a * b) >> 32);
+#endif
+}
 template <bool PAD>
-__device__ __forceinline__ int dw_pos(const DWMap& mp, int r) {
+__host__ __device__ __forceinline__ int dw_pos(const DWMap& mp, int r) {
     if (!PAD) return r;
-    return r + 2 * (int)__umulhi((uint32_t)(r - mp.c0m), mp.minv);
+    return r + 2 * (int)dw_umulhi((uint32_t)(r - mp.c0m), mp.minv);
 }
 
 // ---- complex64 rows: load j, lane l = samples 128 j + 2 l, + 1 of the block
@@ -466,7 +474,7 @@ struct DWRow {
     int r0, cnt;
     int64_t p0;
 };
-__device__ __forceinline__ void dw_row_next(const DDDecimWArgs& A, DWRow& r) {
+__host__ __device__ __forceinline__ void dw_row_next(const DDDecimWArgs& A, DWRow& r) {
     r.p0 += r.cnt;
     r.r0 -= DW_W % A.M;
     if (r.r0 < 0) r.r0 += A.M;
@@ -754,14 +762,17 @@ __device__ __forceinline__ v4f dw_lds_read16(uint32_t addr) {
     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(r) : "v"(addr), "n"(OFF));
     return r;
 }
+// PAD: how many bytes further on read u of step H (block samples 8 H + 2 u, + 1) lies behind the gap -- samples from j = M on sit in the
+// next block's layout.  Read u of step H starts 64 H + 16 u + this bytes behind the block's first sample.
+__host__ __device__ __forceinline__ uint32_t dw_bo_gap(int H, int u, int M) { return 8 * H + 2 * u >= M ? 16u : 0u; }
 template <bool PAD, int H>
 __device__ __forceinline__ void dw_bo_load(uint32_t addr, int M, DWOct<PAD>& d) {
     if constexpr (PAD) {
         // (the kept sample of a block that starts one sample early, j = M, sits behind the gap: sixteen bytes further on)
-        d.x[0] = dw_lds_read16<64 * H>(addr + (8 * H >= M ? 16u : 0u));
-        d.x[1] = dw_lds_read16<64 * H + 16>(addr + (8 * H + 2 >= M ? 16u : 0u));
-        d.x[2] = dw_lds_read16<64 * H + 32>(addr + (8 * H + 4 >= M ? 16u : 0u));
-        d.x[3] = dw_lds_read16<64 * H + 48>(addr + (8 * H + 6 >= M ? 16u : 0u));
+        d.x[0] = dw_lds_read16<64 * H>(addr + dw_bo_gap(H, 0, M));
+        d.x[1] = dw_lds_read16<64 * H + 16>(addr + dw_bo_gap(H, 1, M));
+        d.x[2] = dw_lds_read16<64 * H + 32>(addr + dw_bo_gap(H, 2, M));
+        d.x[3] = dw_lds_read16<64 * H + 48>(addr + dw_bo_gap(H, 3, M));
     } else {
         d.x[0] = dw_lds_read16<64 * H>(addr);
         d.x[1] = dw_lds_read16<64 * H + 16>(addr);
@@ -877,24 +888,49 @@ __device__ __forceinline__ void dw_bsums(const DDDecimWArgs& A, const float2* __
 }
 
 // the LDS layout of a PAD row of the block-sum form: gaps counted from its first block's start
-__device__ __forceinline__ int dw_b_first(const DDDecimWArgs& A, const DWRow& r) { return A.HP + r.r0 - A.M + 1 - A.e; }
-__device__ __forceinline__ DWMap dw_b_row_map(const DDDecimWArgs& A, const DWRow& r) {
+__host__ __device__ __forceinline__ int dw_b_first(const DDDecimWArgs& A, const DWRow& r) { return A.HP + r.r0 - A.M + 1 - A.e; }
+__host__ __device__ __forceinline__ DWMap dw_b_row_map(const DDDecimWArgs& A, const DWRow& r) {
     const int bs0 = dw_b_first(A, r);
-    const int k = (int)__umulhi((uint32_t)bs0, A.minv);
+    const int k = (int)dw_umulhi((uint32_t)bs0, A.minv);
     return DWMap{bs0 - k * A.M - A.M, A.minv};
+}
+// PAD: a row's last block is read in steps of eight samples, up to seven past its kept sample (under zero taps).  Past the row's last staged
+// sample these are cells the row does not write: nothing this launch wrote, or a sample an earlier row staged (the layout moves by two cells
+// from row to row) -- and 0 x NaN is NaN on the matrix pipe.  The DW_BTAIL cells behind the last staged one are cleared with every staged
+// row (dd_debug_decimb_lds_check)
+#define DW_BTAIL 8
+__host__ __device__ __forceinline__ int dw_b_tail(const DDDecimWArgs& A, const DWMap& mp) { return dw_pos<true>(mp, A.HP + DW_W - 2) + 2; }
+template <bool PAD>
+__device__ __forceinline__ void dw_b_tail_zero(const DDDecimWArgs& A, float2* buf, int lane, const DWMap& mp) {
+    if (PAD && lane < DW_BTAIL / 2) *reinterpret_cast<v4f*>(buf + dw_b_tail(A, mp) + 2 * lane) = (v4f){0.f, 0.f, 0.f, 0.f};
+}
+// the part of the row before a run that the run needs: the blocks of its last NI outputs (NI M < K + M samples back from the last kept one)
+__host__ __device__ __forceinline__ int dw_b_jlo(int M, int NI) {
+    const int rmin = DW_W - M - NI * M - 2;
+    return (rmin > 0 ? rmin : 0) >> 7;
 }
 
 // a staged row of the block-sum form: block sums, the sums travel up the lanes, the outputs leave, the halo moves down.  cy: the partial
 // sums the row before left for this row's first outputs (in), this row's for the next (out); ycarry as in dw_row_outputs.  emit false: the
 // row before a run -- one pass over its LAST 64 outputs, for cy, ycarry and the halo.
 // the block of the lane's output in pass t of a row (emit false: the one pass over the row's last 64 outputs)
+// (as three pieces: the first block's LDS sample, the lane's block, the stride)
+template <bool PAD>
+__host__ __device__ __forceinline__ int dw_b_first_at(const DDDecimWArgs& A, const DWRow& r) {
+    const int bs0 = dw_b_first(A, r);
+    return PAD ? bs0 + 2 * ((int)dw_umulhi((uint32_t)bs0, A.minv) + 1) : bs0;
+}
+__host__ __device__ __forceinline__ int dw_b_index(int lane, const DWRow& r, bool emit, int t) {
+    const int i = emit ? 64 * t + lane : r.cnt - 64 + lane;
+    return i < 0 ? 0 : (i < r.cnt ? i : r.cnt - 1);
+}
+template <bool PAD>
+__host__ __device__ __forceinline__ int dw_b_stride(const DDDecimWArgs& A) { return PAD ? A.M + 2 : A.M; }
 template <bool PAD>
 __device__ __forceinline__ const float2* dw_b_block(const DDDecimWArgs& A, const float2* buf, int lane, const DWRow& r, bool emit, int t) {
-    const int bs0 = dw_b_first(A, r);
-    const int bsp = PAD ? bs0 + 2 * ((int)__umulhi((uint32_t)bs0, A.minv) + 1) : bs0;
-    const int bstep = PAD ? A.M + 2 : A.M;
-    const int i = emit ? 64 * t + lane : r.cnt - 64 + lane;
-    const int ic = i < 0 ? 0 : (i < r.cnt ? i : r.cnt - 1);
+    const int bsp = dw_b_first_at<PAD>(A, r);
+    const int bstep = dw_b_stride<PAD>(A);
+    const int ic = dw_b_index(lane, r, emit, t);
     return buf + bsp + ic * bstep;
 }
 // pre0: the first pass's first reads have been requested (dw_bsums_begin on dw_b_block(.., 0))
@@ -1038,9 +1074,7 @@ __global__ void __launch_bounds__(64, DW_WAVES_PER_SIMD) k_chain_decim_b(const D
     if (gw == 0 && A.tail_out) dw_new_tail<U8, NCO>(A, lane);
     v2f ylast_in = (v2f){0.f, 0.f};
     if (FM && A.s == 0) ylast_in = dw_v2(*A.lasty_in);
-    // the part of the row before a run that the run needs: the blocks of its last NI outputs (NI M < K + M samples back from the last kept one)
-    const int rmin = DW_W - M - A.NI * M - 2;
-    const int jlo = (rmin > 0 ? rmin : 0) >> 7;
+    const int jlo = dw_b_jlo(M, A.NI);
 #ifdef DW_TRACE
     unsigned tr[DW_NPH];
 #pragma unroll
@@ -1090,6 +1124,7 @@ __global__ void __launch_bounds__(64, DW_WAVES_PER_SIMD) k_chain_decim_b(const D
                 if constexpr (U8) dw_stage_guarded<NCO, PAD, true>(A, buf, gl, lane, jlo, brel(q0 - 1), pw, mp);
                 else dw_stage_guarded<NCO, PAD>(A, buf, gl, lane, jlo, brel(q0 - 1), pw, mp);
             }
+            dw_b_tail_zero<PAD>(A, buf, lane, mp);
         }
         v2f ycarry = (v2f){0.f, 0.f};
         DWCarry cy;
@@ -1123,6 +1158,7 @@ __global__ void __launch_bounds__(64, DW_WAVES_PER_SIMD) k_chain_decim_b(const D
                 //  request in flight -- no gain, the launch sits on the memory system's rate, not on the bytes in flight; r06_decimb_notes.txt)
                 if constexpr (U8) dw_stage4<NCO, PAD, 0, DW_NL>(A, buf, gl, lane, pw, x8, mp);
                 else dw_stage<NCO, PAD, 0, DW_NL>(A, buf, gl, lane, pw, x, mp);
+                dw_b_tail_zero<PAD>(A, buf, lane, mp);
                 DW_T(0);
                 // (the block sums' first LDS reads ahead of the loads' address arithmetic)
                 dw_bsums_begin<PAD, NG>(A, dw_b_block<PAD>(A, buf, lane, r, true, 0), pre);
@@ -1133,6 +1169,7 @@ __global__ void __launch_bounds__(64, DW_WAVES_PER_SIMD) k_chain_decim_b(const D
             } else {
                 if constexpr (U8) dw_stage_guarded<NCO, PAD, true>(A, buf, gl, lane, 0, brel(q), pw, mp);
                 else dw_stage_guarded<NCO, PAD>(A, buf, gl, lane, 0, brel(q), pw, mp);
+                dw_b_tail_zero<PAD>(A, buf, lane, mp);
                 dw_bsums_begin<PAD, NG>(A, dw_b_block<PAD>(A, buf, lane, r, true, 0), pre);
             }
 #ifdef DW_TRACE
@@ -1246,6 +1283,128 @@ extern "C" int dd_debug_decimw_plan(int64_t abs0, int64_t Ld, int K, int M, int 
     return DD_OK;
 }
 
+// the launch constants of the LDS layout and the row walk
+static void dw_layout_args(const DWPlan& pl, int K, int M, DDDecimWArgs& A) {
+    A.K = K; A.K16 = pl.K16; A.M = M; A.HP = pl.HP;
+    A.e = pl.e; A.phi = pl.phi;
+    A.cq = (DW_W - 1) / M + 1; A.cr = (DW_W - 1) % M;
+    A.minv = (uint32_t)(0x100000000ull / (uint64_t)M) + 1u;
+    A.img = pl.img;
+    A.NI = pl.NI; A.nh = pl.nh; A.h1lo = pl.j1lo >> 3;
+}
+
+// k_chain_decim_b's LDS image over one run of rows, on the host, through the kernel's own address functions (dw_b_row_map, dw_pos,
+// dw_b_first_at / dw_b_index / dw_b_stride, dw_bo_gap, dw_b_tail, dw_b_jlo).  A run starts from the row before it (staged from load 12 -- pin -- or from load jlo --
+// guarded -- on, no halo, only its last NI blocks used) and walks on row by row (halo of the row before, all sixteen loads, every block).
+// Here the row before the run has its first kept sample at offset phi, and the run goes on until every row phase of the stream has come
+// once and the first once more (phi over [0, M) starts a run from each of them); a fresh image, both ways of staging the row before.  A cell
+// a row reads is good when this row wrote it (halo, staging, tail zeros) or it lies in the launch's zero fill, which no row writes.
+extern "C" int dd_debug_decimb_lds_check(int K, int M, int phi, int64_t* out) {
+    DD_REQUIRE(out && phi >= 0 && phi < M, "arguments");
+    if (!dd_decimw_supported(K, M, 0, nullptr)) {
+        dd_set_error("k_chain_decim_b takes even M in [8, 64] and 2 .. 256 taps");
+        return DD_ERR_UNSUPPORTED;
+    }
+    DWPlan pl;
+    decimw_plan(phi, 1 << 20, K, M, 0, 256, pl);               // (row 0's first kept sample at offset phi)
+    if (!pl.bsum) {
+        dd_set_error("K > 8 M: k_chain_decim_w");
+        return DD_ERR_UNSUPPORTED;
+    }
+    DDDecimWArgs A;
+    memset(&A, 0, sizeof(A));
+    dw_layout_args(pl, K, M, A);
+    const bool pad = pl.pad != 0;
+    const int ncell = pl.img + DW_NG;                           // the wave's LDS allocation (the NCO group phasors behind the image)
+    const int NG = pl.NI > 4 ? 2 : 1;
+    const int nread = pl.nh + (NG == 2 ? 1 : 2);               // steps requested: the MAC steps and the one or two requested ahead
+    static const int CAP = 4096;
+    if (ncell > CAP) { dd_set_error("LDS image"); return DD_ERR_UNSUPPORTED; }
+    int tag[CAP], seen[CAP];                                    // the row that last wrote a cell (-1: none, -2: the launch's zero fill)
+    auto pos = [&](const DWMap& mp, int r) { return pad ? dw_pos<true>(mp, r) : dw_pos<false>(mp, r); };
+    auto block_at = [&](int lane, const DWRow& r, bool emit, int t) {          // (dw_b_block's offset from the image's start)
+        return pad ? dw_b_first_at<true>(A, r) + dw_b_index(lane, r, emit, t) * dw_b_stride<true>(A)
+                   : dw_b_first_at<false>(A, r) + dw_b_index(lane, r, emit, t) * dw_b_stride<false>(A);
+    };
+    int64_t na = 0, nb = 0, rmin = INT64_MAX, rmax = -1, wmax = -1, pmax = -1, amin = -1, amax = -1, rows = 0;
+    // the row phases of the stream: row 0 has its first kept sample at phi, every later one W mod M earlier
+    DWRow r0;
+    r0.r0 = phi; r0.cnt = A.cq - (phi > A.cr ? 1 : 0); r0.p0 = 0;
+    int len = 0;
+    {
+        DWRow r = r0;
+        do { dw_row_next(A, r); ++len; } while (r.r0 != r0.r0);
+    }
+    ++len;
+    const DWRow start = r0;
+    for (int pin = 0; pin < 2; ++pin) {
+        for (int c = 0; c < ncell; ++c) { tag[c] = -1; seen[c] = -1; }
+        for (int c = pl.img - 2 * DW_PAD; c < pl.img; ++c) tag[c] = -2;
+        DWRow r = start;
+        DWMap mp = DWMap{0, A.minv};
+        int id = 0;
+        for (int q = -1; q < len; ++q, ++id) {
+            ++rows;
+            auto write = [&](int c) {
+                if (c > wmax) wmax = c;
+                if (c >= 0 && c < ncell) tag[c] = id;
+            };
+            if (q >= 0) {                                   // the halo: out of the row before's layout into this row's
+                dw_row_next(A, r);
+                const DWMap mpn = pad ? dw_b_row_map(A, r) : DWMap{0, A.minv};
+                for (int l = 0; l < A.HP / 2; ++l) { write(pos(mpn, 2 * l)); write(pos(mpn, 2 * l) + 1); }
+                mp = mpn;
+            } else if (pad) {
+                mp = dw_b_row_map(A, r);
+            }
+            const int j0 = q >= 0 ? 0 : (pin ? DW_NL - 4 : dw_b_jlo(M, A.NI));
+            for (int j = j0; j < DW_NL; ++j)
+                for (int l = 0; l < 64; ++l) {
+                    const int c = pos(mp, A.HP + 128 * j + 2 * l);
+                    write(c);
+                    write(c + 1);
+                }
+            if (pad)
+                for (int c = dw_b_tail(A, mp); c < dw_b_tail(A, mp) + DW_BTAIL; ++c) write(c);
+            // the reads: the blocks of the outputs that count (the row before a run: its last NI, which carry into the run)
+            auto read = [&](int c) {
+                if (c < rmin) rmin = c;
+                if (c > rmax) rmax = c;
+                if (c < 0 || c >= ncell) { ++na; return; }
+                if (seen[c] == id) return;
+                seen[c] = id;
+                if (tag[c] == id || tag[c] == -2) return;
+                if (tag[c] == -1) {
+                    ++na;
+                    if (amin < 0 || c < amin) amin = c;
+                    if (c > amax) amax = c;
+                } else {
+                    ++nb;
+                }
+            };
+            const bool emit = q >= 0;
+            const int npass = emit ? (r.cnt + 63) >> 6 : 1;
+            for (int t = 0; t < npass; ++t)
+                for (int l = 0; l < 64; ++l) {
+                    const int i = emit ? 64 * t + l : r.cnt - 64 + l;
+                    const int blk = block_at(l, r, emit, t);
+                    for (int H = 0; H < nread; ++H)
+                        for (int u = 0; u < 4; ++u) {
+                            const int c = blk + (64 * H + 16 * u + (int)(pad ? dw_bo_gap(H, u, M) : 0u)) / 8;
+                            if (c + 1 > pmax) pmax = c + 1;
+                            const bool used = emit ? i < r.cnt : i >= r.cnt - A.NI;
+                            if (H < pl.nh && used) { read(c); read(c + 1); }
+                        }
+                }
+            // the halo the next row takes: this row's last HP samples
+            for (int l = 0; l < A.HP / 2; ++l) { read(pos(mp, DW_W + 2 * l)); read(pos(mp, DW_W + 2 * l) + 1); }
+        }
+    }
+    out[0] = na; out[1] = nb; out[2] = rmin; out[3] = rmax; out[4] = pl.img; out[5] = wmax; out[6] = pmax; out[7] = rows;
+    out[8] = NG; out[9] = amin; out[10] = amax; out[11] = pl.pad;
+    return DD_OK;
+}
+
 static const void* decimw_kernel(bool u8, bool nco, bool fm, bool pad) {
     static const void* const k[16] = {
         (const void*)k_chain_decim_w<false, false, false, false>, (const void*)k_chain_decim_w<true, false, false, false>,
@@ -1333,12 +1492,8 @@ int dd_decimw_launch(const DDChainParams& P, const float* taps_g0, const double*
     A.cyc = P.cyc; A.abs0 = P.abs0; A.L = P.L; A.Ld = P.Ld;
     A.R0 = pl.R0;
     A.nrows = pl.nrows; A.nwaves = pl.nwaves; A.run_rows = pl.run_rows;
-    A.K = P.K; A.K16 = pl.K16; A.M = P.M; A.HP = pl.HP;
-    A.e = pl.e; A.phi = pl.phi; A.off = P.off; A.s = P.s;
-    A.cq = (DW_W - 1) / P.M + 1; A.cr = (DW_W - 1) % P.M;
-    A.minv = (uint32_t)(0x100000000ull / (uint64_t)P.M) + 1u;
-    A.img = pl.img;
-    A.NI = pl.NI; A.nh = pl.nh; A.h1lo = pl.j1lo >> 3;
+    dw_layout_args(pl, P.K, P.M, A);
+    A.off = P.off; A.s = P.s;
     {
         // rows of the launch that lie inside the chunk: abs0 <= (R0 + q) W and (R0 + q + 1) W <= abs0 + L
         const int64_t lo = dw_floordiv(P.abs0 - pl.R0 * DW_W + DW_W - 1, DW_W), hi = dw_floordiv(P.abs0 + P.L - pl.R0 * DW_W, DW_W);

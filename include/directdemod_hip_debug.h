@@ -49,6 +49,16 @@ int  dd_debug_cos1k_plan(int64_t L, int s, int out_align_elems, int ncu, int* ou
  *   k_chain_decim_w), partial sums per output ceil(K / M), first block sample of the second accumulator set, samples of the LDS image.
  *   DD_ERR_UNSUPPORTED when the kernels do not take (K, M). */
 int  dd_debug_decimw_plan(int64_t abs0, int64_t Ld, int K, int M, int off, int ncu, int64_t* out);
+/* dd_debug_decimb_lds_check -- k_chain_decim_b's LDS image for K taps, decimation M and stream phase phi (absolute index of the first kept
+ *   sample mod M), evaluated on the host with the kernel's own address functions: a run starts from a row before it whose first kept
+ *   sample sits at offset phi (staged in part, no halo; both ways of staging it) over a fresh image, and goes on row by row (halo of the
+ *   row before, whole row, tail zeros) until every row phase of the stream has come.  The cells that the matrix steps of the blocks that
+ *   reach an output read, zero taps included, and the halo: out[0] = reads of cells nothing wrote, out[1] = reads of cells that hold a
+ *   sample an EARLIER row wrote (the current one did not), out[2..3] = smallest and largest cell read, out[4] = cells of the image,
+ *   out[5] = largest cell written, out[6] = largest cell of any read requested (the steps read ahead included), out[7] = rows checked,
+ *   out[8] = accumulator sets (1 / 2), out[9..10] = smallest and largest cell counted in out[0] (-1: none), out[11] = 1 for the padded
+ *   image (M = 0 mod 4).  DD_ERR_UNSUPPORTED unless k_chain_decim_b takes (K, M). */
+int  dd_debug_decimb_lds_check(int K, int M, int phi, int64_t* out);
 int  dd_debug_cos_fit(const double* taps_host, int K, double* a_out, int* Q_out);
 int  dd_debug_sync_envelope(const void* X_dev, int64_t L, int nwin, int route, double* env_dev, void* stream);
 

@@ -341,3 +341,118 @@ def test_audio_side_stages_are_bit_reproducible(g):
         for k, (got, ref) in enumerate(zip(r, runs[0])):
             assert got.dtype == ref.dtype and got.shape == ref.shape, k
             assert np.array_equal(got.view(np.uint8), ref.view(np.uint8)), "stage output %d differs between runs" % k
+
+
+# k_chain_decim_b through the padded LDS image (M = 0 mod 4), at stream phases where a row's last block reads past the row's last staged
+# sample (phi = (first kept absolute index) mod M; dd_debug_decimb_lds_check, tests/test_decimb_layout.py) and at phi = 0
+PADDED_B = [(32, 151, (26, 30)), (40, 151, (2, 38)), (16, 33, (10, 14)), (64, 255, (58, 62)), (12, 65, (1, 11)), (20, 100, (3, 18)), (8, 33, (2, 6))]
+PADDED_PATTERNS = PATTERNS + (0x7F800000,)                      # + Inf (0 x Inf = NaN as well)
+START = 7 * 2048 + 333                                          # absolute index of the chunk's first sample: rows do not start with the chunk
+
+
+def _fused_handles(g, taps, fm):
+    lib, hip = g.lib, g.hip
+    taps = np.ascontiguousarray(taps, dtype=np.float64)
+    fir = C.c_void_p()
+    hip.check(lib.dd_fir_create(C.byref(fir), taps.ctypes.data_as(C.POINTER(C.c_double)), len(taps)), "dd_fir_create")
+    hip.check(lib.dd_fir_reset(fir, hip.DD_HIST_ZEROS, None, g.stream), "dd_fir_reset")
+    fmh = None
+    if fm:
+        fmh = C.c_void_p()
+        hip.check(lib.dd_fm_create(C.byref(fmh)), "dd_fm_create")
+    return fir, fmh
+
+
+def _fused_once(g, taps, M, fm, x, isz, n, start, off, flags, fill=None):
+    """one dd_fused_process call (NCO on, stream at absolute sample `start`, first kept sample at chunk index `off`) on fresh state"""
+    t, lib, hip = g.torch, g.lib, g.hip
+    fir, fmh = _fused_handles(g, taps, fm)
+    try:
+        if fill is not None:
+            hip.check(lib.dd_debug_fill_lds(fill, g.stream), "dd_debug_fill_lds")
+        per = 1 if fm else 2
+        out = t.full((per * (n // M + 2),), float("nan"), dtype=t.float32, device=g.dev)
+        got = C.c_int64(0)
+        hip.check(lib.dd_fused_process(fir, fmh, x.data_ptr(), out.data_ptr(), n, 1, hip.cycles_q64(25000.0, FS), start, M, off, flags, 1,
+                                       C.byref(got), g.stream), "dd_fused_process")
+        t.cuda.synchronize()
+        return out, got.value, lib.dd_fir_last_kernel(fir)
+    finally:
+        lib.dd_fir_destroy(fir)
+        if fmh is not None:
+            lib.dd_fm_destroy(fmh)
+
+
+@pytest.mark.parametrize("fm,u8", [(True, False), (False, False), (True, True), (False, True)])
+@pytest.mark.parametrize("M,ntaps,phis", PADDED_B)
+def test_padded_block_sums_are_bit_reproducible_after_lds_fills(g, M, ntaps, phis, fm, u8):
+    """k_chain_decim_b's padded image: a row's last block reads up to seven samples past its kept sample (under zero taps, on the matrix pipe,
+    where 0 x NaN is NaN); past the row's last staged sample those are cells the row clears.  Six rows per call (runs of two rows and the
+    row before each), NaN / zero / huge / Inf LDS fills: every output finite and the same bits after every fill."""
+    t, hip = g.torch, g.hip
+    n = 6 * 2048 + 1111
+    x = g.bench.make_input(t, n, START, g.dev, 77 + M)
+    flags, isz = 0, 8
+    if u8:
+        x = (x + 127.5).round().clamp(0, 255).to(t.uint8).contiguous()
+        flags, isz = hip.DD_CHAIN_U8_INPUT, 2
+    per = 1 if fm else 2
+    for phi in (0,) + tuple(phis):
+        off = (phi - START) % M
+        outs = []
+        for pat in PADDED_PATTERNS:
+            out, got, kern = _fused_once(g, _hamming(ntaps), M, fm, x, isz, n, START, off, flags, fill=pat)
+            assert kern == hip.DD_KERNEL_DECIM_BLOCKS, (phi, kern)
+            outs.append((out, got))
+        assert outs[0][1] == len(range(off, n, M)) - (1 if fm else 0)
+        _assert_identical(g, outs, per)
+
+
+@pytest.mark.parametrize("M,ntaps,phi", [(32, 151, 26), (40, 151, 38), (12, 65, 11)])
+@pytest.mark.parametrize("fm", [True, False])
+def test_padded_chunk_list_in_one_launch_equals_the_chunk_loop_after_lds_fills(g, M, ntaps, phi, fm):
+    """dd_fused_process_chunks (one k_chain_decim_b launch for the whole list) at a stream phase where rows read past their last staged
+    sample, after LDS fills: the outputs and per-chunk counts of the dd_fused_process loop, bit for bit."""
+    t, lib, hip = g.torch, g.lib, g.hip
+    n = 40000
+    cuts = [0, 1, 2047, 2048 + 5, 9001, 20011, 20012, n]
+    x = g.bench.make_input(t, n, START, g.dev, 5 + M)
+    off0 = (phi - START) % M
+    taps = _hamming(ntaps)
+    per = 1 if fm else 2
+    nfl = per * (n // M + 8)
+    cyc = hip.cycles_q64(25000.0, FS)
+    # the loop (after a NaN fill): every chunk carries the filter history, the FM sample and the decimation phase on
+    fir, fmh = _fused_handles(g, taps, fm)
+    hip.check(lib.dd_debug_fill_lds(0xFFFFFFFF, g.stream), "fill")
+    ref = t.full((nfl,), float("nan"), dtype=t.float32, device=g.dev)
+    counts, pos, off = [], 0, off0
+    got = C.c_int64(0)
+    for a, b in zip(cuts[:-1], cuts[1:]):
+        hip.check(lib.dd_fused_process(fir, fmh, x.data_ptr() + 8 * a, ref.data_ptr() + 4 * per * pos, b - a, 1, cyc, START + a, M, off, 0, 1,
+                                       C.byref(got), g.stream), "dd_fused_process")
+        counts.append(got.value)
+        pos += got.value
+        off = (off - (b - a)) % M
+    t.cuda.synchronize()
+    lib.dd_fir_destroy(fir)
+    if fmh is not None:
+        lib.dd_fm_destroy(fmh)
+    tot = per * pos
+    assert bool(t.isfinite(ref[:tot]).all())
+    bounds = (C.c_int64 * len(cuts))(*cuts)
+    nout = (C.c_int64 * (len(cuts) - 1))()
+    for pat in PADDED_PATTERNS:
+        fir, fmh = _fused_handles(g, taps, fm)
+        hip.check(lib.dd_debug_fill_lds(pat, g.stream), "fill")
+        out = t.full((nfl,), float("nan"), dtype=t.float32, device=g.dev)
+        hip.check(lib.dd_fused_process_chunks(fir, fmh, x.data_ptr(), out.data_ptr(), bounds, len(cuts) - 1, 1, cyc, START, M, off0, 0, nout,
+                                              g.stream), "dd_fused_process_chunks")
+        t.cuda.synchronize()
+        assert lib.dd_fir_last_kernel(fir) == hip.DD_KERNEL_DECIM_BLOCKS
+        lib.dd_fir_destroy(fir)
+        if fmh is not None:
+            lib.dd_fm_destroy(fmh)
+        assert list(nout) == counts
+        diff = int((out[:tot].view(t.int32) != ref[:tot].view(t.int32)).sum())
+        assert diff == 0, "%d of %d output words differ from the chunk loop (fill %#x)" % (diff, tot, pat)

@@ -803,12 +803,104 @@ def test_a_non_finite_sample_reaches_its_own_outputs_only(dd, M, K):
     assert lib.dd_chain_last_kernel(h) == hip.DD_KERNEL_DECIM_BLOCKS
     lib.dd_chain_destroy(h)
     y = o.to_host()[:got.value]
+    _assert_a_non_finite_sample_reaches_its_own_outputs_only(y, np.arange(0, L, M), pos, K, M)
+
+
+def _assert_a_non_finite_sample_reaches_its_own_outputs_only(y, kept, pos, K, M):
+    """y: the outputs at chunk indices `kept`, the input sample at chunk index `pos` non-finite"""
     bad = np.nonzero(~np.isfinite(y))[0]
-    kept = np.arange(0, L, M)
     ref_bad = np.nonzero((kept >= pos) & (kept - (K - 1) <= pos))[0]          # the reference: outputs whose window [n - K + 1, n] holds the sample
     NI = -(-K // M)
     assert len(ref_bad) <= len(bad) <= NI and set(ref_bad) <= set(bad), (list(bad), list(ref_bad))
     assert bad.min() == ref_bad.min() and bad.max() - bad.min() == len(bad) - 1 and bad.max() <= ref_bad.max() + 1
+
+
+# k_chain_decim_b through the padded LDS image (M = 0 mod 4) at stream phases where a row's last block reads past the row's last staged sample
+# (phi = (first kept absolute index) mod M; dd_debug_decimb_lds_check, tests/test_decimb_layout.py)
+_ROW_START = 100 * 2048 + 517                                 # absolute index of the chunk's first sample: rows do not start with the chunk
+
+
+def _fused_decim(dd, taps, M, x, start, off, fm_on, fill=None):
+    """one dd_fused_process call over complex64 `x` (NCO at 30 kHz, stream at absolute sample `start`, first kept sample at chunk index off),
+    zero FIR history, no FM sample before it; returns (outputs, kernel)"""
+    import ctypes as C
+    hip = dd.hip
+    lib = hip.lib()
+    fs = 2048000
+    K = len(taps)
+    fir = C.c_void_p()
+    hip.check(lib.dd_fir_create(C.byref(fir), taps.ctypes.data_as(C.POINTER(C.c_double)), K))
+    hip.check(lib.dd_fir_reset(fir, hip.DD_HIST_ZEROS, None, None))
+    fmh = None
+    if fm_on:
+        fmh = C.c_void_p()
+        hip.check(lib.dd_fm_create(C.byref(fmh)))
+    src = hip.DevArray.from_host(x, dtype=np.complex64)
+    kept = len(range(off, len(x), M))
+    o = hip.DevArray(max(1, kept), np.float32 if fm_on else np.complex64)
+    got = C.c_int64(0)
+    if fill is not None:
+        hip.check(lib.dd_debug_fill_lds(fill, None))
+    hip.check(lib.dd_fused_process(fir, fmh, src.ptr, o.ptr, len(x), 1, hip.cycles_q64(30000.0, fs), start, M, off, 0, 1, C.byref(got), None))
+    kern = lib.dd_fir_last_kernel(fir)
+    lib.dd_fir_destroy(fir)
+    if fmh is not None:
+        lib.dd_fm_destroy(fmh)
+    assert got.value == kept - (1 if fm_on else 0)
+    return o.to_host()[:got.value], kern
+
+
+@pytest.mark.parametrize("M,K", [(8, 33), (12, 65), (16, 33), (32, 151), (40, 151), (64, 255)])
+@pytest.mark.parametrize("fm_on", [False, True])
+def test_padded_block_sums_after_a_nan_fill_match_float64_at_every_phase(dd, M, K, fm_on):
+    """k_chain_decim_b's padded image at every stream phase (M = 64: sixteen of them, the three where rows read past their last staged sample
+    among them), each launch right after dd_debug_fill_lds(NaN), against the float64 oracle on the same decimation grid: catches a wrong
+    result that repeats from launch to launch, which the bit-reproducibility tests cannot."""
+    fs, L = 2048000, 5 * 2048 + 700
+    x = O.grid_c64(O.synth_iq_fm(L, fs, 900 + M, f_carrier=30000.0, f_mod=900.0, dev=3.0, start=_ROW_START))
+    taps = np.ascontiguousarray(O.firwin_lowpass(K, 0.45 / M))
+    y = O.lfilter_fir(taps, np.concatenate([np.zeros(K - 1, dtype=np.complex128), O.nco(x, 30000.0, fs, _ROW_START)]), None)[K - 1:]
+    phis = range(M) if M < 64 else sorted(set(range(0, 64, 5)) | {58, 60, 62})
+    for phi in phis:
+        off = (phi - _ROW_START) % M
+        got, kern = _fused_decim(dd, taps, M, x, _ROW_START, off, fm_on, fill=0xFFFFFFFF)
+        assert kern == dd.hip.DD_KERNEL_DECIM_BLOCKS, phi
+        yk = y[off::M]
+        assert np.all(np.isfinite(got)), phi
+        if fm_on:
+            ref, _ = O.fm_demod(yk, None)
+            fm_check(got, ref, np.abs(yk[1:] * np.conj(yk[:-1])))
+        else:
+            assert rel_err(got, yk) < FIR_TOL, phi
+
+
+@pytest.mark.parametrize("M,K,phi", [(32, 151, 26), (32, 151, 30), (16, 33, 14), (40, 151, 2), (40, 151, 20), (12, 65, 11), (64, 255, 62),
+                                     (8, 33, 4), (34, 151, 5)])
+@pytest.mark.parametrize("at", [2040, 2043, 2046, 2047, 0])
+def test_a_non_finite_sample_at_a_row_end_reaches_its_own_outputs_only(dd, M, K, phi, at):
+    """The locality rule above where it is hardest to keep: the non-finite sample at one of a row's last eight samples (absolute index = `at`
+    mod 2048) or its first one, at stream phases where a row's last block reads past its last staged sample (the padded image's layout moves
+    by two cells from row to row: a sample one row staged must not reach the next row's outputs).  Zero LDS fill first, so that what shows
+    is the input's own sample; dd_fused_process at a stream start off the row grid, ten rows.  The bound here is one output more on EACH side of
+    the reference's (the rule above allows one after it): the last step of eight samples of a block also multiplies up to seven samples after
+    its kept sample under zero taps, so a sample there reaches that output too (0 x NaN; INTEGRATION.md, deviations of k_chain_decim_b) -- and
+    never an output of another row."""
+    fs, L = 2048000, 10 * 2048 + 999
+    x = O.grid_c64(O.synth_iq_fm(L, fs, 555 + M + at, f_carrier=30000.0, f_mod=900.0, dev=3.0, start=_ROW_START)).copy()
+    pos = (5 * 2048 + at - _ROW_START) % 2048 + 4 * 2048       # chunk index of absolute index = at mod 2048, in the chunk's fifth or sixth row
+    assert (_ROW_START + pos) % 2048 == at and 2048 < pos < L - 2048
+    x[pos] = np.nan + 0j
+    taps = np.ascontiguousarray(O.firwin_lowpass(K, 0.45 / M))
+    off = (phi - _ROW_START) % M
+    y, kern = _fused_decim(dd, taps, M, x, _ROW_START, off, False, fill=0x00000000)
+    assert kern == dd.hip.DD_KERNEL_DECIM_BLOCKS
+    kept = np.arange(off, L, M)
+    bad = np.nonzero(~np.isfinite(y))[0]
+    ref_bad = np.nonzero((kept >= pos) & (kept - (K - 1) <= pos))[0]          # the reference: outputs whose window [n - K + 1, n] holds the sample
+    assert len(ref_bad) > 0 and set(ref_bad) <= set(bad), (list(bad), list(ref_bad))
+    assert bad.max() - bad.min() == len(bad) - 1 and bad.min() >= ref_bad.min() - 1 and bad.max() <= ref_bad.max() + 1, (list(bad), list(ref_bad))
+    if bad.min() < ref_bad.min():                                              # (only the output whose kept sample lies at most 7 before it)
+        assert 0 < pos - kept[bad.min()] <= 7, (pos, kept[bad.min()])
 
 
 @pytest.mark.parametrize("seed", range(40))
