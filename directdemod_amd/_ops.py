@@ -181,3 +181,60 @@ def filtfilt(taps, x):
     else:
         raise TypeError("unsupported dtype %s" % x.dtype)
     return out
+
+
+def median_segments(src, off, length, out=None):
+    """np.median of each segment src[off[i] : off[i] + length[i]] (decode_noaa.py:312-377); float64 device array of the medians"""
+    if src.dtype != _F64:
+        raise TypeError("median_segments expects float64")
+    off = np.ascontiguousarray(off, dtype=np.int64)
+    length = np.ascontiguousarray(length, dtype=np.int64)
+    if off.shape != length.shape:
+        raise ValueError("offsets and lengths differ in shape")
+    if np.any(off < 0) or np.any(length < 0) or np.any(off + length > src.n):
+        raise IndexError("segment outside the source")
+    if out is None:
+        out = DevArray(len(off), _F64)
+    pi = C.POINTER(C.c_int64)
+    check(lib().dd_median_segments_f64(src.ptr, off.ctypes.data_as(pi), length.ctypes.data_as(pi), len(off), out.ptr, None),
+          "dd_median_segments_f64")
+    return out
+
+
+def apt_lines(env, starts, lengths, sync_off, sync_mask, sync_bits, stream_len):
+    """Half-lines of the envelope -> (pixel medians [halves x 1040], sync-pixel stream), decode_noaa.py:330-359, 428-430"""
+    starts = np.ascontiguousarray(starts, dtype=np.int64)
+    lengths = np.ascontiguousarray(lengths, dtype=np.int64)
+    sync_off = np.ascontiguousarray(sync_off, dtype=np.int64).reshape(-1)
+    nh = len(starts)
+    if lengths.shape != (nh,) or sync_off.shape != (2 * nh,):
+        raise ValueError("line table shapes")
+    nwork = int(np.sum((lengths // 1040) * 1040))
+    work = DevArray(max(1, nwork), _F64)
+    pix = DevArray(max(1, nh * 1040), _F64)
+    sync = DevArray(max(1, int(stream_len)), _F64)
+    pi = C.POINTER(C.c_int64)
+    check(lib().dd_apt_lines_f64(env.ptr, env.n, starts.ctypes.data_as(pi), lengths.ctypes.data_as(pi), nh,
+                                 sync_off.ctypes.data_as(pi), int(sync_mask), int(sync_bits), work.ptr, pix.ptr, sync.ptr, None),
+          "dd_apt_lines_f64")
+    return pix, sync
+
+
+def apt_map(pix, nrows, row_len, params):
+    """per-row (mode, a, b) -> uint8 rows (decode_noaa.py:436-455)"""
+    params = np.ascontiguousarray(params, dtype=np.float64).reshape(-1)
+    if params.size != 3 * nrows or pix.n < nrows * row_len:
+        raise ValueError("mapping shapes")
+    out = DevArray(max(1, nrows * row_len), np.uint8)
+    check(lib().dd_apt_map_u8(pix.ptr, int(nrows), int(row_len), params.ctypes.data_as(C.POINTER(C.c_double)), out.ptr, None),
+          "dd_apt_map_u8")
+    return out
+
+
+def apt_color(img, nrows, row_len):
+    """getColor's false colour of uint8 rows [A | B] (decode_noaa.py:537-598) -> uint8 [rows x 1040 x 3]"""
+    if img.dtype != np.dtype(np.uint8) or img.n < nrows * row_len or row_len < 2080:
+        raise ValueError("colour shapes")
+    out = DevArray(max(1, nrows * 1040 * 3), np.uint8)
+    check(lib().dd_apt_color_u8(img.ptr, int(nrows), int(row_len), out.ptr, None), "dd_apt_color_u8")
+    return out

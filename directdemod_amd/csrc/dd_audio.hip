@@ -1,7 +1,7 @@
 // Audio-rate rows of the NOAA tail (R2, A1, X1, X2, and 8f-2 / P: the accurate-sync windows and the crude tail), float64 on the
 // device so that sync index picks stay bit-exact (H7).  Sizes here are 1e5 .. 1e7 samples.  This file holds what the families share -- the FFT
 // library's plan cache (the stand-alone class routes only), the own float64 cyclic convolution of 2^17 / 2^18 points (dd_hconv_kernels.h) and
-// its tables -- and includes the five parts (dd_audio_envelope.h, dd_audio_resample.h, dd_audio_xcorr.h, dd_audio_sync.h, dd_audio_crude.h):
+// its tables -- and includes the six parts (dd_audio_envelope.h, dd_audio_resample.h, dd_audio_xcorr.h, dd_audio_sync.h, dd_audio_crude.h, dd_audio_apt.h):
 // one translation unit, split by entry-point family in round 6.
 #include "dd_common.h"
 #include <hipfft/hipfft.h>
@@ -157,6 +157,7 @@ void dd_audio_forget_stream(hipStream_t s) {
 #include "dd_audio_xcorr.h"         // X1, X2   dd_xcorr_norm_f64, dd_find_peaks_f64
 #include "dd_audio_sync.h"          // 8f-2  dd_noaa_sync_windows(_multi), dd_noaa_prepare
 #include "dd_audio_crude.h"         // P     dd_noaa_crude_tail
+#include "dd_audio_apt.h"           // APT image: dd_median_segments_f64, dd_apt_lines_f64, dd_apt_map_u8, dd_apt_color_u8
 
 // dd_code_warmup (dd_runtime.hip): the runtime loads a translation unit's code object when one of its kernels is first named
 int dd_code_touch_audio(void) {

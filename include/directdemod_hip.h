@@ -359,6 +359,25 @@ int dd_afsk_binary_filter_f64(const double* sig, int64_t n, const double* tables
 /* out = np.correlate(np.sign(binary_filter), [-1]*(spb/2) + [1]*(spb - spb/2), 'same') / spb (:147-156) */
 int dd_afsk_edges_f64(const double* binary_filter, int64_t n, int spb, double* out, void* stream);
 
+/* APT image extraction (decode_noaa.getImage / getColor).
+ * dd_median_segments_f64 -- out[i] = np.median(src[off_host[i] : off_host[i] + len_host[i]]) for `count` segments (device out):
+ *      numpy's semantics (odd: middle element, even: (a + b) / 2, empty or holding a NaN: NaN); segments of any length.
+ * dd_apt_lines_f64 -- half-line h is the len_host[h] envelope samples at env + start_host[h]: scipy.signal.resample to
+ *      num = (len / 1040) * 1040 into work (sum of num doubles, half after half), then pix[h][p] = median of the k = num / 1040
+ *      values of pixel p (pix: nhalf x 1040; NaN when k = 0).  sync_off_host[2h], [2h + 1]: element offsets into sync_stream where
+ *      the k values of each of pixels 0 .. sync_bits-1 go, pixel after pixel, to the low (bit of sync_mask clear) or the high part
+ *      (bit set); -1 = none.
+ * dd_apt_map_u8 -- out = clip(rint(v), 0, 255) as uint8 per row r of pix (nrows x row_len), with par_host[r] = (mode, a, b):
+ *      mode 0: v = 255 * (x - a) / (b - a); mode 1: v = x * a + b (numpy's operation order, no fused multiply-adds).
+ * dd_apt_color_u8 -- the false colour of getColor: v = img[r][c], t = img[r][1040 + c] (c < 1040) -> out[r][c][3] (RGB),
+ *      colorsys.hsv_to_rgb and int(k * 255.0) in the reference's operation order. */
+int dd_median_segments_f64(const double* src, const int64_t* off_host, const int64_t* len_host, int count, double* out, void* stream);
+int dd_apt_lines_f64(const double* env, int64_t n_env, const int64_t* start_host, const int64_t* len_host, int nhalf,
+                     const int64_t* sync_off_host, uint64_t sync_mask, int sync_bits, double* work, double* pix,
+                     double* sync_stream, void* stream);
+int dd_apt_map_u8(const double* pix, int64_t nrows, int row_len, const double* par_host, uint8_t* out, void* stream);
+int dd_apt_color_u8(const uint8_t* img, int64_t nrows, int row_len, uint8_t* out, void* stream);
+
 /* np.abs for demod_am.demod_amFLT (demod_am.py:35-62: butter low-pass of |sig|).
  * kind 0: float64, 1: complex128, 2: complex64 input; float64 output (hypot). */
 int dd_abs_f64(const void* in, int kind, double* out, int64_t n, void* stream);

@@ -133,6 +133,112 @@ def gen_c4_60s():
     print("noaa_c4_60s: crude A %d B %d, accurate A %d B %d, useful %d" % (len(sa), len(sb), len(acc[0]), len(acc[4]), nobj.useful))
 
 
+def _apt_run(raw, fs):
+    """the reference's getImage (and what it needs from its own run: the envelope it extracted the lines from) on one recording"""
+    import time
+    from directdemod import decode_noaa
+    src = ArraySource(raw, fs)
+    nobj = decode_noaa.decode_noaa(src, 30000.0)
+    cap = []
+    get_am = nobj._decode_noaa__getAM
+
+    def _am_tap(sig):
+        out = get_am(sig)
+        cap.append(np.array(out.signal))
+        return out
+    nobj._decode_noaa__getAM = _am_tap
+    nobj.getCrudeSync()
+    t0 = time.perf_counter()
+    img = nobj.getImage
+    dt = time.perf_counter() - t0
+    return nobj, np.asarray(img), cap[-1], dt
+
+
+def _apt_line_inputs(nobj, env, rate):
+    """per decoded line, from the reference's envelope: the two strip medians and the two sync FIFO medians (:348-377), with the
+    package's host line table; the inputs of the host calibration state machine"""
+    import scipy.signal as ss
+    from directdemod_amd import decode_noaa as dn, constants as C
+    n = len(env)
+    sa, sb = nobj.getCrudeSync()
+    unc = dn.to_rate(sa, rate, rate)
+    fa, fb = dn.fill_sync(unc, n), dn.fill_sync(dn.to_rate(sb, rate, rate), n)
+    a, b = dn.pair_syncs(fa, fb, rate)
+    rows = dn.line_table(a, b, unc, rate, n)
+    L1 = int((len(C.NOAA_SYNCA) * C.NOAA_T) * rate)
+    low, high, s1, s2, ml, mh, use = [], [], [], [], [], [], []
+    for (s_a, e_a, s_b, e_b, u) in rows:
+        x = env[s_a:e_a]
+        num = (len(x) // 1040) * 1040
+        la = np.reshape(ss.resample(x, num), (1040, num // 1040))
+        if u:
+            for j in range(len(C.NOAA_SYNCA)):
+                (low if C.NOAA_SYNCA[j] == 0 else high).extend(la[j])
+                low, high = low[-C.NOAA_COLORCORRECT_FIFOLEN:], high[-C.NOAA_COLORCORRECT_FIFOLEN:]
+        ml.append(np.median(low) if u else np.nan)
+        mh.append(np.median(high) if u else np.nan)
+        s1.append(np.median(env[s_a - L1:s_a]))
+        s2.append(np.median(env[s_b - L1:s_b]))
+        use.append(u)
+    return {"line_strip_a": np.array(s1), "line_strip_b": np.array(s2), "line_sync_low": np.array(ml),
+            "line_sync_high": np.array(mh), "line_use": np.array(use, dtype=bool)}
+
+
+def gen_apt_image():
+    """getImage / channelID / getColor of the reference on two synthetic recordings (decode_noaa.py:255-598):
+      apt_image_plain.npz      synth_apt_iq(20 s, seed 1): no telemetry, backupImage; low / high, the __fillSync lists
+      apt_image_telemetry.npz  tests/_apt_telemetry.py (44 s): the calibrated path; slope / intercept, channel IDs, getColor,
+                               and the per-line inputs of the calibration state machine
+    gen_golden.py --apt-image"""
+    install_shim()
+    sys.path.insert(0, REF)
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from oracle import dd_oracle as O
+    from _apt_telemetry import synth_apt_telemetry_iq
+    fs = 2048000
+
+    dur = 20.0
+    nobj, img, env, dt = _apt_run(O.synth_apt_iq(dur, fs, seed=1), fs)
+    sa, sb = nobj.getCrudeSync()
+    rate = nobj._decode_noaa__syncCrudeSampRate
+    ca = np.asarray(sa) / rate
+    ca *= rate
+    cb = np.asarray(sb) / rate
+    cb *= rate
+    g = {"dur": np.float64(dur), "seed": np.int64(1), "image": img.astype(np.uint8),
+         "channel_id": np.array([-1 if v is None else v for v in nobj.channelID], dtype=np.int64),
+         "low": np.float64(nobj._decode_noaa__low), "high": np.float64(nobj._decode_noaa__high),
+         "crude_syncA": np.asarray(sa, dtype=np.int64), "crude_syncB": np.asarray(sb, dtype=np.int64), "rate": np.int64(rate),
+         "n_env": np.int64(len(env)),
+         "fill_syncA": np.asarray(nobj._decode_noaa__fillSync(ca, len(env)), dtype=np.float64),
+         "fill_syncB": np.asarray(nobj._decode_noaa__fillSync(cb, len(env)), dtype=np.float64),
+         "ref_getimage_s": np.float64(dt)}
+    assert nobj._decode_noaa__slope is None
+    np.savez_compressed(os.path.join(OUT, "apt_image_plain.npz"), **g)
+    print("apt_image_plain: image", img.shape, "low %.6g high %.6g" % (g["low"], g["high"]), "getImage %.3f s" % dt)
+
+    dur = 44.0
+    nobj, img, env, dt = _apt_run(synth_apt_telemetry_iq(dur, fs), fs)
+    rate = nobj._decode_noaa__syncCrudeSampRate
+    assert nobj._decode_noaa__slope is not None, "the calibrated path was not taken"
+    ch = nobj.channelID
+    assert ch[0] is not None and ch[1] is not None, ch
+    t0 = __import__("time").perf_counter()
+    col = np.asarray(nobj.getColor)
+    dtc = __import__("time").perf_counter() - t0
+    g = {"dur": np.float64(dur), "seed": np.int64(3), "image": img.astype(np.uint8), "channel_id": np.array(ch, dtype=np.int64),
+         "slope": np.float64(nobj._decode_noaa__slope), "intercept": np.float64(nobj._decode_noaa__intercept), "color": col,
+         "rate": np.int64(rate), "ref_getimage_s": np.float64(dt), "ref_getcolor_s": np.float64(dtc)}
+    m = len(env) // 2080
+    meds = np.median(np.reshape(env[:m * 2080], (2080, m)), axis=-1)
+    g["low0"], g["high0"] = [np.float64(v) for v in np.percentile(meds, (0.5, 99.5))]
+    g.update(_apt_line_inputs(nobj, env, rate))
+    np.savez_compressed(os.path.join(OUT, "apt_image_telemetry.npz"), **g)
+    print("apt_image_telemetry: image", img.shape, "channelID", ch, "slope %.6g intercept %.6g" % (g["slope"], g["intercept"]),
+          "getImage %.3f s getColor %.3f s" % (dt, dtc))
+
+
 C1_NAME = "synth_20180101_120000Z_145825000Hz_IQ.wav"       # (the name pattern lets main.py:167-173 parse the centre frequency)
 C1_FREQ = 145835000                                         # what a user would pass as -f: the signal sits 10 kHz above the centre
 
@@ -191,6 +297,8 @@ def main():
         return gen_c4_60s()
     if "--c1" in sys.argv:
         return gen_c1()
+    if "--apt-image" in sys.argv:
+        return gen_apt_image()
     only_afsk = "--afsk-only" in sys.argv
     install_shim()
     sys.path.insert(0, REF)
