@@ -151,6 +151,10 @@ SIGNATURES = {
                                   _pi64, _int, C.POINTER(_int), _p]),
     "dd_afsk_binary_filter_f64": (_int, [_p, _i64, C.POINTER(C.c_double), _int, _p, _p]),
     "dd_afsk_edges_f64": (_int, [_p, _i64, _int, _p, _p]),
+    "dd_peakdetect_f64": (_int, [_p, _i64, _i64, C.c_double, _p, _p, _i64, _p, _p, _i64, _pi64, _p]),
+    "dd_afsk_bits_f64": (_int, [_p, _i64, _p, _i64, C.c_double, _int, _i64, _p, _p, _p, _p, _p, _i64, _pi64, _p]),
+    "dd_afsk_frames_check": (_int, [_p, _p, _i64, _p, _i64, _pi64, _p]),
+    "dd_afsk_frames_pack": (_int, [_p, _p, _i64, _p, _i64, _pi64, _pi64, _p, _i64, _p]),
     "dd_median_segments_f64": (_int, [_p, _pi64, _pi64, _int, _p, _p]),
     "dd_apt_lines_f64": (_int, [_p, _i64, _pi64, _pi64, _int, _pi64, C.c_uint64, _int, _p, _p, _p, _p]),
     "dd_apt_map_u8": (_int, [_p, _i64, _int, C.POINTER(C.c_double), _p, _p]),

@@ -359,6 +359,29 @@ int dd_afsk_binary_filter_f64(const double* sig, int64_t n, const double* tables
 /* out = np.correlate(np.sign(binary_filter), [-1]*(spb/2) + [1]*(spb - spb/2), 'same') / spb (:147-156) */
 int dd_afsk_edges_f64(const double* binary_filter, int64_t n, int spb, double* out, void* stream);
 
+/* AFSK1200 frame logic behind the correlators (decode_afsk1200.py:160-269).
+ * dd_peakdetect_f64 -- peakdetect.peakdetect(y, lookahead=L, delta) (decode_afsk1200.py:160): the lookahead state machine over
+ *      y[0 .. n-L), exact for finite y (non-finite input: DD_ERR_INVALID).  Maxima (position, value) into max_pos / max_val, minima
+ *      into min_pos / min_val (device, capacities cap_*; n/2 + 2 is always enough), the first hit popped as the reference does;
+ *      counts_host[2] = how many of each.
+ * dd_afsk_bits_f64 -- from the maxima positions peaks[m] (device) and binary_filter bf[n]: bit_repeated = rint(diff(peaks) / (bw/1200))
+ *      (:189), per bit the mean of bf[x_i + r spb : x_i + (r+1) spb] in NumPy's summation order (:199-203; NaN for an empty slice),
+ *      sgn = np.sign of it (NaN as 2), bits = decode_nrzi (:208), marks = find_bit_stuffing (:229), flags = the start-flag positions
+ *      (:217-224).  Device outputs of capacity cap_bits / cap_flags; counts_host[2] = (bits, flags).
+ * dd_afsk_frames_check -- per consecutive flag pair i (:236-251): info_host[2i] = the count of unstuffed bits between them,
+ *      info_host[2i + 1] = 1 when the reference accepts it (count % 8 == 0, message > 128 bits, fcs_crc16 matches).
+ * dd_afsk_frames_pack -- the message bytes (the unstuffed bits but the last 16, LSB first, bits_to_msg's order) of every pair with
+ *      off_host[i] >= 0 to out + off_host[i] (device, out_bytes a multiple of 4, zeroed first). */
+int dd_peakdetect_f64(const double* y, int64_t n, int64_t lookahead, double delta, int64_t* max_pos, double* max_val,
+                      int64_t cap_max, int64_t* min_pos, double* min_val, int64_t cap_min, int64_t* counts_host, void* stream);
+int dd_afsk_bits_f64(const double* bf, int64_t n, const int64_t* peaks, int64_t m, double bw, int spb, int64_t cap_bits,
+                     double* mean, int8_t* sgn, int8_t* bits, int8_t* marks, int64_t* flags, int64_t cap_flags,
+                     int64_t* counts_host, void* stream);
+int dd_afsk_frames_check(const int8_t* bits, const int8_t* marks, int64_t nbits, const int64_t* flags, int64_t nflags,
+                         int64_t* info_host, void* stream);
+int dd_afsk_frames_pack(const int8_t* bits, const int8_t* marks, int64_t nbits, const int64_t* flags, int64_t nflags,
+                        const int64_t* info_host, const int64_t* off_host, uint8_t* out, int64_t out_bytes, void* stream);
+
 /* APT image extraction (decode_noaa.getImage / getColor).
  * dd_median_segments_f64 -- out[i] = np.median(src[off_host[i] : off_host[i] + len_host[i]]) for `count` segments (device out):
  *      numpy's semantics (odd: middle element, even: (a + b) / 2, empty or holding a NaN: NaN); segments of any length.

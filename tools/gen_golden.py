@@ -15,7 +15,9 @@ Compat shim (harness side, the reference is untouched):
   numpy.int                                      := int
 """
 import os
+import re
 import sys
+import time
 
 import numpy as np
 import scipy
@@ -292,7 +294,109 @@ def gen_c1():
           (raw.shape[0], fs, len(fm), int(fs / M), M, offset, os.path.getsize(os.path.join(OUT, "c1_afsk_front.npz"))))
 
 
+def _afsk_frames_run(src, offset):
+    """the reference's getMsg on `src` with taps: the np.correlate output, peakdetect's input and output, decode_nrzi's argument and
+    result, bits_to_msg's arguments, the redirected stdout, the return value and useful"""
+    import contextlib
+    import io
+    from directdemod import decode_afsk1200 as dafsk, peakdetect
+    cap = {"msg_bits": []}
+    _corr, _pd, _nrzi, _b2m = dafsk.np.correlate, peakdetect.peakdetect, dafsk.decode_afsk1200.decode_nrzi, dafsk.decode_afsk1200.bits_to_msg
+
+    def corr_tap(a, v, mode="valid"):
+        r = _corr(a, v, mode)
+        cap["edge_sums"] = np.array(r)
+        return r
+
+    def pd_tap(y, *a, **k):
+        r = _pd(y, *a, **k)
+        cap["pd_in"], cap["pd_out"], cap["pd_kw"] = np.array(y), r, k
+        return r
+
+    def nrzi_tap(x):
+        r = _nrzi(x)
+        cap["nrzi_in"], cap["bitstream"] = np.array(x), np.array(r, dtype=np.int8)
+        return r
+
+    def b2m_tap(bits):
+        cap["msg_bits"].append(np.array(bits, dtype=np.int8))
+        return _b2m(bits)
+    dafsk.np.correlate, dafsk.peakdetect.peakdetect = corr_tap, pd_tap
+    dafsk.decode_afsk1200.decode_nrzi, dafsk.decode_afsk1200.bits_to_msg = nrzi_tap, b2m_tap
+    out = io.StringIO()
+    t0 = time.process_time()
+    try:
+        with contextlib.redirect_stdout(out):
+            obj = dafsk.decode_afsk1200(src, offset, 22050)
+            msg = obj.getMsg
+    finally:
+        dafsk.np.correlate, dafsk.peakdetect.peakdetect = _corr, _pd
+        dafsk.decode_afsk1200.decode_nrzi, dafsk.decode_afsk1200.bits_to_msg = _nrzi, _b2m
+    cap["cpu_s"] = time.process_time() - t0
+    cap["stdout"], cap["msg"], cap["useful"] = out.getvalue(), msg, obj.useful
+    return cap
+
+
+def _afsk_frames_store(name, cap, extra):
+    from directdemod import framechecksequence
+    es = cap["edge_sums"]
+    assert np.array_equal(np.abs(np.round(es) / (22050 // 1200)), cap["pd_in"])     # peakdetect's input is |edge sums| / spb
+    bs = cap["bitstream"]
+    flags = [k for k in range(len(bs) - 8) if "".join(map(str, bs[k:k + 8])) == "01111110"]      # (:217-224, from the captured bits)
+    starts = [int(m) for m in re.findall(r"starts at (\d+)", cap["stdout"])]
+    fidx = [int(m) for m in re.findall(r"# (\d+) starts", cap["stdout"])]
+    mb = cap["msg_bits"]
+    g = dict(extra)
+    g.update({"edge_sums": np.round(es).astype(np.int16), "pd_lookahead": np.int64(cap["pd_kw"]["lookahead"]),
+              "pd_max_x": np.array([p[0] for p in cap["pd_out"][0]], dtype=np.int32),
+              "pd_max_y": np.array([p[1] for p in cap["pd_out"][0]], dtype=np.float64),
+              "pd_min_x": np.array([p[0] for p in cap["pd_out"][1]], dtype=np.int32),
+              "pd_min_y": np.array([p[1] for p in cap["pd_out"][1]], dtype=np.float64),
+              "nrzi_sign": cap["nrzi_in"].astype(np.int8), "bitstream": bs, "bit_startflag": np.array(flags, dtype=np.int32),
+              "frame_flag": np.array(fidx, dtype=np.int32), "frame_start": np.array(starts, dtype=np.int32),
+              "frame_bits_len": np.array([len(b) for b in mb], dtype=np.int32),
+              "frame_bits": np.concatenate(mb) if mb else np.zeros(0, np.int8),
+              "stdout": np.array(cap["stdout"]), "msg": np.array("" if cap["msg"] is None else cap["msg"]),
+              "useful": np.int64(cap["useful"]), "ref_cpu_s": np.float64(cap["cpu_s"])})
+    if name == "afsk_frames_a.npz":         # fcs_crc16 of seeded random bit strings of assorted lengths
+        rng = np.random.default_rng(77)
+        lens = rng.integers(1, 600, 200)
+        strs = [rng.integers(0, 2, k).astype(np.int8) for k in lens]
+        g["crc_lens"] = lens.astype(np.int32)
+        g["crc_bits"] = np.concatenate(strs)
+        g["crc_values"] = np.array([framechecksequence.fcs_crc16("".join(map(str, s))) for s in strs])
+    path = os.path.join(OUT, name)
+    np.savez_compressed(path, **g)
+    print("%s: %d peaks, %d bits, %d flags, %d frames, msg %r, useful %d, reference %.2f s CPU, %d bytes" %
+          (name, len(g["pd_max_x"]), len(bs), len(flags), len(mb), cap["msg"], cap["useful"], cap["cpu_s"], os.path.getsize(path)))
+
+
+def gen_afsk_frames():
+    """AFSK1200 frame logic (decode_afsk1200.py:160-269) on two recordings rebuilt from tests/_ax25.py: (a) 882 kS/s through an
+    in-memory source, (b) config 1's shape, a 2.4 MS/s WAV read by the reference's source.IQwav.   gen_golden.py --afsk-frames"""
+    install_shim()
+    np.Inf = np.inf                         # peakdetect.py still uses it; NumPy 2 dropped it
+    sys.path.insert(0, REF)
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import tempfile
+    import matplotlib
+    matplotlib.use("Agg")
+    from directdemod import source
+    import _ax25
+    raw, fs, offset, _ = _ax25.fixture_a()
+    _afsk_frames_store("afsk_frames_a.npz", _afsk_frames_run(ArraySource(raw, fs), offset), {"fs": np.int64(fs)})
+    raw, fs, offset, _ = _ax25.fixture_b()
+    with tempfile.TemporaryDirectory() as td:
+        path = os.path.join(td, _ax25.C1_NAME)
+        _ax25.write_wav(path, raw, fs)
+        cap = _afsk_frames_run(source.IQwav(path), offset)
+    _afsk_frames_store("afsk_frames_b.npz", cap, {"fs": np.int64(fs), "offset": np.int64(offset)})
+
+
 def main():
+    if "--afsk-frames" in sys.argv:
+        return gen_afsk_frames()
     if "--c4-60s" in sys.argv:
         return gen_c4_60s()
     if "--c1" in sys.argv:
