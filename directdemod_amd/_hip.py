@@ -155,6 +155,11 @@ SIGNATURES = {
     "dd_afsk_bits_f64": (_int, [_p, _i64, _p, _i64, C.c_double, _int, _i64, _p, _p, _p, _p, _p, _i64, _pi64, _p]),
     "dd_afsk_frames_check": (_int, [_p, _p, _i64, _p, _i64, _pi64, _p]),
     "dd_afsk_frames_pack": (_int, [_p, _p, _i64, _p, _i64, _pi64, _pi64, _p, _i64, _p]),
+    "dd_meteor_mix": (_int, [_p, _p, _i64, C.c_double, C.c_double, _p, _p]),
+    "dd_meteor_walk": (_int, [_p, _i64, _i64, _p, C.POINTER(C.c_double), _i64, _p, _p, _p, _p, _p, _p, _p]),
+    "dd_meteor_lim": (_int, [_p, _i64, _i64, _p, _i64, _p, _p, _i64, _p]),
+    "dd_meteor_minsync": (_int, [_p, _i64, _p, _p, _i64, _p, _p, _p]),
+    "dd_meteor_maxcorr": (_int, [_p, _i64, _p, _i64, _p, _p, _p]),
     "dd_median_segments_f64": (_int, [_p, _pi64, _pi64, _int, _p, _p]),
     "dd_apt_lines_f64": (_int, [_p, _i64, _pi64, _pi64, _int, _pi64, C.c_uint64, _int, _p, _p, _p, _p]),
     "dd_apt_map_u8": (_int, [_p, _i64, _int, C.POINTER(C.c_double), _p, _p]),

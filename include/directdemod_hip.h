@@ -382,6 +382,32 @@ int dd_afsk_frames_check(const int8_t* bits, const int8_t* marks, int64_t nbits,
 int dd_afsk_frames_pack(const int8_t* bits, const int8_t* marks, int64_t nbits, const int64_t* flags, int64_t nflags,
                         const int64_t* info_host, const int64_t* off_host, uint8_t* out, int64_t out_bytes, void* stream);
 
+/* ---- Meteor-M2 QPSK sync detection (decode_meteorm2.py:229-324) ----------------------------------------------------
+ * dd_meteor_mix -- out[k] = complex64(x[k] * (cos th, sin th)), th = (w * k) * inv_fs, w = -2 pi f: the reference's offsetFreq
+ *     arithmetic in float64; x = raw u8 pairs - 127.5 (raw_u8) or complex64 (c64), exactly one of them given.
+ * dd_meteor_walk -- the Gardner / agc / costas walk over x[n] (complex128, absolute sample index base + j), state in *state
+ *     (DDMeteorState, carried from chunk to chunk), params_host = DDMeteorParams (7 doubles, then the 256-entry tanh table).
+ *     Symbol k (the walk's k-th A sample) writes bidx[k], aidx[k] (sample indices), agc[k] (agc output of A), ph[k] (the costas
+ *     phasor active after the step), sym[k] (corrected symbol), pf[k] = (phase, freq) after the step; k >= cap sets the
+ *     state's overflow flag instead.
+ * dd_meteor_lim -- out[base + j] = (lim(real(x[j] * o) / 2), lim(imag(x[j] * o) / 2)) as int8 pairs, o the phasor of the last
+ *     symbol with aidx < base + j (1 before the first).
+ * dd_meteor_minsync -- bits[k] = limBin(re) | limBin(im) << 1 of sym[k]; for every k >= 59 whose 60-symbol window scores
+ *     |mismatches - 60| > 30 against sync72khz (re, im order) or sync72khz1 (im, re order; sync_bits_host[120 ..]):
+ *     cand[3c .. 3c+2] = (k, mismatches1, mismatches2), *count = the number of such k (entries past cap are dropped).
+ * dd_meteor_maxcorr -- per buffer i (bufs_host[5i ..] = lo0, n0, lo1, n1, template: samples [lo0, lo0+n0) then [lo1, lo1+n1)
+ *     of lim[lim_len], two entries each): out[2i] = argmax |np.correlate(buffer, np.repeat(templates[template], 28), 'same')|
+ *     (first maximum), out[2i+1] = that maximum.  templates_host = int8[2][120]. */
+int dd_meteor_mix(const void* raw_u8, const void* c64, int64_t n, double w, double inv_fs, void* out, void* stream);
+int dd_meteor_walk(const void* x, int64_t n, int64_t base, void* state, const double* params_host, int64_t cap,
+                   int64_t* bidx, int64_t* aidx, void* agc, void* ph, void* sym, void* pf, void* stream);
+int dd_meteor_lim(const void* x, int64_t n, int64_t base, const int64_t* aidx, int64_t nsym, const void* ph, void* out,
+                  int64_t out_len, void* stream);
+int dd_meteor_minsync(const void* sym, int64_t nsym, const uint8_t* sync_bits_host, uint8_t* bits, int64_t cap,
+                      int64_t* cand, unsigned long long* count, void* stream);
+int dd_meteor_maxcorr(const void* lim, int64_t lim_len, const int64_t* bufs_host, int64_t nbuf, const int8_t* templates_host,
+                      int64_t* out, void* stream);
+
 /* APT image extraction (decode_noaa.getImage / getColor).
  * dd_median_segments_f64 -- out[i] = np.median(src[off_host[i] : off_host[i] + len_host[i]]) for `count` segments (device out):
  *      numpy's semantics (odd: middle element, even: (a + b) / 2, empty or holding a NaN: NaN); segments of any length.

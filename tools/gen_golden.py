@@ -394,7 +394,180 @@ def gen_afsk_frames():
     _afsk_frames_store("afsk_frames_b.npz", cap, {"fs": np.int64(fs), "offset": np.int64(offset)})
 
 
+def _meteor_patterns():
+    """sync72khz, sync72khz1, sync72khz2 (decode_meteorm2.py:163-189)"""
+    import _meteor
+    s = _meteor.sync_bits()
+    alt = np.arange(len(s)) % 2
+    return s, np.where(alt == 0, s, 1 - s), np.where(alt == 1, s, 1 - s)
+
+
+def _meteor_run(raw, offset):
+    """The reference's decode_meteorm2.getSyncs on an in-memory recording, tapped: the sample index of every agc.adjust call (B or
+    A: an A call is the one costas.loop follows), the AGC'd values, costas phase / freq after each loop, the sample of every lim call
+    (the MAXSYNC buffers), each np.correlate's buffer length, template and argmax, and the MINSYNC / MAXSYNC log records."""
+    import logging
+    import types
+    from directdemod import comm
+    from directdemod import decode_meteorm2 as dmet
+    cur = {"base": 0, "j": -1}
+    agc_rec, loop_rec, lim_rec, corr_rec, logs = [], [], [], [], []
+
+    class TapSig(comm.commSignal):
+        tapped = False
+
+        def filter(self, f):
+            r = comm.commSignal.filter(self, f)
+            self.tapped = True
+            return r
+
+        @property
+        def signal(self):
+            arr = comm.commSignal.signal.fget(self)
+            if not self.tapped:
+                return arr
+            return self._walk(arr)
+
+        def _walk(self, arr):
+            base = cur["base"]
+            for j, v in enumerate(arr):
+                cur["j"] = base + j
+                yield v
+            cur["base"] = base + len(arr)
+
+    class TapAgc(dmet.agc):
+        def adjust(self, inp):
+            out = super().adjust(inp)
+            agc_rec.append((cur["j"], out))
+            return out
+
+    class TapCostas(dmet.costas):
+        def loop(self, samp):
+            out = super().loop(samp)
+            loop_rec.append((len(agc_rec) - 1, self.phase, self.freq))
+            return out
+
+    _lim = dmet.lim
+
+    def lim_tap(x):
+        lim_rec.append(cur["j"])
+        return _lim(x)
+    _corr = dmet.np.correlate
+
+    class NpTap(types.ModuleType):
+        def __getattr__(self, k):
+            return getattr(np, k)
+
+    def corr_tap(a, v, mode="valid"):
+        r = _corr(a, v, mode)
+        t = [np.repeat(np.where(p == 1, 127, -128), 28) for p in _meteor_patterns()]
+        corr_rec.append((len(a), int(np.argmax(np.abs(r))), 0 if np.array_equal(v, t[0]) else (1 if np.array_equal(v, t[2]) else 2)))
+        return r
+    nptap = NpTap("np")
+    nptap.correlate = corr_tap
+
+    class H(logging.Handler):
+        def emit(self, rec):
+            logs.append((rec.msg, rec.args))
+    h = H()
+    root = logging.getLogger()
+    old_level = root.level
+    root.addHandler(h)
+    root.setLevel(logging.INFO)
+    saved = (dmet.comm, dmet.agc, dmet.costas, dmet.lim, dmet.np)
+    dmet.comm = types.SimpleNamespace(commSignal=TapSig)
+    dmet.agc, dmet.costas, dmet.lim, dmet.np = TapAgc, TapCostas, lim_tap, nptap
+    try:
+        obj = dmet.decode_meteorm2(ArraySource(raw, 2048000), offset, None)
+        t0 = time.process_time()
+        err = None
+        try:
+            syncs = obj.getSyncs
+        except ValueError as e:               # one MAXSYNC: np.min of an empty diff
+            syncs, err = None, str(e)
+        cpu = time.process_time() - t0
+    finally:
+        dmet.comm, dmet.agc, dmet.costas, dmet.lim, dmet.np = saved
+        root.removeHandler(h)
+        root.setLevel(old_level)
+    return dict(syncs=syncs, useful=obj.useful, err=err, cpu=cpu, agc=agc_rec, loop=loop_rec, lim=lim_rec, corr=corr_rec, logs=logs)
+
+
+def _small_int(v):
+    """int8 where the values fit, else int16 (the per-symbol index steps: the fixtures stay under 300 KB)"""
+    v = np.asarray(v, dtype=np.int64)
+    assert np.abs(v).max(initial=0) < 32767
+    return v.astype(np.int8 if np.abs(v).max(initial=0) < 127 else np.int16)
+
+
+def _meteor_store(name, raw, offset, cap, trace_stride, trace_head):
+    import _meteor
+    agc, loop = cap["agc"], cap["loop"]
+    a_call = np.array([r[0] for r in loop], dtype=np.int64)              # agc call index of each symbol's A
+    is_a = np.zeros(len(agc), dtype=bool)
+    is_a[a_call] = True
+    j = np.array([r[0] for r in agc], dtype=np.int64)
+    # B of symbol k: the last non-A call before its A call (-1 if none since the start)
+    last_b = np.where(~is_a, np.arange(len(agc)), -1)
+    last_b = np.maximum.accumulate(last_b) if len(agc) else last_b
+    b_call = np.array([last_b[c - 1] if c > 0 else -1 for c in a_call], dtype=np.int64)
+    b_idx = np.where(b_call >= 0, j[np.maximum(b_call, 0)], -1)
+    a_idx = j[a_call] if len(a_call) else np.zeros(0, dtype=np.int64)
+    nsym = len(a_call)
+    sel = np.unique(np.concatenate((np.arange(min(nsym, trace_head)), np.arange(0, nsym, trace_stride)))).astype(np.int64)
+    agc_a = np.array([agc[c][1] for c in a_call[sel]], dtype=np.complex128)
+    phase = np.array([loop[k][1] for k in sel], dtype=np.float64)
+    freq = np.array([loop[k][2] for k in sel], dtype=np.float64)
+    mins = [int(a[0]) for m, a in cap["logs"] if m.startswith("MINSYNC")]
+    maxs = [float(a[0]) for m, a in cap["logs"] if m.startswith("MAXSYNC")]
+    # each correlation's buffer: lim's record (two calls per appended sample) from the buffer's first sample (maxBuffStart, the
+    # MAXSYNC value minus argmax / 2) on, len / 2 samples; cut into contiguous stretches
+    lim = np.array(cap["lim"], dtype=np.int64)[::2]
+    ivs, starts, args, tmpl = [], [], [], []
+    pos = 0
+    for (L, am, tm), ms in zip(cap["corr"], maxs):
+        start = int(ms - am / 2.0)
+        k = pos + int(np.argmax(lim[pos:] == start))
+        smp = lim[k:k + L // 2]
+        cuts = [0] + [int(c) + 1 for c in np.nonzero(np.diff(smp) != 1)[0]] + [len(smp)]
+        ivs.append([(int(smp[cuts[i]]), cuts[i + 1] - cuts[i]) for i in range(len(cuts) - 1)])
+        starts.append(start)
+        args.append(am)
+        tmpl.append(tm)
+        pos = k + L // 2
+    iv_flat = np.array([[i, a, b] for i, iv in enumerate(ivs) for a, b in iv], dtype=np.int64).reshape(-1, 3)
+    g = dict(sha256=np.array(_meteor.sha256(raw)), offset=np.int64(offset), n=np.int64(raw.shape[0]),
+             syncs=np.array(cap["syncs"] if cap["syncs"] is not None else [], dtype=np.float64),
+             one_maxsync=np.int64(cap["syncs"] is None), useful=np.int64(cap["useful"]),
+             minsync=np.array(mins, dtype=np.int64), maxsync=np.array(maxs, dtype=np.float64),
+             buf_intervals=iv_flat, buf_start=np.array(starts, dtype=np.int64), argmax=np.array(args, dtype=np.int64),
+             template=np.array(tmpl, dtype=np.int64), nsym=np.int64(nsym),
+             a_first=np.int64(a_idx[0] if nsym else -1), a_diff=_small_int(np.diff(a_idx)), ab_gap=_small_int(a_idx - b_idx),
+             trace_sel=sel, trace_agc=agc_a, trace_phase=phase, trace_freq=freq, trace_stride=np.int64(trace_stride),
+             ref_cpu_s=np.float64(cap["cpu"]))
+    path = os.path.join(OUT, "meteor_%s.npz" % name)
+    np.savez_compressed(path, **g)
+    print("meteor %s: n %d, %d symbols, MINSYNC %s, templates %s, syncs %s, useful %d, cpu %.1f s, %d bytes" %
+          (name, raw.shape[0], nsym, mins, tmpl, g["syncs"].tolist(), cap["useful"], cap["cpu"], os.path.getsize(path)))
+
+
+def gen_meteor():
+    """Meteor-M2 sync detection (decode_meteorm2.py:229-324) on the recordings of tests/_meteor.py.   gen_golden.py --meteor [names]"""
+    install_shim()
+    sys.path.insert(0, REF)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import _meteor
+    names = [a for a in sys.argv[2:] if a in _meteor.CASES] or sorted(_meteor.CASES)
+    for name in names:
+        raw, off = _meteor.case(name)
+        big = raw.shape[0] > 20000000
+        _meteor_store(name, raw, off, _meteor_run(raw, off), 2048 if big else 64, 1024 if big else 4096)
+
+
+
 def main():
+    if "--meteor" in sys.argv:
+        return gen_meteor()
     if "--afsk-frames" in sys.argv:
         return gen_afsk_frames()
     if "--c4-60s" in sys.argv:
