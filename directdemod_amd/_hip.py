@@ -15,7 +15,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libdirectdemod_hip.so")
-# DD_LIB_PATH (diagnostics only: tools/ A/B runs of ablation builds, build/variants/lib_N.so) loads another build of the same
+# DD_LIB_PATH (diagnostics only: tools/ A/B runs of variant builds, build/variants/lib_N.so) loads another build of the same
 # C-ABI INSTEAD of the product library and says so on stderr; the product file is never overwritten by a measurement script
 if os.environ.get("DD_LIB_PATH"):
     LIB_PATH = os.path.abspath(os.environ["DD_LIB_PATH"])
@@ -239,7 +239,7 @@ def check(rc, what=""):
 
 
 def select_kernel(name=None):
-    """Tools and tests: force one of the M = 1 chain kernels ("ab", "ws", "fft1k", "cos1k") for every later launch of this process,
+    """Tools and tests: force one of the M = 1 chain kernels ("ab", "fft1k", "cos1k") for every later launch of this process,
     or go back to the choice by tap class (None / "auto").  Mirrors the choice into os.environ["DD_MFMA_KERNEL"] (which only
     seeds the library's choice, once per process) so that code which looks there sees the same thing."""
     check(lib().dd_debug_select_kernel((name or "auto").encode()), "dd_debug_select_kernel")

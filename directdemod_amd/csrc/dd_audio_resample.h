@@ -196,10 +196,7 @@ static int64_t largest_prime_factor(int64_t n) {
 }
 // the chirp-z route pays when the library would run Bluestein itself (radices up to 17 are native) and few bins are kept
 static bool czt_wanted(int64_t n, int64_t num) {
-    static const char* env = DD_TUNE_ENV("DD_RESAMPLE_CZT");    // tools / tests: 0 = never, 1 = whenever downsampling
-    if (env && atoi(env) == 0) return false;
     if (!(num < n && n >= 256)) return false;
-    if (env && atoi(env) == 1) return true;
     return largest_prime_factor(n) > 17 && 4 * (num / 2 + 1) <= n;
 }
 
@@ -328,16 +325,14 @@ static int resample_czt_batch(const void* in, int in_is_f32, const int64_t* in_o
     for (int j : idx_all) nmax = n_host[j] > nmax ? n_host[j] : nmax;
     // convolution length: the smaller of the next 2^a and 3.2^a (measured for config 3, need 86 199, ms per 16 chunks: 98 304 =
     // 3.2^15 0.103, 131 072 0.112, 114 688 = 7.2^14 0.116, 86 400 = the smallest 7-smooth multiple of 16 0.140, 90 112 = 11.2^13
-    // 0.147: the library's power-of-two passes beat less data).  DD_CZT_LEN=<n> (tools) forces a length
-    static const char* lenv = DD_TUNE_ENV("DD_CZT_LEN");
+    // 0.147: the library's power-of-two passes beat less data)
     const char* oenv = getenv("DD_CZT_OWN");                // tools / tests: 0 = the library's transforms at any length
     int64_t L = 1;
     while (L < nmax + K - 1) L <<= 1;
     // 2^17 / 2^18: the convolution as three launches of our own float64 transform (dd_hconv_kernels.h) instead of pre-multiply +
     // library transform + multiply + library transform + post-multiply (config 3: ten launches -> three)
-    const bool own = hc_length_ok(L) && !(oenv && atoi(oenv) == 0) && !lenv;
+    const bool own = hc_length_ok(L) && !(oenv && atoi(oenv) == 0);
     if (!own && L >= 4 && 3 * (L / 4) >= nmax + K - 1) L = 3 * (L / 4);
-    if (lenv && atoll(lenv) >= nmax + K - 1) L = atoll(lenv);
     for (int j : idx_all) {                                  // every table first: 1 = not taken, nothing enqueued yet
         DDCztTab t;
         const int rc = czt_tables(n_host[j], K, L, s, &t);

@@ -807,10 +807,9 @@ extern "C" int dd_noaa_sync_windows_multi(const void* iq, int iq_kind, const int
     memcpy(up.data() + o_taps1, fir_taps_host, sizeof(double) * fir_ntaps);
     if (pre_ntaps) memcpy(up.data() + o_taps2, pre_taps_host, sizeof(double) * pre_ntaps);
     // the envelope's pre-filter is hamming(492) (decode_noaa.py:677): a two-term cosine series -- prefix-sum form
-    // (dd_filtfilt_kernels.h; DD_SYNC_DIRECT_FIR=1, tools: the 492 multiply-adds per sample of the tiled direct form)
+    // (dd_filtfilt_kernels.h)
     DDCosFit fit2;
-    static const char* direct_env = DD_TUNE_ENV("DD_SYNC_DIRECT_FIR");
-    const bool cos2 = pre_ntaps && !(direct_env && atoi(direct_env)) && dd_cos_fit_cached(pre_taps_host, pre_ntaps, &fit2) && dd_fc_ok(pre_ntaps, fit2.Q);
+    const bool cos2 = pre_ntaps && dd_cos_fit_cached(pre_taps_host, pre_ntaps, &fit2) && dd_fc_ok(pre_ntaps, fit2.Q);
     double2* d_tab = (double2*)(base + o_tab);
     if (cos2) {
         // (the table of one tap set is kept on the host between calls; the copy's pageable source is staged before the call returns)

@@ -439,7 +439,7 @@ __global__ void __launch_bounds__(DD_DECIM_THREADS) k_chain_decim(const DDChainP
 // One launch-long workgroup per third of a CU (LDS bound, 3 per CU) walks the interior tiles blockIdx.x, blockIdx.x + nwg,
 // ... (round 4: the device then works on one moving window of nwg tiles, and the tile loads are non-temporal -- what
 // tools/ubench/stream_2to1 found for streaming kernels: C3 / C4 one-chunk passes 0.110 / 0.113 -> 0.0985 / 0.102 ms = 0.69 / 0.67 of
-// 8 TB/s, profiles/r04_decim_map.txt; -DDD_DECIM_CONTIG / -DDD_DECIM_NO_NT: a contiguous run per workgroup, plain loads) of the
+// 8 TB/s, profiles/r04_decim_map.txt, against a contiguous run per workgroup and plain loads) of the
 // interior tiles: whole span inside the chunk, every output valid, complex64 input.  The next
 // tile's samples are requested (12 x 16 B per lane) the moment the current tile has been staged
 // into LDS -- into the same registers, which staging has just freed -- so they are in flight
@@ -458,11 +458,7 @@ __device__ __forceinline__ void dd_decim_issue(const DDChainParams& P, int b, in
     for (int u = 0; u < DD_DECIM_NV; ++u) {
         int q = t + u * DD_DECIM_THREADS;
         q = q < nq ? q : nq - 1;                          // past the span: harmless re-read, never used
-#ifndef DD_DECIM_NO_NT
         v[u] = __builtin_nontemporal_load(reinterpret_cast<const dd_v4f_a8*>(src + 2 * q));
-#else
-        v[u] = *reinterpret_cast<const dd_v4f_a8*>(src + 2 * q);
-#endif
     }
 }
 
@@ -477,11 +473,7 @@ __device__ __forceinline__ void dd_decim_issue_u8(const DDChainParams& P, int b,
     for (int u = 0; u < DD_DECIM_NV8; ++u) {
         int q = t + u * DD_DECIM_THREADS;
         q = q < nq8 ? q : nq8 - 1;
-#ifndef DD_DECIM_NO_NT
         v[u] = __builtin_nontemporal_load(reinterpret_cast<const dd_v4u_a4*>(src + 16 * q));
-#else
-        v[u] = *reinterpret_cast<const dd_v4u_a4*>(src + 16 * q);
-#endif
     }
 }
 
@@ -552,7 +544,6 @@ __device__ __forceinline__ void dd_decim_tile(const DDChainParams& P, int b, con
     if (t < T) {
         const float2* __restrict__ win = sx + t * M;
         int j = 0;
-#ifndef DD_DECIM_LDS_TAPS                                  // (-DDD_DECIM_LDS_TAPS: the taps from LDS, one multiply-add per component, as in rounds 1-4)
         if ((M & 1) == 0) {
             // the taps are wave uniform: they come through the scalar cache (a third of the tap loop's LDS reads were theirs), and a
             // multiply-add handles re and im at once; two partial sums
@@ -575,24 +566,6 @@ __device__ __forceinline__ void dd_decim_tile(const DDChainParams& P, int b, con
             }
             acc.x = a0.x + a1.x; acc.y = a0.y + a1.y;
         }
-#else
-        if ((M & 1) == 0) {                                // 16-byte aligned windows: conflict-free ds_read_b128 (see k_chain_decim)
-            const float4* __restrict__ win4 = reinterpret_cast<const float4*>(__builtin_assume_aligned(win, 16));
-            const float4* __restrict__ G4 = reinterpret_cast<const float4*>(__builtin_assume_aligned(gl, 16));
-            for (; j + 8 <= K; j += 8) {
-                const float4 x0 = win4[j / 2], x1 = win4[j / 2 + 1], x2 = win4[j / 2 + 2], x3 = win4[j / 2 + 3];
-                const float4 c0 = G4[j / 4], c1 = G4[j / 4 + 1];
-                acc.x = fmaf(c0.x, x0.x, acc.x); acc.y = fmaf(c0.x, x0.y, acc.y);
-                acc.x = fmaf(c0.y, x0.z, acc.x); acc.y = fmaf(c0.y, x0.w, acc.y);
-                acc.x = fmaf(c0.z, x1.x, acc.x); acc.y = fmaf(c0.z, x1.y, acc.y);
-                acc.x = fmaf(c0.w, x1.z, acc.x); acc.y = fmaf(c0.w, x1.w, acc.y);
-                acc.x = fmaf(c1.x, x2.x, acc.x); acc.y = fmaf(c1.x, x2.y, acc.y);
-                acc.x = fmaf(c1.y, x2.z, acc.x); acc.y = fmaf(c1.y, x2.w, acc.y);
-                acc.x = fmaf(c1.z, x3.x, acc.x); acc.y = fmaf(c1.z, x3.y, acc.y);
-                acc.x = fmaf(c1.w, x3.z, acc.x); acc.y = fmaf(c1.w, x3.w, acc.y);
-            }
-        }
-#endif
         for (; j + 8 <= K; j += 8) {
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
@@ -641,13 +614,8 @@ __global__ void __launch_bounds__(DD_DECIM_THREADS, 3) k_chain_decim_p(const DDC
     const int t = threadIdx.x;
     // contiguous run of tiles per workgroup, and per XCD (workgroups are dealt round-robin to the 8 XCDs)
     const int n = b_hi - b_lo;
-#ifndef DD_DECIM_CONTIG
     // tiles blockIdx.x, blockIdx.x + nwg, ...: the device works on one moving window of nwg tiles (tools/ubench/stream_2to1)
     const int begin = b_lo + (int)blockIdx.x, end = b_hi, step = nwg;
-#else
-    const int wg = (nwg % 8 == 0) ? (int)(blockIdx.x % 8) * (nwg / 8) + (int)(blockIdx.x / 8) : (int)blockIdx.x;
-    const int begin = b_lo + (int)(((int64_t)wg * n) / nwg), end = b_lo + (int)(((int64_t)(wg + 1) * n) / nwg), step = 1;
-#endif
     (void)n;
     if (begin >= end) return;
 
@@ -706,12 +674,7 @@ __global__ void __launch_bounds__(DD_DECIM_THREADS, 3) k_chain_decim_multi(const
     float* gl = reinterpret_cast<float*>(smem + ((sizeof(float2) * ((size_t)S + 4 + (S / 64 + 2) + DD_DECIM_THREADS) + 15) & ~(size_t)15));
     const int t = threadIdx.x;
     const int n = ipre[nchunks];
-#ifndef DD_DECIM_CONTIG
     const int begin = (int)blockIdx.x, end = n, step = nwg;
-#else
-    const int wg = (nwg % 8 == 0) ? (int)(blockIdx.x % 8) * (nwg / 8) + (int)(blockIdx.x / 8) : (int)blockIdx.x;
-    const int begin = (int)(((int64_t)wg * n) / nwg), end = (int)(((int64_t)(wg + 1) * n) / nwg), step = 1;      // global interior tile indices
-#endif
     if (begin >= end) return;
     int c = 0;
     while (begin >= ipre[c + 1]) ++c;
@@ -1043,8 +1006,6 @@ static int decim_plan(DDChainParams& P, DDDecimPlan& pl) {
                 occ_lds[u8in] = pl.lds_p;
                 occ_val[u8in] = per_cu;
             }
-            static const char* wg_env = DD_TUNE_ENV("DD_DECIM_WGS_PER_CU");            // tools: fewer persistent workgroups per CU than fit
-            if (wg_env && atoi(wg_env) >= 1 && atoi(wg_env) < per_cu) per_cu = atoi(wg_env);
             pl.per_cu = per_cu;
         }
     }

@@ -175,15 +175,7 @@ __device__ __forceinline__ void c1_flush_angles(const DDCos1kArgs& A, const char
     for (int g = 0; g < 4; ++g) v[g] = *reinterpret_cast<const v4f*>(img + 64 * (16 * g + G) + 16 * ((lane & 3) ^ sw));
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-#ifdef C1_ABL_NO_STORE
-        if (v[g].x + v[g].y + v[g].z + v[g].w == 1234.5f) o[256 * g] = v[g].x;
-#else
-#ifdef C1_NT_STORE
-        __builtin_nontemporal_store(v[g], reinterpret_cast<v4f*>(o + 256 * g));
-#else
         *reinterpret_cast<v4f*>(o + 256 * g) = v[g];            // (plain: 0.1514 ms against 0.1633 with the non-temporal hint, same call)
-#endif
-#endif
     }
 }
 
@@ -198,34 +190,11 @@ __device__ __forceinline__ void c1_cx_store(const DDCos1kArgs& A, int64_t S, int
     float2* const o = reinterpret_cast<float2*>(A.out) + S + 2 * lane;
 #pragma unroll
     // (non-temporal: with 8 bytes written per 8 read the hint pays -- 0.195 against 0.210-0.216 ms in the same calls; the angles' stores, 4 per 8, lose by it)
-#ifdef C1_CX_PLAIN_STORE
-    for (int j = 0; j < 8; ++j) *reinterpret_cast<v4f*>(o + 128 * j) = v[j];
-#else
     for (int j = 0; j < 8; ++j) __builtin_nontemporal_store(v[j], reinterpret_cast<v4f*>(o + 128 * j));
-#endif
 }
-
-// Ablation switches for timing experiments (tools/mkvariant.sh N dd_cosfir -DC1_ABL_...; the outputs of such a build are wrong):
-//   C1_ABL_NO_LOAD   no global loads          C1_ABL_NO_STORE  no global stores         C1_ABL_NO_PHASOR  no per-row phase table look-up
-//   C1_ABL_NO_LDS    no LDS traffic           C1_ABL_NO_FM     no discriminator         C1_ABL_NO_SCAN    no scan / window stage
-//   C1_ABL_MEMONLY   the memory side alone: loads, both LDS transpositions, stores; an "angle" is re + im of the sample
-//   C1_CX_IMMEDIATE  (results stay right) complex64 output stored by the row that made it instead of the next one
-//   C1_CX_PLAIN_STORE (results stay right) complex64 output stored without the non-temporal hint
-#ifdef C1_TRACE
-// tools/debug/cos_trace.py: cycles per phase of a row (s_memtime stamps; every stamp drains the wave's LDS / scalar counter), summed
-// per wave over its interior rows
-#define C1_NPH 8
-__device__ unsigned long long g_c1_trace[4096 * (C1_NPH + 2)];
-#define C1_T(i) do { __builtin_amdgcn_sched_barrier(0); const unsigned t_ = (unsigned)__builtin_readcyclecounter(); tr[i] += t_ - tprev; tprev = t_; __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define C1_T(i) do { } while (0)
-#endif
 
 template <bool U8>
 __device__ __forceinline__ void c1_issue_loads(const DDCos1kArgs& A, int64_t S, int lane, v4f (&xin)[8]) {
-#ifdef C1_ABL_NO_LOAD
-    return;
-#endif
     if (U8) {
         const v4f* p = reinterpret_cast<const v4f*>(reinterpret_cast<const unsigned char*>(A.in) + 2 * (S + 16 * lane));
         xin[0] = __builtin_nontemporal_load(p);
@@ -233,20 +202,13 @@ __device__ __forceinline__ void c1_issue_loads(const DDCos1kArgs& A, int64_t S, 
     } else {
         const v4f* p = reinterpret_cast<const v4f*>(reinterpret_cast<const float2*>(A.in) + S + 2 * lane);
 #pragma unroll
-#ifdef C1_PLAIN_LOAD
-        for (int j = 0; j < 8; ++j) xin[j] = p[64 * j];
-#else
         for (int j = 0; j < 8; ++j) xin[j] = __builtin_nontemporal_load(p + 64 * j);
-#endif
     }
 }
 
 template <bool NCO>
 __device__ __forceinline__ v2f c1_row_phasor(const DDCos1kArgs& A, int64_t S, v2f ql) {
     if (!NCO) return (v2f){1.f, 0.f};
-#ifdef C1_ABL_NO_PHASOR
-    return c1_cmul((v2f){0.6f, 0.8f}, ql);
-#else
     // (wave-uniform: the table entry comes through the SCALAR cache -- a vector load here would sit in vmcnt behind the next row's
     //  eight sample loads, and waiting for it would wait for all of them: a memory round trip exposed per row)
     const uint64_t phase64 = (uint64_t)(A.abs0 + S) * A.cyc;
@@ -263,7 +225,6 @@ __device__ __forceinline__ v2f c1_row_phasor(const DDCos1kArgs& A, int64_t S, v2
     const float cc = fmaf(-0.5f, t2, 1.0f), ss = theta * fmaf(-0.16666667f, t2, 1.0f);
     const v2f pr = (v2f){fmaf(Tk.x, cc, Tk.y * ss), fmaf(Tk.y, cc, -Tk.x * ss)};
     return c1_cmul(pr, ql);
-#endif
 }
 
 // One row.  EDGE: sample-by-sample loads (history, chunk end), predicated stores, the carried FIR output.  emit: store the row's outputs.
@@ -271,16 +232,7 @@ __device__ __forceinline__ v2f c1_row_phasor(const DDCos1kArgs& A, int64_t S, v2
 template <bool U8, bool NCO, bool EDGE, bool CX>
 __device__ __forceinline__ void c1_row(const DDCos1kArgs& A, const DDCos1kLane& lt, const int lane, char* const lds,
                                        const int64_t S, const bool emit, const bool prefetch_next,
-                                       v4f (&xin)[8], v4f (&xnext)[8], const v2f ql, C1Carry& cr
-#ifdef C1_TRACE
-                                       , unsigned* tr = nullptr
-#endif
-                                       ) {
-#ifdef C1_TRACE
-    unsigned tprev = (unsigned)__builtin_readcyclecounter();
-    unsigned trdummy[C1_NPH];
-    if (!tr) tr = trdummy;
-#endif
+                                       v4f (&xin)[8], v4f (&xnext)[8], const v2f ql, C1Carry& cr) {
     const float c = C1_C1, s = C1_S1;
     char* const cur = lds + cr.cur;
     char* const own = cur + lane * C1_GROUP_BYTES;                              // this lane's 16 samples of the row
@@ -343,10 +295,8 @@ __device__ __forceinline__ void c1_row(const DDCos1kArgs& A, const DDCos1kLane& 
                 }
                 xt[i] = x;
             }
-#ifndef C1_ABL_NO_LDS
 #pragma unroll
             for (int t = 0; t < 8; ++t) *reinterpret_cast<v4f*>(own + 16 * t) = (v4f){xt[2 * t].x, xt[2 * t].y, xt[2 * t + 1].x, xt[2 * t + 1].y};
-#endif
         } else {
             // row-major registers: xin[j] = samples 128 j + 2 l, + 1  ->  NCO  ->  LDS, group 8 j + (l >> 3), slot l & 7
             char* const wr = cur + (lane >> 3) * C1_GROUP_BYTES + 16 * (lane & 7);
@@ -378,22 +328,16 @@ __device__ __forceinline__ void c1_row(const DDCos1kArgs& A, const DDCos1kLane& 
                     x0 = c1_fma_hi(x0, pj[j], t0[j]);
                     x1 = c1_fma_hi(x1, pj1[j], t1[j]);
                 }
-#ifdef C1_ABL_NO_LDS
-                xt[2 * j] = x0; xt[2 * j + 1] = x1;
-#else
                 *reinterpret_cast<v4f*>(wr + 8 * j * C1_GROUP_BYTES) = (v4f){x0.x, x0.y, x1.x, x1.y};
-#endif
             }
         }
     }
-    C1_T(0);
     // the next row's samples fly during this row's arithmetic (requested ahead of every store of this row: vmcnt retires in order),
     // into the OTHER register set: the caller alternates the two, so that nothing is copied -- or waited for -- at the loop's back edge
     if (prefetch_next) { c1_issue_loads<U8>(A, S + C1_ROW, lane, xnext); cr.prow = c1_row_phasor<NCO>(A, S + C1_ROW, ql); }
     // the angles of the row before leave now: their LDS round trip and their stores overlap this row's arithmetic
     if (CX) { if (cx_pend != C1_NO_PEND) c1_cx_store(A, cx_pend, lane, pv); }
     else if (cr.pend_S != C1_NO_PEND) { c1_flush_angles(A, lds + (C1_BUF_BYTES - cr.cur), cr.pend_S, lane); cr.pend_S = C1_NO_PEND; }
-#ifndef C1_ABL_NO_LDS
     if (!EDGE && !U8) {
 #pragma unroll
         for (int t = 0; t < 8; ++t) {
@@ -402,27 +346,8 @@ __device__ __forceinline__ void c1_row(const DDCos1kArgs& A, const DDCos1kLane& 
             xt[2 * t + 1] = (v2f){v.z, v.w};
         }
     }
-#endif
-#ifdef C1_ABL_MEMONLY
-    if (!EDGE) {
-        cr.cur = C1_BUF_BYTES - cr.cur;
-        if (!emit) return;
-        {
-            const int sw = (lane >> 1) & 3;
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-                *reinterpret_cast<v4f*>(cur + 64 * lane + 16 * (t ^ sw)) = (v4f){xt[4 * t].x + xt[4 * t].y, xt[4 * t + 1].x + xt[4 * t + 1].y, xt[4 * t + 2].x + xt[4 * t + 2].y, xt[4 * t + 3].x + xt[4 * t + 3].y};
-        }
-        cr.pend_S = S;
-        return;
-    }
-#endif
     // d[i] = xt[n - 255] = sample i + 1 of the group 16 lanes back
     v2f d[16];
-#ifdef C1_ABL_NO_LDS
-#pragma unroll
-    for (int i = 0; i < 16; ++i) d[i] = xt[(i + 5) & 15] * 0.5f;
-#else
     d[0] = *reinterpret_cast<const v2f*>(old + 8);
 #pragma unroll
     for (int t = 1; t < 8; ++t) {
@@ -432,8 +357,6 @@ __device__ __forceinline__ void c1_row(const DDCos1kArgs& A, const DDCos1kLane& 
     }
     // (the first sample of the NEXT group: lane 15's is the first sample of this row, in this row's buffer)
     d[15] = *reinterpret_cast<const v2f*>(lane == 15 ? cur : old + C1_GROUP_BYTES);
-#endif
-    C1_T(1);
     // ---- pass A: lane totals of the un-windowed recurrence
     // T = sum_i A^{15-i} (xt[i], 0) = (sum cos((15-i) phi) xt[i], sum sin((15-i) phi) xt[i]): plain sums with constant weights (phi is
     // fixed by K = 255), two partial sums each so that consecutive multiply-adds do not wait for one another
@@ -455,14 +378,11 @@ __device__ __forceinline__ void c1_row(const DDCos1kArgs& A, const DDCos1kLane& 
         }
         t.C = C0 + C1; t.S = S0 + S1; t.R = R0 + R1;
     }
-    C1_T(2);
     // ---- inclusive weighted prefix inside each DPP row of 16 lanes
-#ifndef C1_ABL_NO_SCAN
     c1_scan_step<C1_ROW_SHR(1)>(t, C1_WC0, C1_WS0);
     c1_scan_step<C1_ROW_SHR(2)>(t, C1_WC1, C1_WS1);
     c1_scan_step<C1_ROW_SHR(4)>(t, C1_WC2, C1_WS2);
     c1_scan_step<C1_ROW_SHR(8)>(t, C1_WC3, C1_WS3);
-#endif
     // ---- window.  t is the prefix INSIDE the lane's DPP row of 16 lanes (l = L & 15); the 256 samples that end with lane L are lanes
     // 16 rho .. L of its own row and lanes l + 1 .. 15 of the row before, whose sum is A^{16 (l + 1)} (tot' - A^{16 (15 - l)} pre'_l):
     //     V_L = pre_l + A^{16 (l + 1)} tot' - A^256 pre'_l - A^255 (xt[16 (L - 15)], 0)
@@ -485,11 +405,9 @@ __device__ __forceinline__ void c1_row(const DDCos1kArgs& A, const DDCos1kLane& 
     V.C = c1_fma(-C1_C2, W.C, c1_fma(C1_S2, W.S, c1_fma(-c, e, t.C)));
     V.S = c1_fma(-C1_S2, W.C, c1_fma(-C1_C2, W.S, c1_fma(-s, e, t.S)));
     V.R = t.R - W.R - e;
-#ifndef C1_ABL_NO_SCAN
     V.C = c1_fma(lt.b15c, tot.C, c1_fma(-lt.b15s, tot.S, V.C));
     V.S = c1_fma(lt.b15s, tot.C, c1_fma(lt.b15c, tot.S, V.S));
     V.R += tot.R;
-#endif
     // state at the lane's first sample = V of the lane before (lane 0: the previous row's last)
     C1St u;
     u.C = c1_shr1(V.C, cr.V63.C);
@@ -497,7 +415,6 @@ __device__ __forceinline__ void c1_row(const DDCos1kArgs& A, const DDCos1kLane& 
     u.R = c1_shr1(V.R, cr.V63.R);
     cr.W = Wn;
     cr.V63.C = c1_lane63(V.C); cr.V63.S = c1_lane63(V.S); cr.V63.R = c1_lane63(V.R);
-    C1_T(3);
     // ---- pass B: the windowed recurrence.  y / a0 = R + (a1 / a0) C (filters.py:199): the discriminator does not see the positive
     // factor a0 (the edge rows, which hand y to the next chunk, put it back), so an output is one multiply-add
     v2f y[16];
@@ -511,7 +428,6 @@ __device__ __forceinline__ void c1_row(const DDCos1kArgs& A, const DDCos1kLane& 
         u.R += xt[i] - d[i];
         y[i] = c1_fma(kap, u.C, u.R);
     }
-    C1_T(4);
     cr.cur = C1_BUF_BYTES - cr.cur;                          // this row's buffer is the next row's "row before"
     if (EDGE) {
         // the FIR output before the chunk's first sample is carried state (demod_fm.py:47-49); the chunk's last one becomes it
@@ -541,11 +457,7 @@ __device__ __forceinline__ void c1_row(const DDCos1kArgs& A, const DDCos1kLane& 
 #pragma unroll
         for (int t = 0; t < 8; ++t)
             *reinterpret_cast<v4f*>(img + lane * C1_GROUP_BYTES + 16 * t) = (v4f){a0 * y[2 * t].x, a0 * y[2 * t].y, a0 * y[2 * t + 1].x, a0 * y[2 * t + 1].y};
-#ifdef C1_CX_IMMEDIATE
-        { v4f v[8]; c1_cx_read(img, lane, v); c1_cx_store(A, S, lane, v); }
-#else
         cr.pend_S = S;
-#endif
         return;
     }
     const v2f yl = c1_shr1(y[15], cr.y63);
@@ -561,10 +473,6 @@ __device__ __forceinline__ void c1_row(const DDCos1kArgs& A, const DDCos1kLane& 
         for (int i = 0; i < 16; ++i) tz[i] = c1_mul_lo(y[i], i ? y[i - 1] : yl);
 #pragma unroll
         for (int i = 0; i < 16; ++i) z[i] = c1_fma_hic(y[i], i ? y[i - 1] : yl, tz[i]);          // (re, im) of y[n] conj(y[n-1])
-#ifdef C1_ABL_NO_FM
-#pragma unroll
-        for (int i = 0; i < 16; ++i) ang[i] = z[i].x + z[i].y;
-#else
         // small-angle form (|angle| <= 22.5 degrees: re > 0 and |im / re| <= tan(pi / 8)) for the whole row when all 1024 outputs allow it
         // -- the quotients are formed first and the test is made on them; a product of exactly zero (digital silence) fails `re > 0` and
         // takes the full-range form, which returns np.angle(0) = 0
@@ -607,9 +515,7 @@ __device__ __forceinline__ void c1_row(const DDCos1kArgs& A, const DDCos1kLane& 
                 }
             }
         }
-#endif
     }
-    C1_T(5);
     if (EDGE) {
         float* const o = reinterpret_cast<float*>(A.out) + (S - A.s) + 16 * lane;
 #pragma unroll
@@ -634,7 +540,6 @@ __device__ __forceinline__ void c1_row(const DDCos1kArgs& A, const DDCos1kLane& 
             *reinterpret_cast<v4f*>(img + 64 * lane + 16 * (t ^ sw)) = (v4f){ang[4 * t], ang[4 * t + 1], ang[4 * t + 2], ang[4 * t + 3]};
     }
     cr.pend_S = S;                                           // (stored by the next row, or by the kernel after the wave's last interior row)
-    C1_T(6);
 }
 
 // The row BEFORE a run, cheaply.  What a run needs from it depends on its last 256 samples only: their image in LDS (the samples 255 back of
@@ -645,9 +550,6 @@ __device__ __forceinline__ void c1_row(const DDCos1kArgs& A, const DDCos1kLane& 
 template <bool U8>
 __device__ __forceinline__ void c1_prime_issue(const DDCos1kArgs& A, int64_t S, int lane, v4f (&xp)[2]) {
     xp[0] = xp[1] = (v4f){0.f, 0.f, 0.f, 0.f};
-#ifdef C1_ABL_NO_LOAD
-    return;
-#endif
     if (U8) {
         if (lane >= 48) {
             const v4f* p = reinterpret_cast<const v4f*>(reinterpret_cast<const unsigned char*>(A.in) + 2 * (S + 16 * lane));
@@ -785,22 +687,11 @@ __global__ void __launch_bounds__(64 * C1_WAVES, 2) k_chain_cos1k(const DDCos1kA
     cr.prow = (v2f){1.f, 0.f};
     cr.cur = 0;
     cr.pend_S = C1_NO_PEND;
-#ifdef C1_TRACE
-    unsigned tr[C1_NPH];
-#pragma unroll
-    for (int i = 0; i < C1_NPH; ++i) tr[i] = 0;
-    const unsigned tloop = (unsigned)__builtin_readcyclecounter();
-#endif
     // a row is an edge row when it holds samples before the first output, the carried state or the chunk's end.  Edge rows sit at
     // the two ends of a wave's range only: [q0 - 1, f0) edge, [f0, f1) interior, [f1, q1) edge.
     auto edge = [&](int q) { const int64_t lo = (int64_t)A.base + (int64_t)C1_ROW * q; return lo < A.s || lo + C1_ROW > A.L || q == nrows - 1; };
-#ifdef C1_ABL_MEMONLY
-    int f0 = edge(q0 - 1) ? q0 - 1 : q0;                      // (the memory-only build carries no state: no row before the run)
-    const int qfirst = f0;
-#else
     int f0 = q0 - 1;
     const int qfirst = q0 - 1;
-#endif
     while (f0 < q1 && edge(f0)) ++f0;
     int f1 = f0;
     while (f1 < q1 && !edge(f1)) ++f1;
@@ -811,7 +702,6 @@ __global__ void __launch_bounds__(64 * C1_WAVES, 2) k_chain_cos1k(const DDCos1kA
         c1_row<U8, NCO, true, CX>(A, lt, lane, lds, (int64_t)A.base + (int64_t)C1_ROW * q, q >= q0, false, xa, xb, ql, cr);
     if (f1 > f0) {
         const int64_t S0 = (int64_t)A.base + (int64_t)C1_ROW * f0;
-#if !defined(C1_ABL_MEMONLY) && !defined(C1_FULL_PRIME)
         if (f0 == q0 - 1 && f1 > q0) {
             // the row before the run is an interior row: its last 256 samples are all the run needs (c1_prime_light); the run's first row
             // is requested right behind them
@@ -821,22 +711,15 @@ __global__ void __launch_bounds__(64 * C1_WAVES, 2) k_chain_cos1k(const DDCos1kA
             c1_issue_loads<U8>(A, S0 + C1_ROW, lane, xa);
             c1_prime_light<U8, NCO>(A, lt, lane, lds, S0, xp, ql, cr);
             cr.prow = c1_row_phasor<NCO>(A, S0 + C1_ROW, ql);
-        } else
-#endif
-        {
-        c1_issue_loads<U8>(A, S0, lane, xa);
-        cr.prow = c1_row_phasor<NCO>(A, S0, ql);
+        } else {
+            c1_issue_loads<U8>(A, S0, lane, xa);
+            cr.prow = c1_row_phasor<NCO>(A, S0, ql);
         }
         // two rows per trip: the sample registers alternate (xa: even rows of the run, xb: odd ones)
         for (int q = f0; q < f1; q += 2) {
             const int64_t S = (int64_t)A.base + (int64_t)C1_ROW * q;
-#ifdef C1_TRACE
-            c1_row<U8, NCO, false, CX>(A, lt, lane, lds, S, q >= q0, q + 1 < f1, xa, xb, ql, cr, q >= q0 ? tr : nullptr);
-            if (q + 1 < f1) c1_row<U8, NCO, false, CX>(A, lt, lane, lds, S + C1_ROW, true, q + 2 < f1, xb, xa, ql, cr, tr);
-#else
             c1_row<U8, NCO, false, CX>(A, lt, lane, lds, S, q >= q0, q + 1 < f1, xa, xb, ql, cr);
             if (q + 1 < f1) c1_row<U8, NCO, false, CX>(A, lt, lane, lds, S + C1_ROW, true, q + 2 < f1, xb, xa, ql, cr);
-#endif
         }
     }
     if (cr.pend_S != C1_NO_PEND) {
@@ -846,14 +729,6 @@ __global__ void __launch_bounds__(64 * C1_WAVES, 2) k_chain_cos1k(const DDCos1kA
     }
     for (int q = f1; q < q1; ++q)
         c1_row<U8, NCO, true, CX>(A, lt, lane, lds, (int64_t)A.base + (int64_t)C1_ROW * q, q >= q0, false, xa, xb, ql, cr);
-#ifdef C1_TRACE
-    tr[7] = (unsigned)__builtin_readcyclecounter() - tloop;
-    if (gw < 4096 && lane == 0) {
-#pragma unroll
-        for (int i = 0; i < C1_NPH; ++i) g_c1_trace[gw * (C1_NPH + 2) + i] = tr[i];
-        g_c1_trace[gw * (C1_NPH + 2) + C1_NPH] = (unsigned long long)(q1 - q0);
-    }
-#endif
     if (q1 == nrows && A.tail_out) {
         // the new carried history: the chunk's last K-1 samples after the NCO (older ones from the old history)
         for (int i = lane; i < C1_K - 1; i += 64) {
@@ -926,14 +801,6 @@ void dd_cos1k_destroy(void* stv) {
     delete s;
 }
 
-#ifdef C1_TRACE
-extern "C" int dd_debug_cos1k_trace(unsigned long long* out, int nwaves) {
-    DD_HIP_CHECK(hipDeviceSynchronize());
-    DD_HIP_CHECK(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_c1_trace), sizeof(unsigned long long) * (size_t)nwaves * (C1_NPH + 2)));
-    return DD_OK;
-}
-#endif
-
 // where the row grid sits and how many rows and waves a chunk takes (host arithmetic, also reachable without a GPU: dd_debug_cos1k_plan)
 static void cos1k_plan(int64_t L, int s, int out_align_elems, int ncu, int wg_per_cu, int* base, int* nrows, int* grid, int* nwaves) {
     int b = s - out_align_elems;                                   // out[b - s] starts a 64-byte line
@@ -981,17 +848,12 @@ int dd_cos1k_launch(void* stv, const DDChainParams& P, hipStream_t stream) {
     const bool cx = !(P.flags & DD_CHAIN_FM);
     // rows start where `out` starts a line: 16 angles = 64 bytes, 16 complex outputs = 128
     const int a16 = (int)((reinterpret_cast<uintptr_t>(P.out) >> (cx ? 3 : 2)) & 15);
-    static const char* wg_env = DD_TUNE_ENV("DD_COS_WGS_PER_CU");            // tools: occupancy experiments
     int grid;
-    cos1k_plan(P.L, P.s, a16, dd_cu_count(), wg_env ? atoi(wg_env) : 2, &A.base, &A.nrows, &grid, &A.nwaves);
-    static const char* run_env = DD_TUNE_ENV("DD_COS_RUN");                 // tools: rows per run of the moving-window map (0 = one run per wave)
-    A.run_rows = run_env ? atoi(run_env) : -1;
-    static const char* grid_env = DD_TUNE_ENV("DD_COS_GRID");               // tools: a fixed number of workgroups
-    if (grid_env && atoi(grid_env) > 0 && (int64_t)atoi(grid_env) * C1_WAVES <= A.nrows) { grid = atoi(grid_env); A.nwaves = grid * C1_WAVES; }
+    cos1k_plan(P.L, P.s, a16, dd_cu_count(), 2, &A.base, &A.nrows, &grid, &A.nwaves);
     // runs of 8 rows dealt to the waves in turn once every wave gets at least two of them: the device then walks one moving window of
     // nwaves x 64 KB instead of nwaves streams far apart (memory side alone 5.64 -> 6.05 TB/s, the kernel 0.1455 -> 0.1417 ms in one call,
     // profiles/r05_cos1k_memory_only.txt; a run start costs c1_prime_light: 2 KB read twice and a third of a row's instructions)
-    if (A.run_rows < 0) A.run_rows = A.nrows >= 16 * A.nwaves ? 8 : 0;
+    A.run_rows = A.nrows >= 16 * A.nwaves ? 8 : 0;
     const bool u8 = (P.flags & DD_CHAIN_U8_INPUT) != 0;
     const dim3 g(grid), b(64 * C1_WAVES);
     void* kargs[1] = {&A};

@@ -193,13 +193,8 @@ __host__ __device__ __forceinline__ int dw_pos(const DWMap& mp, int r) {
 template <int J0, int NJ>
 __device__ __forceinline__ void dw_issue(const DDDecimWArgs& A, int64_t Brel, int lane, v4f_a8 (&x)[NJ]) {
     const v4f_a8* p = reinterpret_cast<const v4f_a8*>(reinterpret_cast<const float2*>(A.in) + Brel + 2 * lane);
-#ifdef DW_NO_LOADS      // (diagnostic: the kernel without its sample loads -- wrong outputs, the time of everything else)
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) x[j] = (v4f_a8){(float)lane, 1.f, 2.f, (float)(J0 + j)};
-#else
 #pragma unroll
     for (int j = 0; j < NJ; ++j) x[j] = __builtin_nontemporal_load(p + 64 * (J0 + j));
-#endif
 }
 template <bool NCO, bool PAD, int J0, int NJ>
 __device__ __forceinline__ void dw_stage(const DDDecimWArgs& A, float2* buf, const float2* gl, int lane, const DWPh& pw, const v4f_a8 (&x)[NJ], const DWMap& mp) {
@@ -269,13 +264,8 @@ typedef uint32_t u32_a2 __attribute__((aligned(2)));
 template <int J0, int NJ>
 __device__ __forceinline__ void dw_issue4(const DDDecimWArgs& A, int64_t Brel, int lane, uint32_t (&x)[NJ]) {
     const unsigned char* p = reinterpret_cast<const unsigned char*>(A.in) + 2 * (Brel + 2 * lane);
-#ifdef DW_NO_LOADS
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) x[j] = (uint32_t)lane * 0x01010101u + (uint32_t)(J0 + j);
-#else
 #pragma unroll
     for (int j = 0; j < NJ; ++j) x[j] = __builtin_nontemporal_load(reinterpret_cast<const u32_a2*>(p + 256 * (J0 + j)));
-#endif
 }
 template <bool NCO, bool PAD, int J0, int NJ>
 __device__ __forceinline__ void dw_stage4(const DDDecimWArgs& A, float2* buf, const float2* gl, int lane, const DWPh& pw, const uint32_t (&x)[NJ], const DWMap& mp) {
@@ -318,13 +308,8 @@ __device__ __forceinline__ void dw_stage4(const DDDecimWArgs& A, float2* buf, co
 template <int J0, int NJ>
 __device__ __forceinline__ void dw_issue8(const DDDecimWArgs& A, int64_t Brel, int lane, v4u_a2 (&x)[NJ]) {
     const unsigned char* p = reinterpret_cast<const unsigned char*>(A.in) + 2 * (Brel + 8 * lane);
-#ifdef DW_NO_LOADS
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) x[j] = (v4u_a2){(uint32_t)lane * 0x01010101u, 0x80807f7fu, 0x7f808180u, (uint32_t)(J0 + j)};
-#else
 #pragma unroll
     for (int j = 0; j < NJ; ++j) x[j] = __builtin_nontemporal_load(reinterpret_cast<const v4u_a2*>(p + 1024 * (J0 + j)));
-#endif
 }
 template <bool NCO, bool PAD, int J0, int NJ>
 __device__ __forceinline__ void dw_stage8(const DDDecimWArgs& A, float2* buf, const float2* gl, int lane, const DWPh& pw, const v4u_a2 (&x)[NJ], const DWMap& mp) {
@@ -459,16 +444,6 @@ __device__ __forceinline__ v2f dw_lane(v2f v, int l) {                  // (l: w
     return (v2f){__int_as_float(__builtin_amdgcn_readlane(__float_as_int(v.x), l)), __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v.y), l))};
 }
 
-#ifdef DW_TRACE
-// tools/debug/decimw_trace.py: cycles per phase of an interior row (every stamp drains the wave's counters), summed per wave
-#define DW_NPH 7
-#define DW_NTR (DW_NPH + 6)     // + rows, whole kernel, kernel start -> first run, run start -> row before staged, the row before's outputs, runs
-__device__ unsigned long long g_dw_trace[4096 * DW_NTR];
-#define DW_T(i) do { __builtin_amdgcn_s_waitcnt(0); __builtin_amdgcn_sched_barrier(0); const unsigned t_ = (unsigned)__builtin_readcyclecounter(); tr[i] += t_ - tprev; tprev = t_; __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define DW_T(i) do { } while (0)
-#endif
-
 // where the outputs of a row sit: r0 = block offset of its first kept sample, cnt of them, p0 = chunk-relative index of the first
 struct DWRow {
     int r0, cnt;
@@ -491,15 +466,7 @@ __device__ __forceinline__ DWMap dw_row_map(const DDDecimWArgs& A, const DWRow& 
 }
 
 template <bool FM, bool PAD>
-__device__ __forceinline__ void dw_row_outputs(const DDDecimWArgs& A, float2* buf, int lane, const DWRow& r, const DWMap& mp, bool emit, v2f& ycarry, v2f ylast_in
-#ifdef DW_TRACE
-                                               , unsigned* tr = nullptr, unsigned tprev = 0
-#endif
-                                               ) {
-#ifdef DW_TRACE
-    unsigned trd[DW_NPH];
-    if (!tr) tr = trd;
-#endif
+__device__ __forceinline__ void dw_row_outputs(const DDDecimWArgs& A, float2* buf, int lane, const DWRow& r, const DWMap& mp, bool emit, v2f& ycarry, v2f ylast_in) {
     v4f hl[2];
     DWMap mpn = mp;                                           // the NEXT row's layout: where the halo goes
     if (PAD) {
@@ -522,7 +489,6 @@ __device__ __forceinline__ void dw_row_outputs(const DDDecimWArgs& A, float2* bu
         const int ic = i < r.cnt ? i : r.cnt - 1;
         const v2f y = dw_taps<PAD>(A, buf, wsp + ic * wstep);
         if (t == ng - 1) dw_halo_read<PAD>(A, buf, lane, hl, mp);
-        DW_T(2);
         if (FM) {
             v2f yp = (v2f){dw_shr1(y.x, ycarry.x), dw_shr1(y.y, ycarry.y)};
             const int last = t == ng - 1 ? (r.cnt - 1) & 63 : 63;
@@ -544,10 +510,8 @@ __device__ __forceinline__ void dw_row_outputs(const DDDecimWArgs& A, float2* bu
                 if (p == A.Ld - 1 && A.lasty_out) *A.lasty_out = make_float2(y.x, y.y);
             }
         }
-        DW_T(3);
     }
     dw_halo_write<PAD>(A, buf, lane, hl, mpn);
-    DW_T(4);
 }
 
 // the new carried history (the chunk's last K-1 samples after the NCO, older ones from the old history): the value a row gives a sample,
@@ -609,13 +573,6 @@ __global__ void __launch_bounds__(64, DW_WAVES_PER_SIMD) k_chain_decim_w(const D
     static_assert(DW_W - 512 >= 0 && DW_NL >= 4 && DW_NL8 >= 1, "the last 512 samples of a row hold K + M <= 320");
     v4f_a8 x[DW_NL];
     v4u_a2 x8[DW_NL8];
-#ifdef DW_TRACE
-    unsigned tr[DW_NPH];
-#pragma unroll
-    for (int i = 0; i < DW_NPH; ++i) tr[i] = 0;
-    unsigned trows = 0;
-    const unsigned tstart = (unsigned)__builtin_readcyclecounter();
-#endif
     for (int run = gw; run < nruns; run += A.nwaves) {
         const int q0 = run * RR, q1 = q0 + RR < A.nrows ? q0 + RR : A.nrows;
         auto brel = [&](int q) { return (A.R0 + q) * (int64_t)DW_W - A.abs0; };
@@ -661,19 +618,14 @@ __global__ void __launch_bounds__(64, DW_WAVES_PER_SIMD) k_chain_decim_w(const D
         v2f ycarry = (v2f){0.f, 0.f};
         dw_row_outputs<FM, PAD>(A, buf, lane, r, mp, false, ycarry, ylast_in);
         for (int q = q0; q < q1; ++q) {
-#ifdef DW_TRACE
-            unsigned tprev = (unsigned)__builtin_readcyclecounter();
-#endif
             const bool fast = q >= f0 && q < f1;
             dw_row_next(A, r);
             if (PAD) mp = dw_row_map(A, r);
             DWPh pw;
             dw_row_ph<U8, NCO>(row_phasor(q), ph, pw);
-            DW_T(5);
             if (fast) {
                 if constexpr (U8) dw_stage8<NCO, PAD, 0, DW_NL8>(A, buf, gl, lane, pw, x8, mp);
                 else dw_stage<NCO, PAD, 0, DW_NL>(A, buf, gl, lane, pw, x, mp);
-                DW_T(0);
                 if (q + 1 < f1) {
                     // the next row's samples fly during this row's tap loop
                     if constexpr (U8) dw_issue8<0, DW_NL8>(A, brel(q + 1), lane, x8); else dw_issue<0, DW_NL>(A, brel(q + 1), lane, x);
@@ -682,33 +634,10 @@ __global__ void __launch_bounds__(64, DW_WAVES_PER_SIMD) k_chain_decim_w(const D
                 if constexpr (U8) dw_stage8_guarded<NCO, PAD>(A, buf, gl, lane, 0, brel(q), pw, mp);
                 else dw_stage_guarded<NCO, PAD>(A, buf, gl, lane, 0, brel(q), pw, mp);
             }
-#ifdef DW_TRACE
-            if (fast) {
-                { __builtin_amdgcn_sched_barrier(0); const unsigned t_ = (unsigned)__builtin_readcyclecounter(); tr[1] += t_ - tprev; tprev = t_; __builtin_amdgcn_sched_barrier(0); }
-                ++trows;
-                dw_row_outputs<FM, PAD>(A, buf, lane, r, mp, true, ycarry, ylast_in, tr, tprev);
-            } else
-#endif
             dw_row_outputs<FM, PAD>(A, buf, lane, r, mp, true, ycarry, ylast_in);
         }
     }
-#ifdef DW_TRACE
-    if (gw < 4096 && lane == 0) {
-#pragma unroll
-        for (int i = 0; i < DW_NPH; ++i) g_dw_trace[gw * DW_NTR + i] = tr[i];
-        g_dw_trace[gw * DW_NTR + DW_NPH] = trows;
-        g_dw_trace[gw * DW_NTR + DW_NPH + 1] = (unsigned)__builtin_readcyclecounter() - tstart;
-    }
-#endif
 }
-
-#ifdef DW_TRACE
-extern "C" int dd_debug_decimw_trace(unsigned long long* out, int nwaves) {
-    DD_HIP_CHECK(hipDeviceSynchronize());
-    DD_HIP_CHECK(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_dw_trace), sizeof(unsigned long long) * (size_t)nwaves * DW_NTR));
-    return DD_OK;
-}
-#endif
 
 // ============================================================================ block-sum form (round 6)
 // k_chain_decim_w's tap loop reads every staged sample K / M times (2.5-4.4 for the reference's /34 and /50): 80 sixteen-byte LDS reads and one
@@ -936,15 +865,7 @@ __device__ __forceinline__ const float2* dw_b_block(const DDDecimWArgs& A, const
 // pre0: the first pass's first reads have been requested (dw_bsums_begin on dw_b_block(.., 0))
 template <bool FM, bool PAD, int NG>
 __device__ __forceinline__ void dw_b_row_outputs(const DDDecimWArgs& A, float2* buf, int lane, const DWRow& r, const DWMap& mp, bool emit, v2f& ycarry,
-                                                 DWCarry& cy, v2f ylast_in, const float (&ta)[5], const float (&tb)[5], DWPre<PAD, NG>& pre0
-#ifdef DW_TRACE
-                                                 , unsigned* tr = nullptr, unsigned tprev = 0
-#endif
-                                                 ) {
-#ifdef DW_TRACE
-    unsigned trd[DW_NPH];
-    if (!tr) tr = trd;
-#endif
+                                                 DWCarry& cy, v2f ylast_in, const float (&ta)[5], const float (&tb)[5], DWPre<PAD, NG>& pre0) {
     v4f hl[2];
     DWMap mpn = mp;
     if (PAD) {
@@ -959,7 +880,6 @@ __device__ __forceinline__ void dw_b_row_outputs(const DDDecimWArgs& A, float2* 
         DWAcc<NG> acc;
         if (t > 0) dw_bsums_begin<PAD, NG>(A, blk, pre0);
         dw_bsums<PAD, NG>(A, blk, pre0, ta, tb, acc);
-        DW_T(6);
         if (t == ng - 1) dw_halo_read<PAD>(A, buf, lane, hl, mp);
         const int last = (emit && t == ng - 1) ? (r.cnt - 1) & 63 : 63;
         // y = P_0 + (P_1[lane - 1] + (P_2[lane - 2] + ...)): the sums move up one lane per step
@@ -979,7 +899,6 @@ __device__ __forceinline__ void dw_b_row_outputs(const DDDecimWArgs& A, float2* 
                 }
             }
         }
-        DW_T(2);
         const int64_t p = r.p0 + i;
         if (FM) {
             v2f yp = (v2f){dw_shr1(y.x, ycarry.x), dw_shr1(y.y, ycarry.y)};
@@ -998,10 +917,8 @@ __device__ __forceinline__ void dw_b_row_outputs(const DDDecimWArgs& A, float2* 
                 if (p == A.Ld - 1 && A.lasty_out) *A.lasty_out = make_float2(y.x, y.y);
             }
         }
-        DW_T(3);
     }
     dw_halo_write<PAD>(A, buf, lane, hl, mpn);
-    DW_T(4);
 }
 
 template <bool U8, bool NCO, bool FM, bool PAD, int NG>
@@ -1012,9 +929,6 @@ __global__ void __launch_bounds__(64, DW_WAVES_PER_SIMD) k_chain_decim_b(const D
     const int lane = threadIdx.x;
     const int gw = blockIdx.x;
     const int M = A.M;
-#ifdef DW_TRACE
-    const unsigned tstart = (unsigned)__builtin_readcyclecounter();
-#endif
     const int RR = A.run_rows;
     const int nruns = (A.nrows + RR - 1) / RR;
     v4f_a8 x[DW_NL];
@@ -1075,20 +989,7 @@ __global__ void __launch_bounds__(64, DW_WAVES_PER_SIMD) k_chain_decim_b(const D
     v2f ylast_in = (v2f){0.f, 0.f};
     if (FM && A.s == 0) ylast_in = dw_v2(*A.lasty_in);
     const int jlo = dw_b_jlo(M, A.NI);
-#ifdef DW_TRACE
-    unsigned tr[DW_NPH];
-#pragma unroll
-    for (int i = 0; i < DW_NPH; ++i) tr[i] = 0;
-    unsigned trows = 0;
-#endif
-#ifdef DW_TRACE
-    unsigned tx[4] = {0, 0, 0, 0};
-    tx[0] = (unsigned)__builtin_readcyclecounter() - tstart;
-#endif
     for (int run = gw; run < nruns; run += A.nwaves) {
-#ifdef DW_TRACE
-        const unsigned trun = (unsigned)__builtin_readcyclecounter();
-#endif
         const Run cur = run_of(run);
         const int q0 = cur.q0, q1 = cur.q1, f0 = cur.f0, f1 = cur.f1;
         const bool pin = cur.pin;
@@ -1130,36 +1031,21 @@ __global__ void __launch_bounds__(64, DW_WAVES_PER_SIMD) k_chain_decim_b(const D
         DWCarry cy;
 #pragma unroll
         for (int s = 0; s < 7; ++s) cy.h[s] = (v2f){0.f, 0.f};
-#ifdef DW_TRACE
-        __builtin_amdgcn_s_waitcnt(0xc07f);                   // (lgkmcnt(0) only: the staged samples are in LDS; the loads stay in flight)
-        const unsigned tpre = (unsigned)__builtin_readcyclecounter();
-        tx[1] += tpre - trun;
-#endif
         DWPre<PAD, NG> pre;
         dw_bsums_begin<PAD, NG>(A, dw_b_block<PAD>(A, buf, lane, r, false, 0), pre);
         dw_b_row_outputs<FM, PAD, NG>(A, buf, lane, r, mp, false, ycarry, cy, ylast_in, ta, tb, pre);
-#ifdef DW_TRACE
-        __builtin_amdgcn_s_waitcnt(0xc07f);
-        tx[2] += (unsigned)__builtin_readcyclecounter() - tpre;
-        ++tx[3];
-#endif
         for (int q = q0; q < q1; ++q) {
-#ifdef DW_TRACE
-            unsigned tprev = (unsigned)__builtin_readcyclecounter();
-#endif
             const bool fast = q >= f0 && q < f1;
             dw_row_next(A, r);
             if (PAD) mp = dw_b_row_map(A, r);
             DWPh pw;
             dw_row_ph<false, NCO>(row_phasor(q), ph, pw);
-            DW_T(5);
             if (fast) {
                 // (tried: a second set of sample registers, the next row requested BEFORE this one is staged so that the wave always has a
                 //  request in flight -- no gain, the launch sits on the memory system's rate, not on the bytes in flight; r06_decimb_notes.txt)
                 if constexpr (U8) dw_stage4<NCO, PAD, 0, DW_NL>(A, buf, gl, lane, pw, x8, mp);
                 else dw_stage<NCO, PAD, 0, DW_NL>(A, buf, gl, lane, pw, x, mp);
                 dw_b_tail_zero<PAD>(A, buf, lane, mp);
-                DW_T(0);
                 // (the block sums' first LDS reads ahead of the loads' address arithmetic)
                 dw_bsums_begin<PAD, NG>(A, dw_b_block<PAD>(A, buf, lane, r, true, 0), pre);
                 if (q + 1 < f1) {
@@ -1172,26 +1058,9 @@ __global__ void __launch_bounds__(64, DW_WAVES_PER_SIMD) k_chain_decim_b(const D
                 dw_b_tail_zero<PAD>(A, buf, lane, mp);
                 dw_bsums_begin<PAD, NG>(A, dw_b_block<PAD>(A, buf, lane, r, true, 0), pre);
             }
-#ifdef DW_TRACE
-            if (fast) {
-                { __builtin_amdgcn_sched_barrier(0); const unsigned t_ = (unsigned)__builtin_readcyclecounter(); tr[1] += t_ - tprev; tprev = t_; __builtin_amdgcn_sched_barrier(0); }
-                ++trows;
-                dw_b_row_outputs<FM, PAD, NG>(A, buf, lane, r, mp, true, ycarry, cy, ylast_in, ta, tb, pre, tr, tprev);
-            } else
-#endif
             dw_b_row_outputs<FM, PAD, NG>(A, buf, lane, r, mp, true, ycarry, cy, ylast_in, ta, tb, pre);
         }
     }
-#ifdef DW_TRACE
-    if (gw < 4096 && lane == 0) {
-#pragma unroll
-        for (int i = 0; i < DW_NPH; ++i) g_dw_trace[gw * DW_NTR + i] = tr[i];
-        g_dw_trace[gw * DW_NTR + DW_NPH] = trows;
-        g_dw_trace[gw * DW_NTR + DW_NPH + 1] = (unsigned)__builtin_readcyclecounter() - tstart;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) g_dw_trace[gw * DW_NTR + DW_NPH + 2 + i] = tx[i];
-    }
-#endif
 }
 
 // ============================================================================ host side
@@ -1224,11 +1093,7 @@ static void decimw_plan(int64_t abs0, int64_t Ld, int K, int M, int off, int ncu
     pl.nrows = (int)(Rl - pl.R0 + 1);
     // block sums (k_chain_decim_b) where an output needs at most eight of them: K <= 8 M -- every K for M >= 32, the reference's /34 and /50
     pl.NI = (K + M - 1) / M;
-#ifdef DW_NO_BSUM
-    pl.bsum = 0;
-#else
     pl.bsum = pl.NI <= 8 ? 1 : 0;
-#endif
     pl.j1lo = 0;
     pl.nh = 0;
     if (pl.bsum) {
@@ -1437,13 +1302,6 @@ int dd_decimw_launch(const DDChainParams& P, const float* taps_g0, const double*
     const bool u8 = (P.flags & DD_CHAIN_U8_INPUT) != 0, nco = (P.flags & DD_CHAIN_NCO) != 0, fm = (P.flags & DD_CHAIN_FM) != 0;
     DWPlan pl;
     decimw_plan(P.abs0, P.Ld, P.K, P.M, P.off, dd_cu_count(), pl);
-    static const char* run_env = DD_TUNE_ENV("DD_DECIMW_RUN");              // tools: rows per run
-    if (run_env && atoi(run_env) > 0) {
-        pl.run_rows = atoi(run_env);
-        pl.nruns = (pl.nrows + pl.run_rows - 1) / pl.run_rows;
-        const int slots = dd_cu_count() * pl.wpc;
-        pl.nwaves = pl.nruns < slots ? pl.nruns : slots;
-    }
     const float* taps = taps_g0 - pl.e;
     if (pl.bsum) {
         // the taps as the matrix instruction takes them, for (M, e): [set][register g][lane 4 t + m] = h[M (4 set + m) + d], d = M - 1 + e - j the

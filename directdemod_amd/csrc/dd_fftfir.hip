@@ -280,38 +280,20 @@ __device__ __forceinline__ void f1_load_pairs(const void* in, int64_t n0, int la
         unsigned m = (unsigned)lane + 64u * (r0 + i);
         if (CLAMP) m = m < lim ? m : lim;
         if (U8) {
-#ifndef FF_NO_NT_LOAD
             const unsigned uu = __builtin_nontemporal_load(reinterpret_cast<const unsigned*>(reinterpret_cast<const uchar2*>(in) + n0) + m);
             const uchar4 u = make_uchar4(uu & 255u, (uu >> 8) & 255u, (uu >> 16) & 255u, uu >> 24);
-#else
-            const uchar4 u = reinterpret_cast<const uchar4*>(reinterpret_cast<const uchar2*>(in) + n0)[m];
-#endif
             x[2 * (r0 + i)] = (v2f){(float)u.x - 127.5f, (float)u.y - 127.5f};
             x[2 * (r0 + i) + 1] = (v2f){(float)u.z - 127.5f, (float)u.w - 127.5f};
         } else {
-            // non-temporal (streamed once): with the moving-window block map the memory side of this kernel (-DFF_NO_COMPUTE) runs
-            // 0.1553 ms instead of 0.1622 (profiles/r04_fft_map_sweep.txt); -DFF_NO_NT_LOAD / -DFF_NO_NT_STORE: plain accesses
-#ifndef FF_NO_NT_LOAD
+            // non-temporal (streamed once): with the moving-window block map the memory side of this kernel runs 0.1553 ms instead
+            // of 0.1622 (profiles/r04_fft_map_sweep.txt)
             typedef float v4f_ __attribute__((ext_vector_type(4)));
             const v4f_ v = __builtin_nontemporal_load(reinterpret_cast<const v4f_*>(reinterpret_cast<const float2*>(in) + n0) + m);
-#else
-            const float4 v = reinterpret_cast<const float4*>(reinterpret_cast<const float2*>(in) + n0)[m];
-#endif
             x[2 * (r0 + i)] = (v2f){v.x, v.y};
             x[2 * (r0 + i) + 1] = (v2f){v.z, v.w};
         }
     }
 }
-
-#ifdef FF_TRACE
-// tools/debug/fft_trace.py: cycles per phase of f1_block (s_memtime stamps; every stamp drains the wave's LDS / scalar counter),
-// summed per wave over its interior blocks
-#define FF_NPH 14
-__device__ unsigned long long g_ff_trace[4096 * (FF_NPH + 2)];
-#define FF_T(i) do { __builtin_amdgcn_sched_barrier(0); const unsigned t_ = (unsigned)__builtin_readcyclecounter(); tr[i] += t_ - tprev; tprev = t_; __builtin_amdgcn_sched_barrier(0); } while (0)
-#else
-#define FF_T(i) do { } while (0)
-#endif
 
 struct F1Edge {
     int prev_m;            // block position (256 + output index) of the FIR output before the chunk's first one, which comes from the
@@ -351,19 +333,16 @@ __device__ __forceinline__ v2f f1_edge_sample(const DDChainParams& P, int64_t n)
 }
 
 // angles of row pairs 2 + 2 g, 3 + 2 g (group g of three) from zz (two per lane and row pair: zz[2 r], zz[2 r + 1]):
-// angles | two of the next block's loads | two 8-byte stores.  FAST: every product of the group has |im| < tan(pi/8) re
+// angles | two 8-byte stores.  FAST: every product of the group has |im| < tan(pi/8) re
 // (wave-uniform, decided per group of 256 outputs: an angle beyond 22.5 degrees -- an amplitude null of a noise-like input,
 // SURVEY 8(d) input A -- sends 256 outputs through the full-range form, not the block's 768).
-template <bool U8, bool PARTIAL, bool LOADNEXT, bool FAST>
-__device__ __forceinline__ void f1_tail_group(const int g, const v2f (&zz)[16], v2f (&a)[16], const void* in, const int64_t n0_next, const int lane, float* const ob, const int lim_lo,
-                                              const int limit, const float theta_sub, const v2f crot) {
+template <bool PARTIAL, bool FAST>
+__device__ __forceinline__ void f1_tail_group(const int g, const v2f (&zz)[16], const int lane, float* const ob, const int lim_lo, const int limit,
+                                              const float theta_sub, const v2f crot) {
     float ang[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         v2f z = zz[4 + 4 * g + i];
-#ifdef FF_NO_DISC
-        ang[i] = z.x;
-#else
         if (FAST) {
             // theta_sub: the NCO's per-sample rotation taken off the angle (|theta| <= 0.25, so the result stays inside (-pi, pi))
             ang[i] = ff_atan_small(z.y, z.x) - theta_sub;          // (the compiler pairs these into packed instructions)
@@ -376,38 +355,17 @@ __device__ __forceinline__ void f1_tail_group(const int g, const v2f (&zz)[16], 
             }
             ang[i] = ff_atan2(z.y, z.x);
         }
-#endif
     }
-#ifdef FF_LOAD_NOWAIT
-    if (LOADNEXT) {                        // same loads, never consumed
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const float4* q = reinterpret_cast<const float4*>(reinterpret_cast<const float2*>(in) + n0_next) + lane + 64 * (2 + 2 * g + i);
-            float4 junk;
-            asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(junk) : "v"(q) : "memory");
-        }
-    }
-#elif !defined(FF_NO_LOAD) && defined(FF_LOADS_IN_TAIL)
-    if (LOADNEXT) f1_load_pairs<U8>(in, n0_next, lane, a, 2 + 2 * g, 2);
-#endif
-#ifdef FF_NO_STORE
-    if (ang[0] + ang[1] + ang[2] + ang[3] == 1234.5f) ob[0] = ang[0];
-#else
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         const int o = 128 * (2 * g + i);                    // output of this lane's first sample of the row pair, relative to ob
         if (!PARTIAL) {
-#ifndef FF_NO_NT_STORE
             __builtin_nontemporal_store((v2f){ang[2 * i], ang[2 * i + 1]}, reinterpret_cast<v2f*>(ob + o));
-#else
-            *reinterpret_cast<float2*>(ob + o) = make_float2(ang[2 * i], ang[2 * i + 1]);
-#endif
         } else {
             if (2 * lane + o >= lim_lo && 2 * lane + o < limit) ob[o] = ang[2 * i];
             if (2 * lane + o + 1 >= lim_lo && 2 * lane + o + 1 < limit) ob[o + 1] = ang[2 * i + 1];
         }
     }
-#endif
 }
 
 // (Round 4 also tried the exchanges' sixteen reads as explicit ds_read_b64 -- the compiler merges them into eight ds_read2_b64, which
@@ -429,27 +387,13 @@ __device__ __forceinline__ v2f f1_cmul(v2f a, v2f b) { return (v2f){fmaf(a.x, b.
 template <bool U8, bool PARTIAL, bool LOADNEXT, bool CX = false>
 __device__ __forceinline__ void f1_block(v2f (&a)[16], v2f (&keep)[4], v2f (&jl)[4], v2f* const Xp, const v2f (&tw1)[16], const v2f (&tw3)[16], const v2f* const hp,
                                          const v2f crot, const float theta_sub, const int lane, const void* in, const int64_t n0_next, float* const out_row4, const int lim_lo, const int limit,
-                                         const bool jump = false, const F1Edge* edge = nullptr, const F1Cx* cx = nullptr
-#ifdef FF_TRACE
-                                         , unsigned* tr = nullptr
-#endif
-                                         ) {
+                                         const bool jump = false, const F1Edge* edge = nullptr, const F1Cx* cx = nullptr) {
     const int hi = lane >> 2, lo = lane & 3;
     v2f* const X = Xp;
-#ifdef FF_TRACE
-    unsigned tdummy[FF_NPH];
-    if (!tr) tr = tdummy;
-    unsigned tprev = (unsigned)__builtin_readcyclecounter();
-#endif
 #pragma unroll
     for (int r = 2; r < 8; ++r) f1_swap(a[2 * r], a[2 * r + 1]);
 #pragma unroll
     for (int r = 0; r < 4; ++r) keep[r] = a[12 + r];          // the overlap the next block starts with
-#ifdef FF_NO_COMPUTE
-    v2f zz[16];
-#pragma unroll
-    for (int r = 0; r < 16; ++r) zz[r] = a[r];
-#else
     // column t = 2 (lane & 31) + (lane >> 5) sits at position (t >> 1) + 34 (t & 1) of an X1 row: contiguous per half wave
     const int x1w = (lane & 31) + 34 * (lane >> 5);                        // + 68 k0
     const int x1r = hi * F1_S1 + (lo >> 1) + 34 * (lo & 1);                // + 2 n1     (column 4 n1 + lo)
@@ -457,30 +401,20 @@ __device__ __forceinline__ void f1_block(v2f (&a)[16], v2f (&keep)[4], v2f (&jl)
     const int x2r = hi * F1_S2 + 5 * lo;     // + 20 c + n0      (k1 = 4 c + j)
     // ---- forward pass 1 (over n2), T1, X1
     ff_bfly16<false>(a);
-    FF_T(0);
     ff_twiddle15<false, true>(a, tw1);
-    FF_T(1);
-#ifndef FF_NO_LDS
 #pragma unroll
     for (int k = 0; k < 16; ++k) X[x1w + F1_S1 * k] = a[FF_P(k)];
 #pragma unroll
     for (int k = 0; k < 16; ++k) a[k] = X[x1r + 2 * k];
-#endif
     // ---- forward pass 2 (over n1), X2
-    FF_T(2);
     ff_bfly16<false>(a);
-    FF_T(3);
-    FF_T(4);
-#ifndef FF_NO_LDS
 #pragma unroll
     for (int k = 0; k < 16; ++k) X[x2w + 5 * k] = a[FF_P(k)];
 #pragma unroll
     for (int c = 0; c < 4; ++c)
 #pragma unroll
         for (int n = 0; n < 4; ++n) a[4 * c + n] = X[x2r + 20 * c + n];
-#endif
     // ---- T2 folded into forward pass 3 (radix 4 over n0); the spectrum product folded into inverse pass 3; T2*
-    FF_T(5);
     ff_stage<false, false, 1, 0xEEEEu, 0u, false>(a, tw3);
     {
         v2f h[16];
@@ -500,29 +434,20 @@ __device__ __forceinline__ void f1_block(v2f (&a)[16], v2f (&keep)[4], v2f (&jl)
 #pragma unroll
         for (int k = 0; k < 16; ++k) if (k & 3) a[k] = ff_fma_hic(a[k], tw3[k], z[k]);
     }
-    FF_T(6);
-#ifndef FF_NO_LDS
 #pragma unroll
     for (int c = 0; c < 4; ++c)
 #pragma unroll
         for (int n = 0; n < 4; ++n) X[x2r + 20 * c + n] = a[4 * c + n];
 #pragma unroll
     for (int k = 0; k < 16; ++k) a[k] = X[x2w + 5 * k];
-#endif
     // ---- inverse pass 2
-    FF_T(7);
     ff_bfly16<true>(a);
-    FF_T(8);
-#ifndef FF_NO_LDS
 #pragma unroll
     for (int k = 0; k < 16; ++k) X[x1r + 2 * k] = a[FF_P(k)];
 #pragma unroll
     for (int k = 0; k < 16; ++k) a[k] = X[x1w + F1_S1 * k];
-#endif
     // ---- T1* folded into inverse pass 1: a[FF_P(r)] = w[n0 + 64 r + t]
-    FF_T(9);
     ff_bfly16<true, true>(a, tw1);
-    FF_T(10);
     // ---- back to two consecutive outputs per lane: B[r] = w[128 r + 2 lane], A[r] = the one after it (row pairs 1..7;
     // of pair 1 only lane 63's second value is used, as the left-hand neighbour of the block's first output)
     v2f zz[16];
@@ -532,13 +457,9 @@ __device__ __forceinline__ void f1_block(v2f (&a)[16], v2f (&keep)[4], v2f (&jl)
         for (int r = 1; r < 8; ++r) { B[r] = a[FF_P(2 * r)]; A[r] = a[FF_P(2 * r + 1)]; f1_swap(B[r], A[r]); }
         if (CX) {
             // ---- complex64 output: NCO factor, 16-byte stores of two outputs per lane; the next block's loads in between
-#ifndef FF_NO_LOAD
             if (LOADNEXT && jump) f1_load_pairs<U8, false, 4>(in, n0_next, lane, jl, 0, 2);
-#ifndef FF_LOADS_IN_TAIL
             // (B and A hold this block's results: a[] is free for the next block's samples, requested ahead of every store)
             if (LOADNEXT) f1_load_pairs<U8>(in, n0_next, lane, a, 2, 6);
-#endif
-#endif
             float2* const oc = reinterpret_cast<float2*>(out_row4) + 2 * lane;
 #pragma unroll
             for (int g = 0; g < 3; ++g) {
@@ -551,19 +472,12 @@ __device__ __forceinline__ void f1_block(v2f (&a)[16], v2f (&keep)[4], v2f (&jl)
                     y[2 * i] = f1_cmul(B[r], f1_cmul(rp, cx->lp0));
                     y[2 * i + 1] = f1_cmul(A[r], f1_cmul(rp, cx->lp1));
                 }
-#if !defined(FF_NO_LOAD) && defined(FF_LOADS_IN_TAIL)
-                if (LOADNEXT) f1_load_pairs<U8>(in, n0_next, lane, a, 2 + 2 * g, 2);
-#endif
 #pragma unroll
                 for (int i = 0; i < 2; ++i) {
                     const int o = 128 * (2 * g + i);
                     if (!PARTIAL) {
                         typedef float v4f_ __attribute__((ext_vector_type(4)));
-#ifndef FF_NO_NT_STORE
                         __builtin_nontemporal_store((v4f_){y[2 * i].x, y[2 * i].y, y[2 * i + 1].x, y[2 * i + 1].y}, reinterpret_cast<v4f_*>(oc + o));
-#else
-                        *reinterpret_cast<v4f_*>(oc + o) = (v4f_){y[2 * i].x, y[2 * i].y, y[2 * i + 1].x, y[2 * i + 1].y};
-#endif
                     } else {
                         if (2 * lane + o >= lim_lo && 2 * lane + o < limit) oc[o] = make_float2(y[2 * i].x, y[2 * i].y);
                         if (2 * lane + o + 1 >= lim_lo && 2 * lane + o + 1 < limit) oc[o + 1] = make_float2(y[2 * i + 1].x, y[2 * i + 1].y);
@@ -615,15 +529,12 @@ __device__ __forceinline__ void f1_block(v2f (&a)[16], v2f (&keep)[4], v2f (&jl)
             for (int r = 4; r < 16; ++r) zz[r] = ff_fma_hi(zz[r], crot, t[r]);         // the NCO's rotation per sample
         }
     }
-#endif
     // a[] is dead from here: the next block's samples fly during the angles and stores.  Its first four rows are this
     // block's last four (the 256-sample overlap), kept in `keep`: six loads per block
     // (jump, wave-uniform: the next block is not this one's successor -- its first two row pairs are loaded as well, into
     // registers of their own: the caller swaps them into a[0..3] at the top of the next block, where the wave waits for that
     // block's samples anyway; otherwise the caller copies `keep`)
-#ifndef FF_NO_LOAD
     if (LOADNEXT && jump) f1_load_pairs<U8, false, 4>(in, n0_next, lane, jl, 0, 2);
-#ifndef FF_LOADS_IN_TAIL
     // ALL of the next block's loads go out here, ahead of every store of this block.  The memory counter (vmcnt) of gfx9 counts
     // loads and stores alike and retires them in issue order, so a wave that waits for a load also waits for every store it
     // issued before that load.  Round 3 interleaved "angles | two loads | two stores" three times: the wait for the last loads
@@ -631,8 +542,6 @@ __device__ __forceinline__ void f1_block(v2f (&a)[16], v2f (&keep)[4], v2f (&jl)
     // per block and wave.  (Found when the arithmetic-only build, forced onto the bench input's angle path, measured 0.129 ms
     // and the memory-only build 0.141 ms against 0.200 ms for the kernel: profiles/r04_fft1k_overlap.txt.)
     if (LOADNEXT) f1_load_pairs<U8>(in, n0_next, lane, a, 2, 6);
-#endif
-#endif
     // wave-uniform fast path per group of two row pairs: every |angle| of its 256 outputs below 22.5 degrees, |im| < tan(pi/8) re
     // (strictly: a product of exactly zero -- 1024 samples of digital silence -- must take the full-range form, whose
     // result for it is 0; the small-angle form would divide 0 by 0)
@@ -643,18 +552,13 @@ __device__ __forceinline__ void f1_block(v2f (&a)[16], v2f (&keep)[4], v2f (&jl)
 #pragma unroll
         for (int r = 4 + 4 * g; r < 8 + 4 * g; ++r) worst = fmaxf(worst, fmaf(-0.41421356f, zz[r].x, fabsf(zz[r].y)));
         fast[g] = __builtin_amdgcn_ballot_w64(worst >= 0.f) == 0;
-#ifdef FF_FORCE_FAST
-        fast[g] = true;       // (ablation builds without loads run on whatever the registers hold: keep them on the path the bench input takes)
-#endif
     }
-    FF_T(11);
     float* const ob = out_row4 + 2 * lane;
 #pragma unroll
     for (int g = 0; g < 3; ++g) {
-        if (fast[g]) f1_tail_group<U8, PARTIAL, LOADNEXT, true>(g, zz, a, in, n0_next, lane, ob, lim_lo, limit, theta_sub, crot);
-        else f1_tail_group<U8, PARTIAL, LOADNEXT, false>(g, zz, a, in, n0_next, lane, ob, lim_lo, limit, theta_sub, crot);
+        if (fast[g]) f1_tail_group<PARTIAL, true>(g, zz, lane, ob, lim_lo, limit, theta_sub, crot);
+        else f1_tail_group<PARTIAL, false>(g, zz, lane, ob, lim_lo, limit, theta_sub, crot);
     }
-    FF_T(12);
 }
 
 // one edge block (the chunk's first and / or last): samples fetched one by one through f1_edge_sample, stores
@@ -823,12 +727,6 @@ __global__ void __launch_bounds__(64 * F1_WAVES, 3) k_chain_fft1k(const DDChainP
         __builtin_amdgcn_s_waitcnt(0x0F70);        // vmcnt(0)
         f1_swap(a[0], a[1]);
         f1_swap(a[2], a[3]);
-#ifdef FF_TRACE
-        unsigned tr[FF_NPH];
-#pragma unroll
-        for (int i = 0; i < FF_NPH; ++i) tr[i] = 0;
-        const unsigned tloop = (unsigned)__builtin_readcyclecounter();
-#endif
         for (;;) {
             int qn = q + 1;
             bool jump = false, done = false;
@@ -849,11 +747,7 @@ __global__ void __launch_bounds__(64 * F1_WAVES, 3) k_chain_fft1k(const DDChainP
                 f1_block<U8, false, true, true>(a, keep, jl, X, tw1, tw3, hp, crot, T.theta_sub, lane, P.in, n0_next,
                                                 reinterpret_cast<float*>(reinterpret_cast<float2*>(P.out) + p0), 0, F1_ADV, jump, nullptr, &cx);
             } else {
-#ifdef FF_TRACE
-                f1_block<U8, false, true>(a, keep, jl, X, tw1, tw3, hp, crot, T.theta_sub, lane, P.in, n0_next, outp + (p0 - P.s), 0, F1_ADV, jump, nullptr, nullptr, tr);
-#else
                 f1_block<U8, false, true>(a, keep, jl, X, tw1, tw3, hp, crot, T.theta_sub, lane, P.in, n0_next, outp + (p0 - P.s), 0, F1_ADV, jump);
-#endif
             }
             if (done) break;
             if (jump) {
@@ -867,14 +761,6 @@ __global__ void __launch_bounds__(64 * F1_WAVES, 3) k_chain_fft1k(const DDChainP
             }
             q = qn;
         }
-#ifdef FF_TRACE
-        tr[13] = (unsigned)__builtin_readcyclecounter() - tloop;
-        if (gw < 4096 && lane == 0) {
-#pragma unroll
-            for (int i = 0; i < FF_NPH; ++i) g_ff_trace[gw * (FF_NPH + 2) + i] = tr[i];
-            g_ff_trace[gw * (FF_NPH + 2) + FF_NPH] = (unsigned long long)(w1 - w0);
-        }
-#endif
     }
 #undef F1_RUN
     if (gw == nwaves - 1 && nblk > 1) f1_edge_block<U8, CX>(ka, nblk - 1, X, hp, lane, nblk);
@@ -1016,14 +902,6 @@ static int fft_prepare(DDFftState* s, bool nco, uint64_t cyc, hipStream_t stream
     return DD_OK;
 }
 
-#ifdef FF_TRACE
-extern "C" int dd_debug_fft_trace(unsigned long long* out, int nwaves) {
-    DD_HIP_CHECK(hipDeviceSynchronize());
-    DD_HIP_CHECK(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_ff_trace), sizeof(unsigned long long) * (size_t)nwaves * (FF_NPH + 2)));
-    return DD_OK;
-}
-#endif
-
 // Host arithmetic of a launch -- where the block grid sits (DDFft1kTabs::base), how many blocks and waves there are and which
 // blocks a wave takes in which round (DDFft1kMap) -- as a function of its own, so that the CPU test suite can check it without a
 // GPU (dd_debug_fft1k_plan: every interior block exactly once, waves balanced, runs contiguous).
@@ -1091,8 +969,7 @@ int dd_fft1k_launch(void* stv, const DDChainParams& P, hipStream_t stream) {
         const long double a = 2.0L * 3.14159265358979323846264338327950288L * frac;
         // theta in (-pi, pi]; small -> subtracted from the angle, else applied as a rotation of every product
         const long double th = a > 3.14159265358979323846264338327950288L ? a - 2.0L * 3.14159265358979323846264338327950288L : a;
-        static const char* rot_env = DD_TUNE_ENV("DD_FFT_ROTATE");          // tools: force the rotation form
-        if (fabsl(th) <= 0.25L && th != 0.0L && !(rot_env && atoi(rot_env))) {
+        if (fabsl(th) <= 0.25L && th != 0.0L) {
             T1.theta_sub = (float)th;
             T1.crot = make_float2((float)cosl(a), (float)-sinl(a));     // (the full-range angle path rotates by it instead)
         } else {
@@ -1101,8 +978,6 @@ int dd_fft1k_launch(void* stv, const DDChainParams& P, hipStream_t stream) {
         }
     }
     // the block grid is laid so that block b's first angle, out[768 b + base - s], starts a 64-byte line of `out`
-    // (DD_FFT_FRAME=0, tools: the grid starts at output 0 whatever the alignment, as before round 4)
-    static const char* frame_env = DD_TUNE_ENV("DD_FFT_FRAME");
     const bool cxout = !(P.flags & DD_CHAIN_FM);
     {
         const long double frac = nco ? (long double)P.cyc / 18446744073709551616.0L : 0.0L;
@@ -1115,10 +990,8 @@ int dd_fft1k_launch(void* stv, const DDChainParams& P, hipStream_t stream) {
     }
     // float32 angles: 16 per 64-byte line; complex64 outputs: 8 per line (and no demod_fm shift)
     const int a16 = cxout ? (int)((reinterpret_cast<uintptr_t>(P.out) >> 3) & 7) : (int)((reinterpret_cast<uintptr_t>(P.out) >> 2) & 15);
-    static const char* wg_env1 = DD_TUNE_ENV("DD_FFT_WGS_PER_CU");           // tools: occupancy experiments
-    static const char* rounds_env = DD_TUNE_ENV("DD_FFT_ROUNDS");            // tools: a fixed number of rounds (1 = round 3's map)
     DDFft1kPlan pl;
-    fft1k_plan(P.L, P.s, (frame_env && atoi(frame_env) == 0) ? P.s : a16, dd_cu_count(), wg_env1 ? atoi(wg_env1) : 3, rounds_env ? atoi(rounds_env) : 0, &pl);
+    fft1k_plan(P.L, P.s, a16, dd_cu_count(), 3, 0, &pl);
     T1.base = pl.base;
     const int nb1 = pl.nblk, grid1 = pl.grid, nw1 = pl.nwaves;
     const DDFft1kMap& M1 = pl.map;

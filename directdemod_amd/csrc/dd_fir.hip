@@ -521,14 +521,10 @@ __global__ void __launch_bounds__(64) k_iir_blocks_w(const double2* __restrict__
                                                      double* __restrict__ blk, int64_t nb, double* __restrict__ state, int save, int lb) {
     extern __shared__ __attribute__((aligned(16))) char iir_w_lds[];
     const int lane = threadIdx.x, bl = lane >> 1, c = lane & 1;
-#ifndef IIR_WRITE_FORWARD
     // the pass that writes takes the workgroups' blocks from the END of the input -- what the read pass touched last is what the memory-side cache (256 MB)
     // still holds -- and its stores are non-temporal, so that the 16 bytes written per sample do not push the 8 still to be read out of it (round 6, same call:
     // write pass 360 -> 327 us, the call 0.644 -> 0.591 ms; reversed alone 347 us, non-temporal alone 351 us)
     const int64_t b0 = (int64_t)(WRITE ? gridDim.x - 1 - blockIdx.x : blockIdx.x) * IIR_W_BLOCKS, b = b0 + bl;
-#else
-    const int64_t b0 = (int64_t)blockIdx.x * IIR_W_BLOCKS, b = b0 + bl;
-#endif
     const bool live = b < nb;
     double z[S];
 #pragma unroll
@@ -594,7 +590,6 @@ __global__ void __launch_bounds__(64) k_iir_blocks_w(const double2* __restrict__
         }
         if (WRITE) {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                            // the rows hold the outputs
-#ifndef IIR_W_PLAIN_READS
             // the rows are read back by instructions the compiler cannot see into: it puts s_waitcnt vmcnt(0) in front of every LDS read that
             // might touch what a DMA in flight writes -- sixteen drains of the whole queue per step, each store waiting for the one before it
             // (round 6, the ISA: profiles/r06_iir_notes.txt).  The rows of THIS step landed before the loop above read them.
@@ -610,25 +605,10 @@ __global__ void __launch_bounds__(64) k_iir_blocks_w(const double2* __restrict__
                     const int64_t bb = b0 + 2 * (r0 + q) + half;
                     const int64_t idx = bb * lb + (int64_t)st * IIR_W_CH + l32;
                     if (bb < nb && idx < n) {
-#ifndef IIR_WRITE_PLAIN
                         __builtin_nontemporal_store(v[q], reinterpret_cast<iir_v2d*>(out + idx));
-#else
-                        *reinterpret_cast<iir_v2d*>(out + idx) = v[q];
-#endif
                     }
                 }
             }
-#else
-#pragma unroll
-            for (int r = 0; r < IIR_W_BLOCKS / 2; ++r) {
-                const int64_t bb = b0 + 2 * r + half;
-                const int64_t pos = (int64_t)st * IIR_W_CH + l32;
-                const int64_t idx = bb * lb + pos;
-                const double2 v = *reinterpret_cast<const double2*>(cur + r * IIR_W_PAIR + lane * 16);
-                if (bb < nb && idx < n) out[idx] = v;
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                            // rows read before a later DMA overwrites them
-#endif
         }
     }
     if (!WRITE) {
@@ -675,14 +655,10 @@ __global__ void __launch_bounds__(64) k_iir_blocks_w32(const float2* __restrict_
     extern __shared__ __attribute__((aligned(16))) char iir_w_lds[];
     char* const tile = iir_w_lds + IIR_W32_NB * G::IN;
     const int lane = threadIdx.x, bl = lane >> 1, c = lane & 1;
-#ifndef IIR_WRITE_FORWARD
     // the pass that writes takes the workgroups' blocks from the END of the input -- what the read pass touched last is what the memory-side cache (256 MB)
     // still holds -- and its stores are non-temporal, so that the 16 bytes written per sample do not push the 8 still to be read out of it (round 6, same call:
     // write pass 360 -> 327 us, the call 0.644 -> 0.591 ms; reversed alone 347 us, non-temporal alone 351 us)
     const int64_t b0 = (int64_t)(WRITE ? gridDim.x - 1 - blockIdx.x : blockIdx.x) * IIR_W_BLOCKS, b = b0 + bl;
-#else
-    const int64_t b0 = (int64_t)blockIdx.x * IIR_W_BLOCKS, b = b0 + bl;
-#endif
     const bool live = b < nb;
     double z[S];
 #pragma unroll
@@ -761,11 +737,7 @@ __global__ void __launch_bounds__(64) k_iir_blocks_w32(const float2* __restrict_
                     const int64_t bb = b0 + 2 * (r0 + q) + half;
                     const int64_t idx = bb * lb + (int64_t)st * IIR_W_CH + l32;
                     if (bb < nb && idx < n) {
-#ifndef IIR_WRITE_PLAIN
                         __builtin_nontemporal_store(v[q], reinterpret_cast<iir_v2d*>(out + idx));
-#else
-                        *reinterpret_cast<iir_v2d*>(out + idx) = v[q];
-#endif
                     }
                 }
             }
@@ -945,8 +917,7 @@ static void iir_block_matrices(const dd_iir* h, int lb, double* out /* 6 * IIR_M
 // in32: `in` is complex64 (ncomp == 2, buffers 16-byte aligned: the caller has checked) -- the one-wave kernels k_iir_blocks_w32
 static int iir_parallel(dd_iir* h, const double* in, double* out, int64_t n, int ncomp, int carry, hipStream_t s, bool in32 = false) {
     const int S = h->n - 1;
-    int lb = n >= IIR_LONG_FROM ? IIR_LB_LONG : IIR_LB_SHORT;
-    if (const char* e = DD_TUNE_ENV("DD_IIR_LB")) lb = atoi(e) == IIR_LB_LONG ? IIR_LB_LONG : IIR_LB_SHORT;      // A/B switch
+    const int lb = n >= IIR_LONG_FROM ? IIR_LB_LONG : IIR_LB_SHORT;
     // block start states: blocks -> groups of G1 -> (if there are many groups) super-groups of G2 -> one short serial sweep
     const int64_t nb = (n + lb - 1) / lb, ng = (nb + IIR_G1 - 1) / IIR_G1;
     const bool three = ng > 2 * IIR_G2;
@@ -976,7 +947,7 @@ static int iir_parallel(dd_iir* h, const double* in, double* out, int64_t n, int
     iir_coef(h, &C);
     const unsigned gb = (unsigned)((nb * ncomp + 255) / 256);
     // LDS-staged block kernels need 16-byte aligned buffers (always true for whole device arrays)
-    const bool staged = !(((uintptr_t)in | (uintptr_t)out) & 15) && !DD_TUNE_ENV("DD_IIR_UNSTAGED");
+    const bool staged = !(((uintptr_t)in | (uintptr_t)out) & 15);
     const unsigned gbt = (unsigned)((nb + 256 / ncomp - 1) / (256 / ncomp));
     const size_t lds_t = sizeof(double) * 2 * (256 / ncomp) * iir_lds_row(ncomp);
 #define DD_IIR_BLOCKS(SS, WR, SAVE)                                                                                  \
@@ -996,9 +967,8 @@ static int iir_parallel(dd_iir* h, const double* in, double* out, int64_t n, int
         DD_IIR_BLOCKS(13, WR, SAVE) DD_IIR_BLOCKS(14, WR, SAVE) DD_IIR_BLOCKS(15, WR, SAVE)                           \
         default: break;                                                                                              \
     }
-    // complex128 input: the one-wave LDS-DMA form (DD_IIR_WAVE=0 keeps the 256-thread staged kernels: A/B switch)
-    static const bool wave_env = !(DD_TUNE_ENV("DD_IIR_WAVE") && atoi(DD_TUNE_ENV("DD_IIR_WAVE")) == 0);
-    const bool wave = staged && ncomp == 2 && wave_env && (lb % IIR_W_CH) == 0;
+    // complex128 input: the one-wave LDS-DMA form
+    const bool wave = staged && ncomp == 2 && (lb % IIR_W_CH) == 0;
     const unsigned gbw = (unsigned)((nb + IIR_W_BLOCKS - 1) / IIR_W_BLOCKS);
     const size_t lds_w = (size_t)IIR_W_NB * IIR_W_BUF;
 #define DD_IIR_BLOCKS_W(SS, WR, SAVE)                                                                                \
@@ -1111,7 +1081,7 @@ extern "C" int dd_iir_c64(dd_iir* h, const void* in_c64, double* out_c128, int64
     DD_REQUIRE(in_c64 && out_c128 && (const void*)in_c64 != (const void*)out_c128, "buffers");
     hipStream_t s = dd_stream(stream);
     const bool aligned = !(((uintptr_t)in_c64 | (uintptr_t)out_c128) & 15);
-    if (n >= 16 * IIR_LB_SHORT && h->n >= 2 && aligned && !DD_TUNE_ENV("DD_IIR_WIDEN"))
+    if (n >= 16 * IIR_LB_SHORT && h->n >= 2 && aligned)
         return iir_parallel(h, (const double*)in_c64, out_c128, n, 2, carry, s, true);
     hipLaunchKernelGGL(k_iir_widen_c64, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const float2*)in_c64, (double2*)out_c128, n);
     DDIirCoef C;

@@ -1,10 +1,11 @@
-// k_chain_mfma_ab -- the FM-output interior kernel with TWO alternating sets of matrix waves
-// (included by dd_mfma.hip after k_chain_mfma_ws, whose helpers and LDS plane image it shares).
+// k_chain_mfma_ab -- the interior kernel of the M = 1 MFMA path, with TWO alternating sets of matrix waves
+// (included by dd_mfma.hip, whose tile geometry, LDS plane image and edge-tile code it uses).
 //
-// Where k_chain_mfma_ws loses its time (PMC, profiles/r01_mfma_ws_pmc_sq.txt: matrix pipe 56 % busy): inside a
-// phase the matrix wave of a SIMD first runs its own discriminator unit, then the 108 MFMAs, then waits for the
-// y-buffer, copies its accumulators into it and meets the barrier -- 1460 of 5110 cycles with the pipe idle -- and
-// the FIR outputs take a round trip through LDS (32 KB written and read per tile) on their way to the discriminator.
+// Why two sets: with ONE matrix wave per SIMD (round 1's y-buffer kernel; PMC, profiles/r01_mfma_ws_pmc_sq.txt:
+// matrix pipe 56 % busy), inside a phase the matrix wave of a SIMD first runs its own discriminator unit, then the 108
+// MFMAs, then waits for the y-buffer, copies its accumulators into it and meets the barrier -- 1460 of 5110 cycles with
+// the pipe idle -- and the FIR outputs take a round trip through LDS (32 KB written and read per tile) on their way to
+// the discriminator.
 //
 // Here a SIMD hosts two matrix waves, A and B, that alternate tiles:
 //
@@ -16,12 +17,13 @@
 // no hand-over counter, no LDS traffic for the outputs.  In the accumulator layout a lane holds column j of 16
 // rows, so y[n-1] is the same register one lane to the left (DPP row_shr:1); only the first lane of each 16-lane
 // row needs a value DPP cannot deliver, which lanes 15/31/47/63 leave in a 2 KB LDS table at the end of the MFMA
-// phase (column 0 takes the previous row's column 31; the last output of a strip goes to its right-hand neighbour).  The 8 remaining waves (two per SIMD) do what the 12 vector
-// waves of k_chain_mfma_ws do minus the discriminator: tile loads two phases ahead, NCO rotation + f16 limb split
-// into the plane buffer of the next tile, and the next tile's range check.  Registers: 128 per wave either way
+// phase (column 0 takes the previous row's column 31; the last output of a strip goes to its right-hand neighbour).  The 8 remaining waves (two per SIMD) are vector
+// waves: tile loads two phases ahead, NCO rotation + f16 limb split into the plane buffer of the next tile, and the
+// next tile's range check.  Registers: 128 per wave either way
 // (16 waves); LDS: two plane buffers + tap fragments (124 KB).
 #pragma once
 
+#define AB_THREADS 1024       // 8 matrix waves (two sets of 4) + AB_VWAVES vector waves
 #define AB_VWAVES 8
 #define AB_VTHREADS (64 * AB_VWAVES)
 #define AB_REG_ROWS 16        // accumulator registers (of 16) whose outputs the owning matrix wave turns into angles itself (with 8
@@ -33,12 +35,6 @@
 #ifndef DD_AB_VEC_PRIO
 #define DD_AB_VEC_PRIO 0
 #endif
-// The round-2 experiments that were built, parity-tested, measured and found no faster (boundary table
-// deferred, first k-step prefetched across the barrier, ratio-form discriminator, grouped fragment reads, the halo step
-// on a vector wave) are no longer switches of this header: tools/variants/mfma_ab_switches.patch puts them back.
-// timing ablations (tools/mkvariant.sh ... -DDD_AB_NO_xxx; results are wrong by construction, never shipped):
-//   DD_AB_NO_EPI      matrix waves skip the discriminator      DD_AB_NO_MFMA   matrix waves skip the MFMAs
-//   DD_AB_NO_CONVERT  vector waves skip the rotation / split   DD_AB_NO_LOAD   vector waves skip the tile loads
 
 template <int NKS>
 struct AbGeom {
@@ -103,7 +99,6 @@ __device__ __forceinline__ AbRaw dd_ab_load_quad(const DDChainParams& P, int b, 
         return r;
     }
     const char* base = reinterpret_cast<const char*>(reinterpret_cast<const float2*>(P.in) + ns);   // wave-uniform
-#ifndef DD_AB_NO_SADDR
     // told to the compiler in so many words (both halves through readfirstlane, and back into the GLOBAL address space:
     // a pointer rebuilt from an integer is a generic pointer, its loads are flat loads and a flat load's wait is
     // vmcnt(0)): the loads then take the tile's base from scalar registers and a 32-bit lane offset -- no 64-bit
@@ -117,10 +112,6 @@ __device__ __forceinline__ AbRaw dd_ab_load_quad(const DDChainParams& P, int b, 
     const ab_v4f vb = *(const __attribute__((address_space(1))) ab_v4f*)(gb + 32u * (unsigned)q + 16u);
     r.a = make_float4(va.x, va.y, va.z, va.w);
     r.b = make_float4(vb.x, vb.y, vb.z, vb.w);
-#else
-    r.a = *reinterpret_cast<const float4*>(base + 32u * (unsigned)q);
-    r.b = *reinterpret_cast<const float4*>(base + 32u * (unsigned)q + 16u);
-#endif
     return r;
 }
 
@@ -138,7 +129,12 @@ __device__ __forceinline__ void dd_ab_split2(float x0, float x1, uint32_t& hi, u
     asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(lo) : "v"(t0), "v"(t1));
 }
 
-// rotate (tile-relative NCO phase, see dd_ws_convert), split into f16 limbs, write 8 bytes into each of the four planes
+// rotate, split into f16 limbs, write 8 bytes into each of the four planes.  The NCO phase is TILE-RELATIVE:
+// x[n] e^{-j w (n0+k)} = e^{-j w n0} (x[n] e^{-j w k}).  The lane's phasors W[k] (k = its fixed positions inside a tile)
+// are loop invariant; the per-tile factor e^{-j w n0} is common to every output of the tile, so it cancels in the
+// discriminator's y[n] conj(y[n-1]) and is applied for complex output only (dd_ab_store_cx).  Plain v_fma/v_mul on
+// purpose: packed f32 ops beside the matrix waves' MFMAs cost ~5x a plain op (measured: the vector phases ran 2.3x
+// slower with v_pk_*).
 template <int NKS, bool UNIT_SCALE>
 __device__ __forceinline__ void dd_ab_convert_quad(const AbRaw& raw, char* planes, int q, const float2 (&wk)[4], float scale) {
     using G = MfmaGeom<NKS>;
@@ -169,7 +165,8 @@ __device__ __forceinline__ float dd_ab_absmax(const AbRaw& r, float m) {
 
 // "does the tile fit the f16 limbs unscaled" -- this wave's share of the answer for the tile in slot `slot`:
 // red entry `ent` = 1.0 (any value of the unit range) when all of the wave's samples lie below 32768 and at least one
-// reaches 0.25, else the wave's true maximum together with the tile's non-unit flag (see dd_ws_vphase)
+// reaches 0.25, else the wave's true maximum (DPP reduction, result in lane 63) together with the tile's non-unit flag.
+// The maximum over the waves' entries then still selects the same scale as the tile's exact maximum would.
 __device__ __forceinline__ void dd_ab_publish_range(float m, char* smem, int red_off, int nonunit_off, int slot, int ent, int lane) {
     const bool hi_any = __builtin_amdgcn_ballot_w64(!(m < 32768.0f)) != 0;
     const bool lo_any = __builtin_amdgcn_ballot_w64(m >= 0.25f) != 0;
@@ -189,7 +186,9 @@ __device__ __forceinline__ float dd_ab_tile_scale(const char* smem, int red_off,
 #pragma unroll
         for (int k = 1; k < AB_RED_ENTRIES; ++k) m = fmaxf(m, red[k]);
     }
-    unit = (m >= 0.25f) && (m < 32768.0f);                 // the f16 limbs hold the tile unscaled (see dd_ws_vphase)
+    // the f16 limbs hold the tile as it is when its peak lies in [0.25, 32768): the hi limb cannot overflow after the
+    // rotation, and the lo limb's subnormal floor stays below 2^-22 of the peak (8-bit SDR samples peak at 181)
+    unit = (m >= 0.25f) && (m < 32768.0f);
     return unit ? 1.0f : dd_pow2_scale_for(m);
 }
 
@@ -241,39 +240,29 @@ __device__ __forceinline__ void dd_ab_unit_store(const DDChainParams& P, int b, 
     }
 }
 
-#define DD_AB_STAMP(i) if (stamp) { const unsigned long long tn = __builtin_readcyclecounter(); acc_t[i] += tn - tp; tp = tn; }
-
 // one vector-wave phase p: loads of tile p+2 | conversion of tile p | range check of tile p+1 | barrier
 template <int NKS, bool U8, bool CX>
 __device__ __forceinline__ void dd_ab_vphase(const DDChainParams& P, char* smem, int t_begin, int n, int p,
                                              AbRaw (&rcur)[AB_VSTEPS], AbRaw (&rnext)[AB_VSTEPS], AbRaw (&rld)[AB_VSTEPS],
                                              const float2 (&wk)[AB_VSTEPS][4],
-                                             int vt, int vw, int lane, bool stamp, unsigned long long (&acc_t)[8],
-                                             AbRaw& xraw, const float2 (&wkx)[4]) {
+                                             int vt, int vw, int lane, AbRaw& xraw, const float2 (&wkx)[4]) {
     using A = AbGeom<NKS>;
     using Q = AbQ<NKS>;
-    unsigned long long tp = stamp ? __builtin_readcyclecounter() : 0;
     // the tile's non-unit flag is requested first: its LDS round trip (hundreds of cycles behind the matrix waves'
     // fragment stream) passes under the address arithmetic and the issue of the tile loads
     const int nu_flag = reinterpret_cast<const int*>(smem + A::NONUNIT_OFF)[p & 3];
-#ifndef DD_AB_NO_LOAD
     {
         const int bl = t_begin + (p + 2 < n ? p + 2 : n - 1);   // past the end: harmless re-read, never used
 #pragma unroll
         for (int st = 0; st < AB_VSTEPS; ++st) rld[st] = dd_ab_load_quad<NKS, U8>(P, bl, Q::XQUADS + vt + AB_VTHREADS * st);
     }
-#endif
     // this wave's unit of the discriminator of tile p-2 (its MFMAs ran in phase p-1, by set (p-1) & 1): the outputs
     // are requested from LDS now and turned into angles behind the conversion
     const bool do_unit = AB_REG_ROWS < 16 && p >= 2 && p - 2 < n;
     AbUnit ud;
     ud.r4 = ud.i4 = make_float4(1.f, 0.f, 0.f, 0.f);
     ud.ym = make_float2(1.f, 0.f);
-#ifndef DD_AB_NO_EPI
     if (do_unit) ud = dd_ab_unit_read<NKS>(reinterpret_cast<const float*>(smem + A::YH_OFF + ((p - 1) & 1) * A::YH_SET_BYTES), vw, lane);
-#endif
-    DD_AB_STAMP(0)
-#ifndef DD_AB_NO_CONVERT
     if (p < n) {                                            // convert tile p (range published in phase p-1)
         bool unit;
         const float scale = dd_ab_tile_scale(smem, A::RED_OFF, nu_flag, p, unit);
@@ -287,24 +276,18 @@ __device__ __forceinline__ void dd_ab_vphase(const DDChainParams& P, char* smem,
         }
         dd_ab_conv_done(smem, A::CONVCNT_OFF, p, lane);
     }
-#endif
-    DD_AB_STAMP(1)
-#ifndef DD_AB_NO_EPI
     if (do_unit) dd_ab_unit_store(P, t_begin + p - 2, vw, lane, ud);
-#endif
     if (p + 1 < n) {                                        // does tile p+1 fit the f16 limbs unscaled?
         float m = 0.f;
 #pragma unroll
         for (int st = 0; st < AB_VSTEPS; ++st) m = dd_ab_absmax(rnext[st], m);
         dd_ab_publish_range(m, smem, A::RED_OFF, A::NONUNIT_OFF, p + 1, vw, lane);
     }
-    DD_AB_STAMP(2)
     __syncthreads();
-    DD_AB_STAMP(3)
 }
 
-template <int NKS, bool U8, bool CX, bool ST>
-__device__ __forceinline__ void dd_ab_vector(const DDChainParams& P, const DDMfmaTaps& taps, char* smem, int t_begin, int t_end, int nph) {
+template <int NKS, bool U8, bool CX>
+__device__ __forceinline__ void dd_ab_vector(const DDChainParams& P, char* smem, int t_begin, int t_end, int nph) {
     using A = AbGeom<NKS>;
     using Q = AbQ<NKS>;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -339,16 +322,10 @@ __device__ __forceinline__ void dd_ab_vector(const DDChainParams& P, const DDMfm
     }
     __syncthreads();                                        // prologue barrier (matched in dd_ab_matrix)
     if (DD_AB_VEC_PRIO) __builtin_amdgcn_s_setprio(DD_AB_VEC_PRIO);
-    const bool stamp = ST && taps.stamps != nullptr;       // ST: the in-kernel stamps are compiled in (tools only: ~30 scalar instructions per wave and phase)
-    unsigned long long acc_t[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     for (int p = 0; p < nph; p += 3) {                      // nph is a multiple of 6
-        dd_ab_vphase<NKS, U8, CX>(P, smem, t_begin, n, p, r0, r1, r2, wk, vt, vw, lane, stamp, acc_t, xraw, wkx);
-        dd_ab_vphase<NKS, U8, CX>(P, smem, t_begin, n, p + 1, r1, r2, r0, wk, vt, vw, lane, stamp, acc_t, xraw, wkx);
-        dd_ab_vphase<NKS, U8, CX>(P, smem, t_begin, n, p + 2, r2, r0, r1, wk, vt, vw, lane, stamp, acc_t, xraw, wkx);
-    }
-    if (stamp && lane == 0) {
-        for (int q = 0; q < 4; ++q) taps.stamps[((size_t)blockIdx.x * 16 + (tid >> 6)) * 8 + q] = acc_t[q];
-        taps.stamps[((size_t)blockIdx.x * 16 + (tid >> 6)) * 8 + 7] = (unsigned long long)nph | ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) << 32);
+        dd_ab_vphase<NKS, U8, CX>(P, smem, t_begin, n, p, r0, r1, r2, wk, vt, vw, lane, xraw, wkx);
+        dd_ab_vphase<NKS, U8, CX>(P, smem, t_begin, n, p + 1, r1, r2, r0, wk, vt, vw, lane, xraw, wkx);
+        dd_ab_vphase<NKS, U8, CX>(P, smem, t_begin, n, p + 2, r2, r0, r1, wk, vt, vw, lane, xraw, wkx);
     }
 }
 
@@ -433,15 +410,6 @@ __device__ __forceinline__ void dd_ab_epilogue(const DDChainParams& P, int b, in
     }
     // 4. row r of the lane is output 32 (rowbase(r) + 4 h) + j: 128 contiguous bytes per half wave and row.
     //    The tile's first 32 outputs (strip 0, row 0) belong to the previous tile.
-#ifdef DD_AB_NO_STORE
-    if (P.K != 12345) {                                    // (ablation: angles computed, one store per strip)
-        float sum = 0.f;
-#pragma unroll
-        for (int r = 0; r < NR; ++r) sum += a[r];
-        out[0] = sum;
-        return;
-    }
-#endif
     if (mw != 0 || h != 0) out[0] = a[0];
 #pragma unroll
     for (int r = 1; r < NR; ++r) out[32 * ((r & 3) + 8 * (r >> 2))] = a[r];
@@ -509,13 +477,11 @@ __device__ __forceinline__ void dd_ab_publish_last(int lane, const v16f& cre, co
     }
 }
 __device__ __forceinline__ void dd_ab_publish(int lane, int mw, const v16f& cre, const v16f& cim, float2* xtab0, float2* x0w, float2* xaw, float2* x1w, float2* xbw) {
-#ifndef DD_AB_NO_X0_SELF          // (-DDD_AB_NO_X0_SELF: the round-2 bug, for checking that tests/test_gpu_determinism.py catches it)
     if (mw == 0 && lane == 0) {
         float* d = reinterpret_cast<float*>(xtab0);          // (strip 0's X0 = the set's table base: a constant address, no register kept for it)
         d[0] = cre[0];
         d[1] = cim[0];
     }
-#endif
     if ((lane & 15) == 15) {
         const int g = lane >> 4;
         float2* pa = g == 0 ? xaw : (g == 1 ? x0w + 1 : (g == 2 ? xbw : x1w + 1));     // (q & 3) != 3
@@ -530,6 +496,43 @@ __device__ __forceinline__ void dd_ab_publish(int lane, int mw, const v16f& cre,
     }
 }
 
+// The MFMA loop of a strip: a software pipeline of distance two k-steps.  The six fragments of k-step ks+2 are issued
+// during the six MFMAs of k-step ks, one read per MFMA gap (no read burst between MFMA groups), so a fragment has
+// ~250-380 cycles to arrive; sched_barrier pins the order.  (Expanded where abase, tb, f, cre, cim, G and NKS are in scope.)
+#define DD_AB_LOADF(buf, ks)                                                                     \
+        {                                                                                        \
+            const int off_ = 32 * (ks) + 16 * ((ks) >> 1);                                       \
+            f[buf][0] = *reinterpret_cast<const v8h*>(abase + off_);                             \
+            f[buf][1] = *reinterpret_cast<const v8h*>(abase + G::PLANE + off_);                  \
+            f[buf][2] = *reinterpret_cast<const v8h*>(abase + 2 * G::PLANE + off_);              \
+            f[buf][3] = *reinterpret_cast<const v8h*>(abase + 3 * G::PLANE + off_);              \
+            f[buf][4] = tb[(ks) * 64];                                                           \
+            f[buf][5] = tb[(NKS + (ks)) * 64];                                                   \
+        }
+// one k-step: the six MFMAs of buffer `buf`, with one fragment read of k-step ksn (buffer nb) in each MFMA gap
+#define DD_AB_KSTEP(buf, nb, ksn, pre)                                                           \
+        {                                                                                        \
+            const int off_ = 32 * (ksn) + 16 * ((ksn) >> 1);                                     \
+            cre = __builtin_amdgcn_mfma_f32_32x32x16_f16(f[buf][0], f[buf][4], cre, 0, 0, 0);   \
+            if (pre) f[nb][0] = *reinterpret_cast<const v8h*>(abase + off_);                     \
+            __builtin_amdgcn_sched_barrier(0);                                                   \
+            cim = __builtin_amdgcn_mfma_f32_32x32x16_f16(f[buf][2], f[buf][4], cim, 0, 0, 0);   \
+            if (pre) f[nb][4] = tb[(ksn) * 64];                                                  \
+            __builtin_amdgcn_sched_barrier(0);                                                   \
+            cre = __builtin_amdgcn_mfma_f32_32x32x16_f16(f[buf][1], f[buf][4], cre, 0, 0, 0);   \
+            if (pre) f[nb][2] = *reinterpret_cast<const v8h*>(abase + 2 * G::PLANE + off_);      \
+            __builtin_amdgcn_sched_barrier(0);                                                   \
+            cim = __builtin_amdgcn_mfma_f32_32x32x16_f16(f[buf][3], f[buf][4], cim, 0, 0, 0);   \
+            if (pre) f[nb][1] = *reinterpret_cast<const v8h*>(abase + G::PLANE + off_);          \
+            __builtin_amdgcn_sched_barrier(0);                                                   \
+            cre = __builtin_amdgcn_mfma_f32_32x32x16_f16(f[buf][0], f[buf][5], cre, 0, 0, 0);   \
+            if (pre) f[nb][3] = *reinterpret_cast<const v8h*>(abase + 3 * G::PLANE + off_);      \
+            __builtin_amdgcn_sched_barrier(0);                                                   \
+            cim = __builtin_amdgcn_mfma_f32_32x32x16_f16(f[buf][2], f[buf][5], cim, 0, 0, 0);   \
+            if (pre) f[nb][5] = tb[(NKS + (ksn)) * 64];                                          \
+            __builtin_amdgcn_sched_barrier(0);                                                   \
+        }
+
 // fragments of k-steps 0 and 1 of a strip (what the MFMA loop needs before its first instruction)
 #ifndef AB_HEAD_KSTEPS
 #define AB_HEAD_KSTEPS 1      // k-steps requested a phase early: 2 would cover the whole start-up, and spills (48 live registers across the barrier)
@@ -537,8 +540,8 @@ __device__ __forceinline__ void dd_ab_publish(int lane, int mw, const v16f& cre,
 template <int NKS, int FIRST, int LAST>
 __device__ __forceinline__ void dd_ab_frag_head(const char* abase, const v8h* tb, v8h (&f)[3][6]) {
     using G = MfmaGeom<NKS>;
-    if (FIRST <= 0 && 0 < LAST) { DD_WS_LOADF(0, 0) }
-    if (FIRST <= 1 && 1 < LAST) { DD_WS_LOADF(1, 1) }
+    if (FIRST <= 0 && 0 < LAST) { DD_AB_LOADF(0, 0) }
+    if (FIRST <= 1 && 1 < LAST) { DD_AB_LOADF(1, 1) }
 }
 template <int NKS>
 __device__ __forceinline__ void dd_ab_mfma_strip(const char* abase, const v8h* tb, v16f& cre, v16f& cim, v8h (&f)[3][6], bool have_head) {
@@ -549,9 +552,9 @@ __device__ __forceinline__ void dd_ab_mfma_strip(const char* abase, const v8h* t
     dd_ab_frag_head<NKS, AB_HEAD_KSTEPS, 2>(abase, tb, f);
 #pragma unroll
     for (int ks = 0; ks < NKS - 1; ++ks) {
-        DD_WS_STEP(ks % 3, (ks + 2) % 3, (ks + 2 < NKS ? ks + 2 : ks), (ks + 2 < NKS))
+        DD_AB_KSTEP(ks % 3, (ks + 2) % 3, (ks + 2 < NKS ? ks + 2 : ks), (ks + 2 < NKS))
     }
-    DD_WS_STEP((NKS - 1) % 3, (NKS + 1) % 3, NKS - 1, false)
+    DD_AB_KSTEP((NKS - 1) % 3, (NKS + 1) % 3, NKS - 1, false)
 }
 
 // End of a set's discriminator phase: if every converting wave has reported tile t = qnext - 1 (the set's next MFMA
@@ -567,7 +570,6 @@ template <int NKS, bool U8>
 __device__ __forceinline__ void dd_ab_halo_convert(const DDChainParams& P, char* smem, int t_begin, int n, int q, int lane,
                                                    AbRaw& xraw, const float4* wkx_lds, int nu_flag) {
     using A = AbGeom<NKS>;
-#ifndef DD_AB_NO_CONVERT
     if (q < n) {
         bool unit;
         const float scale = dd_ab_tile_scale(smem, A::RED_OFF, nu_flag, q, unit);
@@ -580,14 +582,11 @@ __device__ __forceinline__ void dd_ab_halo_convert(const DDChainParams& P, char*
         }
         dd_ab_conv_done(smem, A::CONVCNT_OFF, q, lane);
     }
-#endif
-#ifndef DD_AB_NO_LOAD
     // the set's next tile (two phases ahead); lanes past the halo re-read its last quad (never written)
     xraw = dd_ab_load_quad<NKS, U8>(P, t_begin + (q + 2 < n ? q + 2 : n - 1), lane < AbQ<NKS>::XQUADS ? lane : AbQ<NKS>::XQUADS - 1);
-#endif
 }
 
-template <int NKS, int SET, bool U8, bool CX, bool ST>
+template <int NKS, int SET, bool U8, bool CX>
 __device__ __forceinline__ void dd_ab_matrix(const DDChainParams& P, const DDMfmaTaps& taps, char* smem, int t_begin, int t_end, int nph) {
     using A = AbGeom<NKS>;
     const int tid = threadIdx.x, lane = tid & 63, mw = (tid >> 6) & 3;
@@ -622,10 +621,6 @@ __device__ __forceinline__ void dd_ab_matrix(const DDChainParams& P, const DDMfm
     }
     __syncthreads();                                        // prologue barrier (tile 0's range is published)
 
-    const bool stamp = ST && taps.stamps != nullptr;       // ST: the in-kernel stamps are compiled in (tools only: ~30 scalar instructions per wave and phase)
-    unsigned long long acc_t[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    const unsigned long long t_clk0 = stamp ? __builtin_readcyclecounter() : 0;
-    const unsigned long long t_rt0 = stamp ? __builtin_amdgcn_s_memrealtime() : 0;
     v16f cre, cim;
 #pragma unroll
     for (int r = 0; r < 16; ++r) { cre[r] = 0.f; cim[r] = 0.f; }
@@ -636,39 +631,27 @@ __device__ __forceinline__ void dd_ab_matrix(const DDChainParams& P, const DDMfm
     // consumed at the start of the second, so nothing but the accumulators is live across the loop's back edge.
     // Set 0's phase 0 has no tile to compute: only the range of the halo it converts in phase 1.
     if (SET == 0) {
-        unsigned long long tp = stamp ? __builtin_readcyclecounter() : 0;
         if (halo && 1 < n) dd_ab_publish_range(dd_ab_absmax(xraw, 0.f), smem, A::RED_OFF, A::NONUNIT_OFF, 1, AB_VWAVES, lane);
-        DD_AB_STAMP(0)
         __syncthreads();
-        DD_AB_STAMP(2)
     }
     for (int pe = 1 - SET; pe < nph; pe += 2) {
-        unsigned long long tp = stamp ? __builtin_readcyclecounter() : 0;
         const int qm = pe + 1;                              // this set's MFMA phase of the pair (tile pe)
         {   // phase pe: the rest of tile pe - 2's table, halo step of tile pe, discriminator of tile pe - 2
             const bool epi = pe >= 2 && pe - 2 < n;
             const int nu_flag = halo ? reinterpret_cast<const int*>(smem + A::NONUNIT_OFF)[pe & 3] : 0;
             if (halo) dd_ab_halo_convert<NKS, U8>(P, smem, t_begin, n, pe, lane, xraw, wkx_lds, nu_flag);
-#ifndef DD_AB_NO_EPI
             if (epi) {
                 if (CX) dd_ab_store_cx<NKS>(P, taps, smem, t_begin + pe - 2, pe - 2, mw, lane, cre, cim);
                 else dd_ab_epilogue<NKS>(P, t_begin + pe - 2, mw, lane, cre, cim, xrd);
             }
-#endif
             head = dd_ab_try_head<NKS>(smem, n, qm, aoff, tb, f);
-            DD_AB_STAMP(1)
             __syncthreads();
-            DD_AB_STAMP(2)
         }
         if (qm >= nph) break;                               // (set 0: the phase after the last one)
         if (qm <= n) {
             __builtin_amdgcn_s_setprio(3);                  // MFMAs issue as soon as the pipe frees up
             const char* abase = smem + (pe & 1) * A::PLANES_BYTES + aoff;
-#ifndef DD_AB_NO_MFMA
             dd_ab_mfma_strip<NKS>(abase, tb, cre, cim, f, head);
-#else
-            (void)abase; (void)tb;
-#endif
             if (!CX) dd_ab_publish(lane, mw, cre, cim, reinterpret_cast<float2*>(smem + A::BCOL_OFF + SET * A::BCOL_SET_BYTES), x0, xa, x1, xb);
             if (AB_REG_ROWS < 16)
                 dd_ab_write_yhalf(lane, cre, cim, reinterpret_cast<float*>(smem + A::YH_OFF + SET * A::YH_SET_BYTES) + mw * A::YH_STRIDE, 4 * A::YH_STRIDE);
@@ -676,31 +659,20 @@ __device__ __forceinline__ void dd_ab_matrix(const DDChainParams& P, const DDMfm
         }
         // range of the halo the set converts in its next discriminator phase (tile qm + 1, requested a phase ago)
         if (halo && qm + 1 < n) dd_ab_publish_range(dd_ab_absmax(xraw, 0.f), smem, A::RED_OFF, A::NONUNIT_OFF, qm + 1, AB_VWAVES, lane);
-        DD_AB_STAMP(0)
         __syncthreads();
-        DD_AB_STAMP(2)
-    }
-    if (stamp && lane == 0) {
-        const size_t w = (size_t)blockIdx.x * 16 + (tid >> 6);
-        if ((tid >> 6) == 0) {   // in-kernel clock: shader ticks per 100 MHz reference tick over the whole loop
-            taps.stamps[w * 8 + 5] = __builtin_readcyclecounter() - t_clk0;
-            taps.stamps[w * 8 + 6] = __builtin_amdgcn_s_memrealtime() - t_rt0;
-            taps.stamps[((size_t)blockIdx.x * 16 + 1) * 8 + 4] = t_rt0;                              // loop start (abs)
-            taps.stamps[((size_t)blockIdx.x * 16 + 2) * 8 + 4] = __builtin_amdgcn_s_memrealtime();   // loop end (abs)
-        }
-        for (int q = 0; q < 3; ++q) taps.stamps[w * 8 + q] = acc_t[q];
-        taps.stamps[w * 8 + 7] = (unsigned long long)nph | ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) << 32);
     }
 }
 
 // U8: raw interleaved uint8 I,Q input.  CX: complex64 output (no DD_CHAIN_FM) instead of angles.
-template <int NKS, bool U8, bool CX, bool ST = false>
-__global__ void __launch_bounds__(WS_THREADS) k_chain_mfma_ab(const DDChainParams P, const DDMfmaTaps taps, int t_first, int t_last, int nwg) {
+template <int NKS, bool U8, bool CX>
+__global__ void __launch_bounds__(AB_THREADS) k_chain_mfma_ab(const DDChainParams P, const DDMfmaTaps taps, int t_first, int t_last, int nwg) {
     using A = AbGeom<NKS>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int wg = blockIdx.x;
     if (wg >= nwg) {
-        // edge tiles ([0, t_first) and [t_last, nblocks)) ride along as trailing 4-wave workgroups (see k_chain_mfma_ws)
+        // edge tiles ([0, t_first) and [t_last, nblocks)) ride along as trailing 4-wave workgroups: they are dispatched when
+        // the first persistent workgroups retire, i.e. inside the spread of the persistent workgroups' finish times, and
+        // cost no launch of their own
         if (threadIdx.x >= MF_THREADS) return;
         const int e = wg - nwg;
         const int b = e < t_first ? e : t_last + (e - t_first);
@@ -709,21 +681,20 @@ __global__ void __launch_bounds__(WS_THREADS) k_chain_mfma_ab(const DDChainParam
         dd_edge_tile_lean<NKS>(P, taps, b, smem, tl);
         return;
     }
-    if (ST && taps.stamps && threadIdx.x == 0) taps.stamps[((size_t)wg * 16) * 8 + 4] = __builtin_amdgcn_s_memrealtime();
     const int nt = t_last - t_first;
     const int t_begin = t_first + (int)(((int64_t)wg * nt) / nwg);
     const int t_end = t_first + (int)(((int64_t)(wg + 1) * nt) / nwg);
     if (t_begin >= t_end) return;
     {
         v8h* tl = reinterpret_cast<v8h*>(smem + A::TAPS_OFF);
-        for (int idx = threadIdx.x; idx < 2 * NKS * 64; idx += WS_THREADS) tl[idx] = taps.frag[idx];
+        for (int idx = threadIdx.x; idx < 2 * NKS * 64; idx += AB_THREADS) tl[idx] = taps.frag[idx];
         if (threadIdx.x < 4) reinterpret_cast<int*>(smem + A::NONUNIT_OFF)[threadIdx.x] = threadIdx.x == 0 ? 1 : 0;   // tile 0: read the true max
         if (threadIdx.x < 2 * AB_RED_ENTRIES) reinterpret_cast<float*>(smem + A::RED_OFF)[threadIdx.x] = 0.f;          // (unused entries stay 0)
         if (threadIdx.x < 4) reinterpret_cast<int*>(smem + A::YHCNT_OFF)[threadIdx.x] = 0;                            // (+ the two conversion counters)
     }
     __syncthreads();
     const int nph = ((t_end - t_begin + 2 + 5) / 6) * 6;      // phases: a multiple of the vector loop's 3 and the matrix sets' 2
-    if (threadIdx.x < 256) dd_ab_matrix<NKS, 0, U8, CX, ST>(P, taps, smem, t_begin, t_end, nph);
-    else if (threadIdx.x < 512) dd_ab_matrix<NKS, 1, U8, CX, ST>(P, taps, smem, t_begin, t_end, nph);
-    else dd_ab_vector<NKS, U8, CX, ST>(P, taps, smem, t_begin, t_end, nph);
+    if (threadIdx.x < 256) dd_ab_matrix<NKS, 0, U8, CX>(P, taps, smem, t_begin, t_end, nph);
+    else if (threadIdx.x < 512) dd_ab_matrix<NKS, 1, U8, CX>(P, taps, smem, t_begin, t_end, nph);
+    else dd_ab_vector<NKS, U8, CX>(P, smem, t_begin, t_end, nph);
 }

@@ -337,7 +337,7 @@ def _afsk_frames_run(src, offset):
     return cap
 
 
-def _afsk_frames_store(name, cap, extra):
+def _save_afsk_frames(name, cap, extra):
     from directdemod import framechecksequence
     es = cap["edge_sums"]
     assert np.array_equal(np.abs(np.round(es) / (22050 // 1200)), cap["pd_in"])     # peakdetect's input is |edge sums| / spb
@@ -385,13 +385,13 @@ def gen_afsk_frames():
     from directdemod import source
     import _ax25
     raw, fs, offset, _ = _ax25.fixture_a()
-    _afsk_frames_store("afsk_frames_a.npz", _afsk_frames_run(ArraySource(raw, fs), offset), {"fs": np.int64(fs)})
+    _save_afsk_frames("afsk_frames_a.npz", _afsk_frames_run(ArraySource(raw, fs), offset), {"fs": np.int64(fs)})
     raw, fs, offset, _ = _ax25.fixture_b()
     with tempfile.TemporaryDirectory() as td:
         path = os.path.join(td, _ax25.C1_NAME)
         _ax25.write_wav(path, raw, fs)
         cap = _afsk_frames_run(source.IQwav(path), offset)
-    _afsk_frames_store("afsk_frames_b.npz", cap, {"fs": np.int64(fs), "offset": np.int64(offset)})
+    _save_afsk_frames("afsk_frames_b.npz", cap, {"fs": np.int64(fs), "offset": np.int64(offset)})
 
 
 def _meteor_patterns():

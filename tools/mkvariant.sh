@@ -1,6 +1,6 @@
 #!/bin/bash
 # build/variants/lib_<N>.so from the current tree with extra -D flags for one translation unit:
-#   mkvariant.sh <N> <unit> [flags...]      e.g.  mkvariant.sh 1 dd_mfma -DDD_WS_SADDR
+#   mkvariant.sh <N> <unit> [flags...]      e.g.  mkvariant.sh 1 dd_decimw -DDW_TRIP=8
 cd "$(dirname "$0")/.."
 N=$1; U=$2; shift 2
 mkdir -p build/variants

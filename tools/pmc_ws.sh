@@ -1,5 +1,5 @@
 #!/bin/bash
-# SQ / LDS counters of the headline kernel (k_chain_mfma_ws, C2 workload), separate --pmc passes
+# SQ / LDS counters of the M = 1 MFMA kernels (k_chain_mfma_*, headline workload), separate --pmc passes
 cd /tmp && export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}; cd $R
 i=0
