@@ -35,6 +35,7 @@ DD_CHAIN_NCO, DD_CHAIN_FM, DD_CHAIN_U8_INPUT, DD_CHAIN_FORCE_DIRECT, DD_CHAIN_TI
 (DD_KERNEL_NONE, DD_KERNEL_DENSE_F32, DD_KERNEL_DECIM_TILES, DD_KERNEL_DECIM_PERSISTENT, DD_KERNEL_MFMA_WS,
  DD_KERNEL_MFMA_TILES, DD_KERNEL_MFMA_AB, DD_KERNEL_FFT_OS, DD_KERNEL_DECIM_MULTI, DD_KERNEL_COS_RS, DD_KERNEL_DECIM_WAVE,
  DD_KERNEL_DECIM_BLOCKS) = range(12)
+DD_FAMILY_DENSE, DD_FAMILY_TILES, DD_FAMILY_ROWS, DD_FAMILY_COS1K, DD_FAMILY_FFT1K, DD_FAMILY_MFMA = range(6)   # dd_debug_chain_select
 
 
 def decim_wave_kernel(K, M):
@@ -81,6 +82,7 @@ SIGNATURES = {
     "dd_debug_cos1k_plan": (_int, [_i64, _int, _int, _int, C.POINTER(_int)]),
     "dd_debug_decimw_plan": (_int, [_i64, _i64, _int, _int, _int, _int, C.POINTER(_i64)]),
     "dd_debug_decimb_lds_check": (_int, [_int, _int, _int, C.POINTER(_i64)]),
+    "dd_debug_chain_select": (_int, [C.POINTER(C.c_double), _int, _int, _int, _int, C.c_char_p, C.POINTER(_int)]),
     "dd_debug_cos_fit": (_int, [C.POINTER(C.c_double), _int, C.POINTER(C.c_double), C.POINTER(_int)]),
     "dd_debug_sync_envelope": (_int, [_p, _i64, _int, _int, _p, _p]),
     "dd_memcpy_h2d": (_int, [_p, _p, _sz, _p]),

@@ -8,59 +8,69 @@
 // ---- handles (host side) ------------------------------------------------------
 // filters.filter object: taps + carried history (filters.py:21-75)
 struct dd_fir {
-    int K;
+    int K = 0;
     std::vector<double> taps;
-    float* taps_rev;        // device: reversed taps, zero padded (direct-form kernels)
-    float2* tail[2];        // device: K-1 past inputs (complex64), ping-pong
-    float2* tail_const[2];  // device: constant histories (all zeros / all ones) for launch-free resets
-    const float2* tail_override;   // non-null: the next launch reads this history instead of tail[parity]
-    int parity;
-    void* mfma;             // f16-limb Toeplitz operand for the MFMA path (lazy)
-    int mfma_tried;
+    float* taps_rev = nullptr;                     // device: reversed taps, zero padded (direct-form kernels)
+    float2* tail[2] = {nullptr, nullptr};          // device: K-1 past inputs (complex64), ping-pong
+    float2* tail_const[2] = {nullptr, nullptr};    // device: constant histories (all zeros / all ones) for launch-free resets
+    const float2* tail_override = nullptr;         // non-null: the next launch reads this history instead of tail[parity]
+    int parity = 0;
+    // one lazily created state per M = 1 kernel family other than the dense one (dd_chain.hip, chain_select): the f16-limb
+    // Toeplitz fragments of the MFMA kernels (dd_mfma.hip), the overlap-save tables of k_chain_fft1k (dd_fftfir.hip), the
+    // running-sum constants of k_chain_cos1k (dd_cosfir.hip).  *_tried: a create that failed is not tried again.
+    void* mfma = nullptr;
+    void* fft = nullptr;
+    void* cos = nullptr;
+    int mfma_tried = 0, fft_tried = 0, cos_tried = 0;
     // float64 real path (audio rate)
-    double* taps_dev;
-    double* hist[2];
-    int hpar;
-    int hist_mode;
-    int last_kernel;        // DD_KERNEL_* of the last fused launch through this filter
-    long long launches;     // fused kernel launches through this filter (dd_fir_launch_count)
-    DDDecimWTaps dw_taps;   // k_chain_decim_w's padded taps (M = 0 mod 4), lazy
-    char* multi;            // chunk-list launches: seam flags, per-chunk parameter blocks, prefix tables, seam state (grow-only)
-    size_t multi_bytes;
-    // chunk-list launches: hand-overs that timed out (dd_seam_wait), counted on the device, mirrored into a pinned word
-    // behind every launch and looked at by the next chunk-list call on this filter and by dd_stream_sync
-    unsigned int* seam_err;         // device
-    unsigned int* seam_err_host;    // pinned
-    hipEvent_t seam_ev;             // recorded behind the mirror copy
-    int seam_pending;               // a mirror copy has been enqueued and not looked at yet
-    int state_invalid;              // a chunk-list launch through this filter timed out: the carried history and last FM sample it
-                                    // committed are not to be used -- every fused launch reports DD_ERR_TIMEOUT until dd_fir_reset
+    double* taps_dev = nullptr;
+    double* hist[2] = {nullptr, nullptr};
+    int hpar = 0;
+    int hist_mode = DD_HIST_ONES;
+    int last_kernel = DD_KERNEL_NONE;   // DD_KERNEL_* of the last fused launch through this filter
+    long long launches = 0;             // fused kernel launches through this filter (dd_fir_launch_count)
+    DDDecimWTaps dw_taps;               // k_chain_decim_w's padded taps (M = 0 mod 4), lazy
+    char* multi = nullptr;              // chunk-list launches: seam flags, per-chunk parameter blocks, prefix tables, seam state (grow-only)
+    size_t multi_bytes = 0;
+    // chunk-list launches: a hand-over wait that gives up (dd_seam_wait) counts itself, with a system-scope atomic, into word [0]
+    // of two words of pinned, mapped host memory (word [1]: where dd_debug_seam sends a withheld flag).  No copy, no event: the
+    // host reads the word -- every fused launch through this filter and dd_stream_sync look at it -- and it is final once the
+    // launch's stream has been synchronised.
+    unsigned int* seam_err_host = nullptr;   // the two words, host address
+    unsigned int* seam_err = nullptr;        // the same words, device address
+    int seam_pending = 0;                    // a chunk-list launch has been made: the word is looked at until the filter is destroyed
+    int state_invalid = 0;                   // a chunk-list launch through this filter timed out: the carried history and last FM sample it
+                                             // committed are not to be used -- every fused launch reports DD_ERR_TIMEOUT until dd_fir_reset
 };
 
 // demod_fm object: carried last sample (demod_fm.py:43-49)
 struct dd_fm {
-    float2* last;           // device: [2] ping-pong
-    int parity;
-    int has_last;           // host mirror of "self.__last is not None"
+    float2* last = nullptr; // device: [2] ping-pong
+    int parity = 0;
+    int has_last = 0;       // host mirror of "self.__last is not None"
 };
 
 // core fused launch (dd_chain.hip); state is read from / written to fir and fm
 struct DDFusedArgs {
-    const void* in;
-    void* out;
-    int64_t n;
-    int nco;                // apply offsetFreq
-    uint64_t cyc;
-    int64_t start_index;    // absolute index of in[0] for the NCO phase
-    int M;                  // decimation
-    int off;                // chunk-relative index of the first kept sample
-    int u8;                 // input is interleaved u8 I,Q
-    int commit;             // carry the state forward (storeState)
-    int force_direct;
-    int tight;              // DD_CHAIN_TIGHT: no running-sum kernel
+    const void* in = nullptr;
+    void* out = nullptr;
+    int64_t n = 0;
+    uint64_t cyc = 0;
+    int64_t start_index = 0;    // absolute index of in[0] for the NCO phase
+    int M = 1;                  // decimation
+    int off = 0;                // chunk-relative index of the first kept sample
+    int flags = 0;              // DD_CHAIN_NCO | DD_CHAIN_U8_INPUT | DD_CHAIN_FORCE_DIRECT | DD_CHAIN_TIGHT (DD_CHAIN_FM: by the fm handle)
+    int commit = 0;             // carry the state forward (storeState)
 };
 int dd_fused_launch(dd_fir* fir, dd_fm* fm, const DDFusedArgs& a, int64_t* n_out, hipStream_t s);
 int64_t dd_fused_out_count(const dd_fm* fm, int64_t n, int M, int off);
+
+// MFMA kernels (dd_mfma.hip): M = 1, up to 257 taps.  dd_mfma_supported: the k-step count of the tap class (6, 10, 12, 18), 0 = not taken.
+// dd_mfma_launch: P as dd_fused_launch fills it; *kernel_id = DD_KERNEL_MFMA_AB or DD_KERNEL_MFMA_TILES
+int dd_mfma_supported(int K, int M);
+int dd_mfma_create(void** st, const double* taps, int K);
+void dd_mfma_destroy(void* st);
+int dd_mfma_launch(void* st, const struct DDChainParams& P, hipStream_t s, int* kernel_id);
 
 struct DDChainParams {
     const void* in;            // complex64 (float2) or interleaved u8

@@ -29,10 +29,6 @@
 //   k_chain_mfma_edge  stream start/end, unaligned or u8 input, partial tiles: one tile
 //                      per 4-wave workgroup, fully predicated, same MFMA core.
 #include "dd_chain_kernels.h"
-#include "dd_fftfir.h"
-#include "dd_cosfir.h"
-#include <stdlib.h>
-#include <atomic>
 
 typedef _Float16 v8h __attribute__((ext_vector_type(8)));
 typedef _Float16 v2h __attribute__((ext_vector_type(2)));
@@ -448,15 +444,9 @@ __device__ __forceinline__ float dd_wave_max(float m) {
 // host side
 // ============================================================================
 struct DDMfmaState {
-    int K;
-    int nks;
-    v8h* frag;          // device
-    float inv_tapscale;
-    std::vector<double> taps;
-    void* fft;          // overlap-save FFT form of the interior run (dd_fftfir.hip), lazy
-    int fft_tried;
-    void* cos;          // running-sum form for cosine-series windows of 255 taps (dd_cosfir.hip), lazy
-    int cos_tried;
+    int nks = 0;
+    v8h* frag = nullptr;        // device
+    float inv_tapscale = 1.f;
 };
 
 static int mfma_nks_for(int K) {
@@ -466,9 +456,8 @@ static int mfma_nks_for(int K) {
     return 0;
 }
 
-int dd_mfma_supported(int K, int M, int flags) {
-    (void)flags;
-    return (M == 1 && mfma_nks_for(K) != 0) ? 1 : 0;
+int dd_mfma_supported(int K, int M) {
+    return M == 1 ? mfma_nks_for(K) : 0;
 }
 
 int dd_mfma_create(void** st, const double* taps, int K) {
@@ -500,15 +489,8 @@ int dd_mfma_create(void** st, const double* taps, int K) {
         }
     }
     DDMfmaState* s = new DDMfmaState();
-    s->K = K;
     s->nks = nks;
-    s->frag = nullptr;
     s->inv_tapscale = (float)(1.0 / tapscale);
-    s->taps.assign(taps, taps + K);
-    s->fft = nullptr;
-    s->fft_tried = 0;
-    s->cos = nullptr;
-    s->cos_tried = 0;
     hipError_t e = hipMalloc((void**)&s->frag, frag.size() * sizeof(_Float16));
     if (e == hipSuccess) e = hipMemcpy(s->frag, frag.data(), frag.size() * sizeof(_Float16), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
@@ -524,43 +506,8 @@ int dd_mfma_create(void** st, const double* taps, int K) {
 void dd_mfma_destroy(void* st) {
     DDMfmaState* s = reinterpret_cast<DDMfmaState*>(st);
     if (!s) return;
-    if (s->fft) dd_fft_destroy(s->fft);
-    if (s->cos) dd_cos1k_destroy(s->cos);
     (void)hipFree(s->frag);
     delete s;
-}
-
-// Which M = 1 kernel runs: by tap class, unless a tool or test has forced one.  The choice is a process-wide word set
-// through dd_debug_select_kernel (a debug entry like dd_debug_fill_lds); the environment variable DD_MFMA_KERNEL only
-// seeds it, read ONCE when the first chain is launched (no getenv in the launch path).
-enum { DD_KSEL_UNREAD = -1, DD_KSEL_AUTO = 0, DD_KSEL_AB = 1, DD_KSEL_FFT1K = 2, DD_KSEL_COS1K = 3, DD_KSEL_DECIMP = 4 };
-static std::atomic<int> g_kernel_sel{DD_KSEL_UNREAD};
-static int kernel_sel_parse(const char* name) {
-    if (!name || !*name || strcmp(name, "auto") == 0) return DD_KSEL_AUTO;
-    if (strcmp(name, "ab") == 0) return DD_KSEL_AB;
-    if (strcmp(name, "fft1k") == 0) return DD_KSEL_FFT1K;
-    if (strcmp(name, "cos1k") == 0) return DD_KSEL_COS1K;
-    if (strcmp(name, "decimp") == 0) return DD_KSEL_DECIMP;      // M > 1: the tile kernels of rounds 1-4 instead of k_chain_decim_w (M = 1: as "auto")
-    return -2;
-}
-static int kernel_sel() {
-    int c = g_kernel_sel.load(std::memory_order_relaxed);
-    if (c == DD_KSEL_UNREAD) {
-        c = kernel_sel_parse(getenv("DD_MFMA_KERNEL"));
-        if (c < 0) c = DD_KSEL_AUTO;
-        g_kernel_sel.store(c, std::memory_order_relaxed);
-    }
-    return c;
-}
-int dd_kernel_sel_decimp(void) { return kernel_sel() == DD_KSEL_DECIMP ? 1 : 0; }
-extern "C" int dd_debug_select_kernel(const char* name) {
-    const int c = kernel_sel_parse(name);
-    if (c < 0) {
-        dd_set_error("dd_debug_select_kernel: unknown kernel '%s' (auto, ab, fft1k, cos1k, decimp)", name);
-        return DD_ERR_INVALID;
-    }
-    g_kernel_sel.store(c, std::memory_order_relaxed);
-    return DD_OK;
 }
 
 template <int NKS>
@@ -580,7 +527,6 @@ static int mfma_launch_t(DDMfmaState* st, DDChainParams& P, hipStream_t s, int* 
     t.frag = st->frag;
     t.inv_tapscale = st->inv_tapscale;
     t.stamps = nullptr;
-    const int ksel = kernel_sel();
     // interior tiles: whole span inside the chunk, all outputs emitted, aligned complex64
     int t_first = 1, t_last = 1;
     const bool u8in = (P.flags & DD_CHAIN_U8_INPUT) != 0;
@@ -596,42 +542,6 @@ static int mfma_launch_t(DDMfmaState* st, DDChainParams& P, hipStream_t s, int* 
         if (hi >= lo) { t_first = (int)lo; t_last = (int)hi + 1; }
     }
     const int n_int = t_last - t_first;
-    // dd_debug_select_kernel (tools and tests switch kernels inside one process): "ab" forces the MFMA kernels,
-    // "fft1k" the overlap-save FFT kernel wherever it applies; "auto" = by tap class
-    const bool force_fft1k = ksel == DD_KSEL_FFT1K;
-    const bool force_mfma = ksel == DD_KSEL_AB;
-    // The FFT kernel's time does not depend on the tap count (0.221 ms per 2^26 samples, 0.207 from raw u8); the MFMA
-    // kernel's does: 0.227 ms in the 162..257-tap class, 0.20 below.  FM output only.
-    const bool fft_class = NKS == 18;
-    // 255 taps of the form a0 + a1 cos(2 pi k / 254) (filters.hamming), FM or complex64 output: the running-sum kernel (dd_cosfir.hip),
-    // a third of the overlap-save form's arithmetic.  "cos1k" forces it wherever it applies (it never applies to other taps),
-    // "fft1k" / "ab" keep it off.
-    // (DD_CHAIN_TIGHT: the caller asks for the transform kernel's stop-band error bound)
-    if ((ksel == DD_KSEL_AUTO || ksel == DD_KSEL_COS1K) && st->K == 255 && !(P.flags & DD_CHAIN_TIGHT)) {
-        if (!st->cos && !st->cos_tried) {
-            st->cos_tried = 1;
-            if (!dd_cos1k_supported(st->taps.data(), st->K, 1, P.flags) || dd_cos1k_create(&st->cos, st->taps.data(), st->K) != DD_OK) st->cos = nullptr;
-        }
-        if (st->cos) {
-            int rc = dd_cos1k_launch(st->cos, P, s);
-            if (rc != DD_OK) return rc;
-            if (kernel_id) *kernel_id = DD_KERNEL_COS_RS;
-            return DD_OK;
-        }
-    }
-    // (any input alignment: its block grid follows the alignment of `out`, dd_fftfir.hip DDFft1kTabs::base)
-    if ((force_fft1k || (fft_class && !force_mfma)) && dd_fft1k_supported(st->K, 1, P.flags)) {
-        if (!st->fft && !st->fft_tried) {
-            st->fft_tried = 1;
-            if (dd_fft_create(&st->fft, st->taps.data(), st->K) != DD_OK) st->fft = nullptr;
-        }
-        if (st->fft) {
-            int rc = dd_fft1k_launch(st->fft, P, s);
-            if (rc != DD_OK) return rc;
-            if (kernel_id) *kernel_id = DD_KERNEL_FFT_OS;
-            return DD_OK;
-        }
-    }
     if (n_int > 0) {
         // one 16-wave workgroup per CU (LDS bound): persistent workgroups for the interior run plus
         // one workgroup per edge tile (both sides of the run), all resident at once -- the edge

@@ -19,8 +19,8 @@ extern "C" {
  * suite runs the chain kernels after a NaN fill and after a zero fill and requires bit-identical outputs. */
 int  dd_debug_fill_lds(uint32_t pattern, void* stream);
 /* diagnostic: force one of the M = 1 chain kernels for every later launch of this process -- "ab" (k_chain_mfma_ab), "fft1k" (k_chain_fft1k, wherever it applies), "cos1k" (k_chain_cos1k where it applies -- 255 taps of a
- * two-term cosine series, FM output -- and the choice by tap class elsewhere), "decimp" (M > 1: the tile kernels of rounds 1-4 instead of
- * k_chain_decim_b / k_chain_decim_w), "auto" / NULL (by tap class, the default).  The parity,
+ * two-term cosine series -- and the choice by tap class elsewhere), "decimp" (M > 1: the tile kernels of rounds 1-4 instead of
+ * k_chain_decim_b / k_chain_decim_w; M = 1: by tap class but without k_chain_cos1k), "auto" / NULL (by tap class, the default).  The parity,
  * full-size and determinism suites run both FM kernels this way; the environment variable DD_MFMA_KERNEL seeds the choice
  * once per process.  No reference counterpart. */
 int  dd_debug_select_kernel(const char* name);
@@ -59,6 +59,17 @@ int  dd_debug_decimw_plan(int64_t abs0, int64_t Ld, int K, int M, int off, int n
  *   out[8] = accumulator sets (1 / 2), out[9..10] = smallest and largest cell counted in out[0] (-1: none), out[11] = 1 for the padded
  *   image (M = 0 mod 4).  DD_ERR_UNSUPPORTED unless k_chain_decim_b takes (K, M). */
 int  dd_debug_decimb_lds_check(int K, int M, int phi, int64_t* out);
+/* dd_debug_chain_select -- which kernel family a fused launch through a filter of these taps takes: the dispatcher of dd_chain.hip, asked
+ *   with the selector as an argument (a dd_debug_select_kernel name; the process-wide choice is neither read nor changed).  flags: DD_CHAIN_*;
+ *   in_align_bytes: the input pointer's address modulo 16.  *family = DD_FAMILY_*: the family tried FIRST -- a family whose state cannot be
+ *   created on the device falls through to the next one (cos1k -> fft1k -> MFMA -> dense). */
+#define DD_FAMILY_DENSE 0    /* k_chain_dense (DD_KERNEL_DENSE_F32) */
+#define DD_FAMILY_TILES 1    /* k_chain_decim / _p / _multi (DD_KERNEL_DECIM_TILES / _PERSISTENT / _MULTI) */
+#define DD_FAMILY_ROWS 2     /* k_chain_decim_w / _b (DD_KERNEL_DECIM_WAVE / _BLOCKS) */
+#define DD_FAMILY_COS1K 3    /* k_chain_cos1k (DD_KERNEL_COS_RS) */
+#define DD_FAMILY_FFT1K 4    /* k_chain_fft1k (DD_KERNEL_FFT_OS) */
+#define DD_FAMILY_MFMA 5     /* k_chain_mfma_ab / _edge (DD_KERNEL_MFMA_AB / _TILES) */
+int  dd_debug_chain_select(const double* taps_host, int ntaps, int decim, int flags, int in_align_bytes, const char* selector_name, int* family);
 int  dd_debug_cos_fit(const double* taps_host, int K, double* a_out, int* Q_out);
 int  dd_debug_sync_envelope(const void* X_dev, int64_t L, int nwin, int route, double* env_dev, void* stream);
 

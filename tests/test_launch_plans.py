@@ -1,6 +1,6 @@
 """
-Host arithmetic of two launch paths, checked without a GPU through the library's diagnostic entries (the library loads and these
-two functions run on any machine: they never touch the device).
+Host arithmetic of the launch paths, checked without a GPU through the library's diagnostic entries (the library loads and these
+functions run on any machine: they never touch the device).
 
 * dd_debug_fft1k_plan: where k_chain_fft1k lays its 768-output blocks over a chunk (base: the block grid follows the alignment of
   `out`) and which interior blocks a wave takes in which round (DDFft1kMap).  The kernel evaluates
@@ -224,3 +224,86 @@ def test_a_variant_library_is_loaded_through_dd_lib_path_and_says_so(tmp_path):
     assert r.returncode == 0, r.stderr[-1000:]
     assert r.stdout.strip() == alt
     assert "DD_LIB_PATH set, loading" in r.stderr and alt in r.stderr
+
+
+def _remez127():
+    import scipy.signal as ss
+    return ss.remez(127, [0, 100e3, 150e3, 4999999], [1, 0], fs=1e7)
+
+
+_TAPS = {
+    "hamming255": lambda: _win("hamming", 255),
+    "bh151": lambda: _win("bh", 151),
+    "remez127": _remez127,
+    # a (near) pure cosine: no constant term for k_chain_cos1k to divide by (dd_cos1k_supported declines it)
+    "cosine255": lambda: 1e-5 - np.cos(2 * np.pi * np.arange(255) / 254),
+    "hamming257": lambda: _win("hamming", 257),
+    "hamming258": lambda: _win("hamming", 258),
+    "hamming300": lambda: _win("hamming", 300),
+}
+_NCO, _FM, _U8, _DIRECT, _TIGHT = (_hip.DD_CHAIN_NCO, _hip.DD_CHAIN_FM, _hip.DD_CHAIN_U8_INPUT, _hip.DD_CHAIN_FORCE_DIRECT,
+                                   _hip.DD_CHAIN_TIGHT)
+_DENSE, _TILES, _ROWS, _COS1K, _FFT1K, _MFMA = (_hip.DD_FAMILY_DENSE, _hip.DD_FAMILY_TILES, _hip.DD_FAMILY_ROWS, _hip.DD_FAMILY_COS1K,
+                                                _hip.DD_FAMILY_FFT1K, _hip.DD_FAMILY_MFMA)
+
+
+@pytest.mark.parametrize("taps,M,flags,align,sel,want", [
+    # filters.hamming(255) at M = 1, the headline: the running-sum kernel under "auto" / "cos1k", FM or complex64 output, complex64 or u8
+    # input; every other selector keeps it off, and its tap class (162..257) then takes the transform kernel unless "ab" forces MFMA
+    ("hamming255", 1, _NCO | _FM, 0, "auto", _COS1K), ("hamming255", 1, _NCO | _FM, 0, None, _COS1K), ("hamming255", 1, _NCO | _FM, 0, "cos1k", _COS1K),
+    ("hamming255", 1, _NCO | _FM, 0, "fft1k", _FFT1K), ("hamming255", 1, _NCO | _FM, 0, "ab", _MFMA), ("hamming255", 1, _NCO | _FM, 0, "decimp", _FFT1K),
+    ("hamming255", 1, _NCO, 0, "auto", _COS1K), ("hamming255", 1, 0, 0, "cos1k", _COS1K), ("hamming255", 1, _NCO | _FM | _U8, 0, "auto", _COS1K),
+    ("hamming255", 1, _FM | _U8, 2, "auto", _COS1K), ("hamming255", 1, _NCO | _FM, 8, "auto", _COS1K),
+    # DD_CHAIN_TIGHT: no running-sum kernel, whatever the selector
+    ("hamming255", 1, _NCO | _FM | _TIGHT, 0, "auto", _FFT1K), ("hamming255", 1, _NCO | _FM | _TIGHT, 0, "cos1k", _FFT1K),
+    ("hamming255", 1, _NCO | _FM | _TIGHT, 0, "fft1k", _FFT1K), ("hamming255", 1, _NCO | _FM | _TIGHT, 0, "ab", _MFMA),
+    ("hamming255", 1, _NCO | _FM | _TIGHT, 0, "decimp", _FFT1K), ("hamming255", 1, _NCO | _TIGHT, 0, "auto", _FFT1K), ("hamming255", 1, _FM | _U8 | _TIGHT, 0, "auto", _FFT1K),
+    # 255 taps that are a cosine series, but not one k_chain_cos1k takes
+    ("cosine255", 1, _NCO | _FM, 0, "auto", _FFT1K), ("cosine255", 1, _NCO | _FM, 0, "cos1k", _FFT1K), ("cosine255", 1, _NCO | _FM, 0, "ab", _MFMA),
+    # the tap classes below 162 taps at M = 1: MFMA, the transform kernel only when forced
+    ("bh151", 1, _NCO | _FM, 0, "auto", _MFMA), ("bh151", 1, _NCO | _FM, 0, "cos1k", _MFMA), ("bh151", 1, _NCO | _FM, 0, "fft1k", _FFT1K), ("bh151", 1, _NCO | _FM, 0, "decimp", _MFMA),
+    ("remez127", 1, _NCO | _FM, 0, "auto", _MFMA), ("remez127", 1, _NCO, 0, "ab", _MFMA), ("remez127", 1, _FM | _U8, 0, "fft1k", _FFT1K),
+    # the reference's decimations: the row kernels; "decimp" the tile kernels
+    ("bh151", 34, _NCO | _FM, 0, "auto", _ROWS), ("bh151", 50, _NCO | _FM, 0, "auto", _ROWS), ("remez127", 34, _NCO | _FM, 0, "auto", _ROWS),
+    ("remez127", 50, _NCO, 0, "auto", _ROWS), ("bh151", 34, _NCO | _FM, 0, "decimp", _TILES), ("remez127", 50, _NCO | _FM | _U8, 0, "decimp", _TILES),
+    ("bh151", 34, _NCO | _FM, 0, "fft1k", _ROWS), ("bh151", 34, _NCO | _FM, 0, "ab", _ROWS), ("hamming255", 34, _NCO | _FM, 0, "auto", _ROWS),
+    # the transform kernel stops at 256 taps, the MFMA tap classes at 257, and nothing but the dense kernel lies beyond
+    ("hamming257", 1, _NCO | _FM, 0, "fft1k", _MFMA), ("hamming257", 1, _NCO | _FM, 0, "auto", _MFMA), ("hamming258", 1, _NCO | _FM, 0, "fft1k", _DENSE),
+    ("hamming258", 1, _NCO | _FM, 0, "auto", _DENSE), ("hamming300", 1, _NCO | _FM, 0, "fft1k", _DENSE), ("hamming300", 1, _NCO | _FM, 0, "cos1k", _DENSE),
+    # DD_CHAIN_FORCE_DIRECT: the f32 direct form at M = 1; at M > 1 it names no kernel of its own
+    ("hamming255", 1, _NCO | _FM | _DIRECT, 0, "auto", _DENSE), ("hamming255", 1, _NCO | _FM | _DIRECT, 0, "cos1k", _DENSE), ("bh151", 1, _DIRECT, 0, "ab", _DENSE),
+    ("remez127", 1, _FM | _U8 | _DIRECT, 0, "fft1k", _DENSE), ("bh151", 34, _NCO | _FM | _DIRECT, 0, "auto", _ROWS),
+    # what the row kernels do not take (dd_decimw.h: even M in [8, 64], 2..256 taps): the tile kernels
+    ("bh151", 33, _NCO | _FM, 0, "auto", _TILES), ("bh151", 5, _NCO, 0, "auto", _TILES), ("bh151", 6, _NCO | _FM, 0, "auto", _TILES),
+    ("bh151", 68, _NCO | _FM, 0, "auto", _TILES), ("hamming300", 34, _NCO | _FM, 0, "auto", _TILES), ("hamming257", 34, _NCO | _FM, 0, "auto", _TILES),
+    ("bh151", 8, _NCO | _FM, 0, "auto", _ROWS), ("bh151", 64, _NCO | _FM, 0, "auto", _ROWS), ("bh151", 2, _NCO | _FM, 0, "auto", _TILES),
+    # ... and an input pointer off their alignment: complex64 on 8 bytes, raw u8 on 2
+    ("bh151", 34, _NCO | _FM, 8, "auto", _ROWS), ("bh151", 34, _NCO | _FM, 4, "auto", _TILES), ("bh151", 34, _NCO | _FM, 12, "auto", _TILES),
+    ("bh151", 34, _NCO | _FM | _U8, 2, "auto", _ROWS), ("bh151", 34, _NCO | _FM | _U8, 14, "auto", _ROWS), ("bh151", 34, _NCO | _FM | _U8, 1, "auto", _TILES),
+    ("remez127", 50, _FM | _U8, 7, "auto", _TILES),
+])
+def test_chain_select_dispatch_table(taps, M, flags, align, sel, want):
+    """dd_debug_chain_select: the dispatcher of dd_chain.hip (chain_select), a pure function -- the kernel family by taps, decimation, flags,
+    input alignment and selector.  Expected values: the DD_KERNEL_* descriptions of directdemod_hip.h, dd_decimw.h / dd_fftfir.h / dd_cosfir.h,
+    and what the GPU suites assert about the kernel ids they see."""
+    t = np.ascontiguousarray(_TAPS[taps](), dtype=np.float64)
+    fam = C.c_int(-1)
+    rc = _hip.lib().dd_debug_chain_select(t.ctypes.data_as(C.POINTER(C.c_double)), len(t), M, flags, align, None if sel is None else sel.encode(),
+                                          C.byref(fam))
+    _hip.check(rc, "dd_debug_chain_select")
+    assert fam.value == want
+
+
+def test_chain_select_takes_its_selector_as_an_argument_and_refuses_bad_ones():
+    lib = _hip.lib()
+    t = np.ascontiguousarray(_win("hamming", 255))
+    tp = t.ctypes.data_as(C.POINTER(C.c_double))
+    fam = C.c_int(-1)
+    assert lib.dd_debug_chain_select(tp, 255, 1, _FM, 0, b"nonesuch", C.byref(fam)) == _hip.DD_ERR_INVALID
+    assert lib.dd_debug_chain_select(tp, 255, 0, _FM, 0, b"auto", C.byref(fam)) == _hip.DD_ERR_INVALID
+    assert lib.dd_debug_chain_select(tp, 0, 1, _FM, 0, b"auto", C.byref(fam)) == _hip.DD_ERR_INVALID
+    assert lib.dd_debug_chain_select(None, 255, 1, _FM, 0, b"auto", C.byref(fam)) == _hip.DD_ERR_INVALID
+    # the process-wide selector is left alone: asking with "ab" does not change what "auto" answers afterwards, nor the other way round
+    seq = [(b"ab", _MFMA), (b"auto", _COS1K), (b"fft1k", _FFT1K), (b"auto", _COS1K), (b"ab", _MFMA)]
+    for sel, want in seq:
+        assert lib.dd_debug_chain_select(tp, 255, 1, _NCO | _FM, 0, sel, C.byref(fam)) == 0 and fam.value == want
