@@ -100,6 +100,9 @@ SIGNATURES = {
     "dd_u8iq_to_c64": (_int, [_p, _p, _i64, _p]),
     "dd_nco_c64": (_int, [_p, _p, _i64, _u64, _i64, _p]),
     "dd_nco_c64_freqs": (_int, [_p, _p, _i64, _p, C.c_double, _i64, _p]),
+    "dd_nco_c64_ramp": (_int, [_p, _p, _i64, C.c_double, C.c_double, C.c_double, C.c_double, _i64, _p]),
+    "dd_waterfall_u8": (_int, [_p, _i64, _int, C.c_double, _p, _i64, _pi64, _p]),
+    "dd_band_argmax_f32": (_int, [_p, _i64, _int, _int, _int, _p, _p]),
     "dd_fir_create": (_int, [_pp, C.POINTER(C.c_double), _int]),
     "dd_fir_destroy": (_int, [_p]),
     "dd_fir_reset": (_int, [_p, _int, _p, _p]),

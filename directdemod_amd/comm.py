@@ -21,6 +21,7 @@ import numpy as np
 
 from . import _hip, constants
 from ._hip import DevArray
+from .frequency_shift import ramp as _ramp
 
 _C64 = np.dtype(np.complex64)
 _F32 = np.dtype(np.float32)
@@ -305,6 +306,19 @@ class commSignal:
         if self.__chunker is not None:
             offset = self.__chunker.get(constants.CHUNK_FREQOFFSET, 0)
             self.__chunker.set(constants.CHUNK_FREQOFFSET, offset + self.length)
+        if isinstance(freqOffset, _ramp):
+            # a frequency ramp formed in the kernel (frequency_shift.dopplerRamp, decode_funcube.py:215-226): run now, like the array form
+            if freqOffset.n != self.length:
+                raise ValueError("operands could not be broadcast together with shapes (%d,) (%d,)" % (self.length, freqOffset.n))
+            self._settle()
+            self._materialise()
+            d = self._device(_C64)
+            out = DevArray(d.n, _C64)
+            _hip.check(_hip.lib().dd_nco_c64_ramp(d.ptr, out.ptr, d.n, float(freqOffset.start), float(freqOffset.delta),
+                                                  float(freqOffset.target), float(self.sampRate), int(offset), None),
+                       "dd_nco_c64_ramp")
+            self._store(out, copy=False)
+            return self
         if np.ndim(freqOffset) != 0:
             # per-sample frequency (Doppler correction, decode_funcube.py:228): its own kernel, run now
             f = np.ascontiguousarray(freqOffset, dtype=np.float64).ravel()

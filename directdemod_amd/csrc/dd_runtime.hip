@@ -399,18 +399,21 @@ extern "C" int dd_nco_c64(const float* in_c64, float* out_c64, int64_t n, uint64
 // array freqOffset: the Doppler correction of decode_funcube.py:228).  phase = f[n] (n0+n) / fs is
 // formed and reduced in float64, like the reference's np.exp argument; 1e-9-grade phase, the product
 // is rounded once to complex64.
+__device__ __forceinline__ float2 dd_nco_rotate_f64(float2 x, double f, int64_t idx, double fs) {
+    const double cyc = f * (double)idx / fs;
+    const double fr = cyc - floor(cyc);
+    double sn, cs;
+    sincospi(2.0 * fr, &sn, &cs);
+    const double re = (double)x.x * cs + (double)x.y * sn;      // x * (cos - j sin)
+    const double im = (double)x.y * cs - (double)x.x * sn;
+    return make_float2((float)re, (float)im);
+}
+
 __global__ void __launch_bounds__(256) k_nco_c64_freqs(const float2* __restrict__ in, float2* __restrict__ out, int64_t n,
                                                        const double* __restrict__ f, double fs, int64_t start) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const double cyc = f[i] * (double)(start + i) / fs;
-        const double fr = cyc - floor(cyc);
-        double sn, cs;
-        sincospi(2.0 * fr, &sn, &cs);
-        const float2 x = in[i];
-        const double re = (double)x.x * cs + (double)x.y * sn;      // x * (cos - j sin)
-        const double im = (double)x.y * cs - (double)x.x * sn;
-        out[i] = make_float2((float)re, (float)im);
+        out[i] = dd_nco_rotate_f64(in[i], f[i], start + i, fs);
     }
 }
 
@@ -424,6 +427,33 @@ extern "C" int dd_nco_c64_freqs(const float* in_c64, float* out_c64, int64_t n, 
     DD_LAUNCH_CHECK();
     return DD_OK;
 }
+
+// The same with the frequency formed here (decode_funcube.py:215-226): f[i] = start + i * delta as NumPy's arange fills it -- a
+// product and a sum, each rounded (no fma) -- then clipped to the target, from above when rising and from below when falling.
+// The rotation is dd_nco_rotate_f64, the array kernel's: equal frequencies give equal bits.
+__global__ void __launch_bounds__(256) k_nco_c64_ramp(const float2* __restrict__ in, float2* __restrict__ out, int64_t n,
+                                                      double f0, double delta, double target, double fs, int64_t start) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    const bool rising = target > f0;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        double f = __dadd_rn(f0, __dmul_rn((double)i, delta));
+        if (rising ? f > target : f < target) f = target;
+        out[i] = dd_nco_rotate_f64(in[i], f, start + i, fs);
+    }
+}
+
+extern "C" int dd_nco_c64_ramp(const float* in_c64, float* out_c64, int64_t n, double start_hz, double delta_hz, double target_hz,
+                               double samp_rate, int64_t start_index, void* stream) {
+    DD_REQUIRE(n >= 0 && samp_rate > 0, "n / samp_rate");
+    if (n == 0) return DD_OK;
+    DD_REQUIRE(in_c64 && out_c64, "null buffer");
+    hipLaunchKernelGGL(k_nco_c64_ramp, dim3(dd_grid_for(n, 256)), dim3(256), 0, dd_stream(stream),
+                       (const float2*)in_c64, (float2*)out_c64, n, start_hz, delta_hz, target_hz, samp_rate, start_index);
+    DD_LAUNCH_CHECK();
+    return DD_OK;
+}
+
+#include "dd_doppler.h"             // D1: frequency_shift.make_fft and the band argmax
 
 // ---------------------------------------------------------------- R1: decimation gather
 template <typename T>

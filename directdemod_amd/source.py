@@ -41,6 +41,12 @@ class _u8source:
         ''':obj:`int`: get source length'''
         return self.__length
 
+    @property
+    def memmap(self):
+        ''':obj:`numpy array`: the whole recording as the flat interleaved uint8 I,Q view that frequency_shift reads
+        (decode_funcube.py:205); limitData does not move it'''
+        return self._data.reshape(-1)
+
     def _range(self, fromIndex, toIndex):
         if toIndex is None:
             toIndex = fromIndex + 1

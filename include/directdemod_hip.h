@@ -112,6 +112,28 @@ int dd_nco_c64(const float* in_c64, float* out_c64, int64_t n, uint64_t cycles_q
  * freqOffset (Doppler correction, decode_funcube.py:228); phase formed and reduced in float64 */
 int dd_nco_c64_freqs(const float* in_c64, float* out_c64, int64_t n, const double* freqs_hz, double samp_rate,
                      int64_t start_index, void* stream);
+/* the same with the frequency formed in the kernel: f[i] = start_hz + i * delta_hz (one multiplication, one addition, each
+ * rounded to float64), clipped to target_hz from above when target_hz > start_hz and from below otherwise -- the ramp of
+ * decode_funcube.py:215-226 (np.arange(cur, cur + n d + 10 d, d)[:n], then the clip).  `delta_hz` is NumPy's fill step
+ * (start + d) - start, formed on the host; phase arithmetic exactly dd_nco_c64_freqs'.  In place allowed. */
+int dd_nco_c64_ramp(const float* in_c64, float* out_c64, int64_t n, double start_hz, double delta_hz, double target_hz,
+                    double samp_rate, int64_t start_index, void* stream);
+
+/* ---- D1: sandbox/frequency_shift.py (the --freqshift part of decode_funcube.py:202-228) ---- */
+/* make_fft (frequency_shift.py:5-44) over raw interleaved uint8 I,Q on the device.  Slices of `window` samples (a power of
+ * two, 16..8192) start at raw offsets 0, 2 window, ... including a final partial one; every slice counts towards `every`, only
+ * full ones add |FFT((I-127) + j(Q-127))| (magnitudes, not powers) to the row's sum; a row closes at the first count >= every
+ * (ceil(every) slices), slices after the last closed row are dropped.  out_rows[r * window + c] =
+ * log(fftshift(sum)[c] / window / every), float32, `max_rows` rows of room; *n_rows is the row count (out_rows may be null to
+ * ask for it alone).  A row's windows are summed in a fixed order (a fixed split into segments, then the segments in order):
+ * no atomics, equal runs give equal bits.  raw_bytes even, at least one full window; every <= 1 with a partial tail is
+ * DD_ERR_INVALID (the reference dies in fftshift of a scalar). */
+int dd_waterfall_u8(const uint8_t* raw_iq, int64_t raw_bytes, int window, double every, float* out_rows, int64_t max_rows,
+                    int64_t* n_rows, void* stream);
+/* per row of a [rows x width] float32 array the index, relative to band_start, of the first maximum over columns
+ * [band_start, band_stop): np.argmax of frequency_shift.py:95 (the row minimum subtracted at :94 does not move it) */
+int dd_band_argmax_f32(const float* rows_f32, int64_t rows, int width, int band_start, int band_stop, int32_t* out_idx,
+                       void* stream);
 
 /* ---- F1/F3: filters.filter.applyOn, FIR (a=[1]) (filters.py:21-75) ------------ */
 typedef struct dd_fir dd_fir;
