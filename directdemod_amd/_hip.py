@@ -165,6 +165,12 @@ SIGNATURES = {
     "dd_meteor_lim": (_int, [_p, _i64, _i64, _p, _i64, _p, _p, _i64, _p]),
     "dd_meteor_minsync": (_int, [_p, _i64, _p, _p, _i64, _p, _p, _p]),
     "dd_meteor_maxcorr": (_int, [_p, _i64, _p, _i64, _p, _p, _p]),
+    "dd_funcube_mix_ramp": (_int, [_p, _p, _i64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _p, _p]),
+    "dd_funcube_lowpass": (_int, [_p, _p, _i64, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, _p, _p]),
+    "dd_funcube_walk": (_int, [_p, _i64, _i64, _p, C.POINTER(C.c_double), _i64, _p, _p, _p, _p, _p, _p, _p]),
+    "dd_funcube_lim": (_int, [_p, _i64, _i64, _p, _i64, _p, _p, _i64, _p]),
+    "dd_funcube_minsync": (_int, [_p, _i64, _p, _p, _i64, _p, _p, _p]),
+    "dd_funcube_maxcorr": (_int, [_p, _i64, _p, _i64, _p, C.c_int, _p, _i64, _p, _p]),
     "dd_median_segments_f64": (_int, [_p, _pi64, _pi64, _int, _p, _p]),
     "dd_apt_lines_f64": (_int, [_p, _i64, _pi64, _pi64, _int, _pi64, C.c_uint64, _int, _p, _p, _p, _p]),
     "dd_apt_map_u8": (_int, [_p, _i64, _int, C.POINTER(C.c_double), _p, _p]),

@@ -82,6 +82,9 @@ extern "C" int dd_afsk_edges_f64(const double* binary_filter, int64_t n, int spb
 // Meteor-M2 QPSK sync detection (decode_meteorm2.py:229-324)
 #include "dd_meteor.h"
 
+// Funcube BPSK sync detection (decode_funcube.py:148-306)
+#include "dd_funcube.h"
+
 // dd_code_warmup (dd_runtime.hip): the runtime loads a translation unit's code object when one of its kernels is first named
 int dd_code_touch_afsk(void) {
     hipFuncAttributes a;

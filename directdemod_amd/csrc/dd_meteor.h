@@ -46,15 +46,19 @@ struct DDMeteorBuf {                  // a correlation buffer: samples [lo0, lo0
 
 // agc.adjust (decode_meteorm2.py:21-34).  dc * 1048575 and inp * 180.0 are complex products with a zero imaginary part, which
 // NumPy rounds like the component products; the complex quotients by a real are NumPy's Smith division, (a + b * 0) * (1 / c).
-__device__ __forceinline__ double2 dd_met_agc(double2 x, DDMeteorState& s) {
+// (decode_funcube.py:22-35 is the same but for the gain's cap: CAP = 200 here, 20 there)
+template <int CAP>
+__device__ __forceinline__ double2 dd_met_agc_cap(double2 x, DDMeteorState& s) {
     s.dc_re = (s.dc_re * 1048575.0 + x.x) * (1.0 / 1048576.0);
     s.dc_im = (s.dc_im * 1048575.0 + x.y) * (1.0 / 1048576.0);
     const double ir = x.x - s.dc_re, ii = x.y - s.dc_im;
     s.amean = (s.amean * 65535.0 + sqrt(ir * ir + ii * ii)) / 65536.0;
-    if (180.0 / s.amean > 200.0) return make_double2(ir * 200.0, ii * 200.0);
+    if (180.0 / s.amean > (double)CAP) return make_double2(ir * (double)CAP, ii * (double)CAP);
     const double scl = 1.0 / s.amean;
     return make_double2((ir * 180.0) * scl, (ii * 180.0) * scl);
 }
+
+__device__ __forceinline__ double2 dd_met_agc(double2 x, DDMeteorState& s) { return dd_met_agc_cap<200>(x, s); }
 
 __device__ __forceinline__ double dd_met_hyp(double x, const double* __restrict__ tbl) {
     if (x > 127.0) return 1.0;
@@ -63,14 +67,9 @@ __device__ __forceinline__ double dd_met_hyp(double x, const double* __restrict_
     return tbl[i];
 }
 
-// one call of costas.loop (decode_meteorm2.py:58-83): returns correctedIn, leaves the phasor it used in o
-__device__ __forceinline__ double2 dd_met_costas(double2 a, DDMeteorState& s, const DDMeteorParams& p, const double* __restrict__ tbl,
-                                                 double2& o) {
-    double sn, cs;
-    sincos(s.phase, &sn, &cs);                                          // np.exp(-1j * phase) = (cos, -sin)
-    o = make_double2(cs, -sn);
-    const double cr = a.x * o.x - a.y * o.y, ci = a.x * o.y + a.y * o.x;
-    double err = (ci * dd_met_hyp(cr, tbl) - cr * dd_met_hyp(ci, tbl)) / 255.0;
+// costas.loop from the error on (decode_meteorm2.py:66-80, decode_funcube.py:66-80): the error's running mean, the clamp, phase and
+// frequency, and the lock that halves the loop bandwidth
+__device__ __forceinline__ void dd_met_loop_update(double err, DDMeteorState& s, const DDMeteorParams& p) {
     s.pmean = (s.pmean * 39999.0 + fabs(err)) / 40000.0;
     if (err > 1.0) err = 1.0;
     else if (err < -1.0) err = -1.0;
@@ -85,6 +84,16 @@ __device__ __forceinline__ double2 dd_met_costas(double2 a, DDMeteorState& s, co
         s.beta = p.beta_u;
         s.lock = 0;
     }
+}
+
+// one call of costas.loop (decode_meteorm2.py:58-83): returns correctedIn, leaves the phasor it used in o
+__device__ __forceinline__ double2 dd_met_costas(double2 a, DDMeteorState& s, const DDMeteorParams& p, const double* __restrict__ tbl,
+                                                 double2& o) {
+    double sn, cs;
+    sincos(s.phase, &sn, &cs);                                          // np.exp(-1j * phase) = (cos, -sin)
+    o = make_double2(cs, -sn);
+    const double cr = a.x * o.x - a.y * o.y, ci = a.x * o.y + a.y * o.x;
+    dd_met_loop_update((ci * dd_met_hyp(cr, tbl) - cr * dd_met_hyp(ci, tbl)) / 255.0, s, p);
     return make_double2(cr, ci);
 }
 
@@ -340,6 +349,22 @@ __global__ void __launch_bounds__(256) k_meteor_maxcorr(const char2* __restrict_
     }
 }
 
+// x * exp(1j * th) in float64, rounded to complex64
+__device__ __forceinline__ float2 dd_met_rotate(float2 x, double th) {
+    const double c = cos(th), s = sin(th);
+    const double xr = x.x, xi = x.y;
+    return make_float2((float)(xr * c - xi * s), (float)(xr * s + xi * c));
+}
+
+// raw u8 pairs (x = u8 - 127.5, exact in float32) or complex64
+__device__ __forceinline__ float2 dd_met_sample(const uchar2* __restrict__ raw, const float2* __restrict__ c64, int64_t k) {
+    if (raw != nullptr) {
+        const uchar2 r = raw[k];
+        return make_float2((float)r.x - 127.5f, (float)r.y - 127.5f);
+    }
+    return c64[k];
+}
+
 // commSignal.offsetFreq as the reference computes it (comm.py:77 there): x (complex64) *= np.exp(-1.0j*2.0*np.pi*f*np.arange(n)/fs),
 // i.e. theta = (w * k) * (1 / fs) with w = -2 pi f (NumPy's complex products with zero parts and Smith's division by the real fs),
 // the product in float64, rounded to complex64.  Input: raw u8 pairs (x = u8 - 127.5, exact in float32) or complex64.
@@ -347,17 +372,8 @@ __global__ void __launch_bounds__(256) k_meteor_mix(const uchar2* __restrict__ r
                                                      double inv_fs, float2* __restrict__ out) {
     const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (k >= n) return;
-    float2 x;
-    if (raw != nullptr) {
-        const uchar2 r = raw[k];
-        x = make_float2((float)r.x - 127.5f, (float)r.y - 127.5f);
-    } else {
-        x = c64[k];
-    }
-    const double th = (w * (double)k) * inv_fs;
-    const double c = cos(th), s = sin(th);
-    const double xr = x.x, xi = x.y;
-    out[k] = make_float2((float)(xr * c - xi * s), (float)(xr * s + xi * c));
+    const float2 x = dd_met_sample(raw, c64, k);
+    out[k] = dd_met_rotate(x, (w * (double)k) * inv_fs);
 }
 
 extern "C" int dd_meteor_mix(const void* raw_u8, const void* c64, int64_t n, double w, double inv_fs, void* out, void* stream) {

@@ -430,6 +430,36 @@ int dd_meteor_minsync(const void* sym, int64_t nsym, const uint8_t* sync_bits_ho
 int dd_meteor_maxcorr(const void* lim, int64_t lim_len, const int64_t* bufs_host, int64_t nbuf, const int8_t* templates_host,
                       int64_t* out, void* stream);
 
+/* ---- Funcube BPSK sync detection (decode_funcube.py:148-306) ------------------------------------------------------------
+ * dd_funcube_mix_ramp -- dd_meteor_mix with the frequency formed per sample: th = ((w * f[k]) * k) * inv_fs, w = -2 pi,
+ *     f[k] = f0 + k * delta (np.arange's fill) clipped to target from above when target > f0, from below otherwise.
+ * dd_funcube_lowpass -- scipy.signal.lfilter(b, a, x, zi) of complex64 x into complex128 out, sample by sample in lfilter's own
+ *     operation order (bit for bit its output); ncoef = 7 with a[0] = 1 (butter's sixth order); state = device double[2][6],
+ *     the real and the imaginary parts' delays, read on entry and left for the next chunk.
+ * dd_funcube_walk -- dd_meteor_walk with decode_funcube's agc (gain cap 20) and costas (error imag * hyp(real) / 255); the same
+ *     state, parameters and per-symbol outputs.  ph[k] is the phasor symbol k was corrected with, which is pllObj.output after it.
+ * dd_funcube_lim -- out[base + j] = lim(real(x[j] * o) / 2) as int8, o the phasor of the last symbol with aidx < base + j
+ *     (1 before the first).
+ * dd_funcube_minsync -- bits[k] = limBin(real(sym[k])); for every k >= 329 whose 330-symbol window has |mismatches - 165| > 120
+ *     against the 33 sync bits (sync_bits_host), each ten symbols long: cand[2c], cand[2c+1] = (k, mismatches), *count = the
+ *     number of such k (entries past cap are dropped).
+ * dd_funcube_maxcorr -- per buffer i (bufs_host[5i ..] = lo0, n0, lo1, n1, scratch offset: samples [lo0, lo0+n0) then
+ *     [lo1, lo1+n1) of lim[lim_len]): out[2i] = argmax |np.correlate(buffer, np.repeat(t, rep), 'same')| (first maximum),
+ *     out[2i+1] = that maximum, t = 127 / -128 per sync bit.  Each buffer's n0 + n1 + 1 int32 prefix sums go to
+ *     scratch[offset ..]; the ranges must not overlap. */
+int dd_funcube_mix_ramp(const void* raw_u8, const void* c64, int64_t n, double w, double f0, double delta, double target,
+                        double inv_fs, void* out, void* stream);
+int dd_funcube_lowpass(const void* in_c64, void* out_c128, int64_t n, const double* b_host, const double* a_host, int ncoef,
+                       double* state, void* stream);
+int dd_funcube_walk(const void* x, int64_t n, int64_t base, void* state, const double* params_host, int64_t cap,
+                    int64_t* bidx, int64_t* aidx, void* agc, void* ph, void* sym, void* pf, void* stream);
+int dd_funcube_lim(const void* x, int64_t n, int64_t base, const int64_t* aidx, int64_t nsym, const void* ph, int8_t* out,
+                   int64_t out_len, void* stream);
+int dd_funcube_minsync(const void* sym, int64_t nsym, const uint8_t* sync_bits_host, uint8_t* bits, int64_t cap,
+                       int64_t* cand, unsigned long long* count, void* stream);
+int dd_funcube_maxcorr(const int8_t* lim, int64_t lim_len, const int64_t* bufs_host, int64_t nbuf, const uint8_t* sync_bits_host,
+                       int rep, int32_t* scratch, int64_t scratch_len, int64_t* out, void* stream);
+
 /* APT image extraction (decode_noaa.getImage / getColor).
  * dd_median_segments_f64 -- out[i] = np.median(src[off_host[i] : off_host[i] + len_host[i]]) for `count` segments (device out):
  *      numpy's semantics (odd: middle element, even: (a + b) / 2, empty or holding a NaN: NaN); segments of any length.

@@ -564,8 +564,179 @@ def gen_meteor():
         _meteor_store(name, raw, off, _meteor_run(raw, off), 2048 if big else 64, 1024 if big else 4096)
 
 
+def _funcube_run(raw, offset, corrfreq, center, channel):
+    """The reference's decode_funcube.getSyncs on an in-memory recording, tapped like _meteor_run: the sample index of every
+    agc.adjust call (B or A: an A call is the one costas.loop follows), the AGC'd values, costas phase / freq after each loop, the
+    samples of each np.correlate's buffer and its argmax, each chunk's mixer frequencies, and the log records."""
+    import logging
+    import types
+    import scipy.fft as _sfft
+    if not callable(scipy.fft):
+        scipy.fft = _sfft.fft                # `from scipy import fft` (sandbox/frequency_shift.py:2) meant the function
+    from directdemod import comm
+    from directdemod import decode_funcube as dfc
+    cur = {"base": 0, "j": -1}
+    agc_rec, loop_rec, lim_rec, corr_rec, mix_rec, logs = [], [], [], [], [], []
+
+    class TapSig(comm.commSignal):
+        tapped = False
+
+        def offsetFreq(self, f):
+            if np.ndim(f) != 0:
+                mix_rec.append((float(f[0]), float(f[1] - f[0]), float(f[-1]), len(f)))
+            return comm.commSignal.offsetFreq(self, f)
+
+        def filter(self, f):
+            r = comm.commSignal.filter(self, f)
+            self.tapped = True
+            return r
+
+        @property
+        def signal(self):
+            arr = comm.commSignal.signal.fget(self)
+            if not self.tapped:
+                return arr
+            return self._walk(arr)
+
+        def _walk(self, arr):
+            base = cur["base"]
+            for j, v in enumerate(arr):
+                cur["j"] = base + j
+                yield v
+            cur["base"] = base + len(arr)
+
+    class TapAgc(dfc.agc):
+        def adjust(self, inp):
+            out = super().adjust(inp)
+            agc_rec.append((cur["j"], out))
+            return out
+
+    class TapCostas(dfc.costas):
+        def loop(self, samp):
+            out = super().loop(samp)
+            loop_rec.append((len(agc_rec) - 1, self.phase, self.freq))
+            return out
+
+    _lim = dfc.lim
+
+    def lim_tap(x):
+        lim_rec.append(cur["j"])
+        return _lim(x)
+    _corr = dfc.np.correlate
+
+    class NpTap(types.ModuleType):
+        def __getattr__(self, k):
+            return getattr(np, k)
+
+    def corr_tap(a, v, mode="valid"):
+        r = _corr(a, v, mode)
+        smp = np.array(lim_rec[-len(a):], dtype=np.int64)       # the buffer holds the last len(a) lim values (pops leave from the front)
+        cuts = [0] + [int(c) + 1 for c in np.nonzero(np.diff(smp) != 1)[0]] + [len(smp)]
+        corr_rec.append((len(a), int(np.argmax(np.abs(r))), [(int(smp[cuts[i]]), cuts[i + 1] - cuts[i]) for i in range(len(cuts) - 1)]))
+        del lim_rec[:]
+        return r
+    nptap = NpTap("np")
+    nptap.correlate = corr_tap
+
+    class H(logging.Handler):
+        def emit(self, rec):
+            logs.append((rec.msg, rec.args))
+    h = H()
+    root = logging.getLogger()
+    old_level = root.level
+    root.addHandler(h)
+    root.setLevel(logging.INFO)
+    saved = (dfc.comm, dfc.agc, dfc.costas, dfc.lim, dfc.np)
+    dfc.comm = types.SimpleNamespace(commSignal=TapSig)
+    dfc.agc, dfc.costas, dfc.lim, dfc.np = TapAgc, TapCostas, lim_tap, nptap
+    try:
+        src = ArraySource(raw, 2048000)
+        src.memmap = np.ascontiguousarray(raw).reshape(-1).astype(np.int16)     # `-127 + uint8` was promoted by the NumPy of its day
+        obj = dfc.decode_funcube(src, offset, None, center, channel, corrfreq)
+        t0 = time.process_time()
+        err = None
+        try:
+            with np.errstate(divide="ignore"):
+                syncs = obj.getSyncs
+        except ValueError as e:               # one MAXSYNC: np.min of an empty diff
+            syncs, err = None, str(e)
+        cpu = time.process_time() - t0
+    finally:
+        dfc.comm, dfc.agc, dfc.costas, dfc.lim, dfc.np = saved
+        root.removeHandler(h)
+        root.setLevel(old_level)
+    return dict(syncs=syncs, useful=obj.useful, err=err, cpu=cpu, agc=agc_rec, loop=loop_rec, corr=corr_rec, mix=mix_rec, logs=logs)
+
+
+def _funcube_store(name, raw, offset, corrfreq, cap, trace_stride, trace_head):
+    import _funcube
+    agc, loop = cap["agc"], cap["loop"]
+    a_call = np.array([r[0] for r in loop], dtype=np.int64)              # agc call index of each symbol's A
+    is_a = np.zeros(len(agc), dtype=bool)
+    is_a[a_call] = True
+    j = np.array([r[0] for r in agc], dtype=np.int64)
+    last_b = np.where(~is_a, np.arange(len(agc)), -1)
+    last_b = np.maximum.accumulate(last_b) if len(agc) else last_b
+    b_call = np.array([last_b[c - 1] if c > 0 else -1 for c in a_call], dtype=np.int64)
+    b_idx = np.where(b_call >= 0, j[np.maximum(b_call, 0)], -1)
+    a_idx = j[a_call] if len(a_call) else np.zeros(0, dtype=np.int64)
+    nsym = len(a_call)
+    sel = np.unique(np.concatenate((np.arange(min(nsym, trace_head)), np.arange(0, nsym, trace_stride)))).astype(np.int64)
+    agc_a = np.array([agc[c][1] for c in a_call[sel]], dtype=np.complex128)
+    phase = np.array([loop[k][1] for k in sel], dtype=np.float64)
+    freq = np.array([loop[k][2] for k in sel], dtype=np.float64)
+    mins = [int(a[0]) for m, a in cap["logs"] if m.startswith("MINSYNC")]
+    maxs = [int(a[0]) for m, a in cap["logs"] if m.startswith("MAXSYNC")]
+    shifts = [float(a[0]) for m, a in cap["logs"] if m.startswith("doppler shift")]
+    assert len(maxs) == len(cap["corr"]) and len(shifts) == len(cap["mix"])
+    ivs = [c[2] for c in cap["corr"]]
+    args = [c[1] for c in cap["corr"]]
+    starts = [ms - am for ms, am in zip(maxs, args)]
+    assert all(sum(c for _, c in iv) == L for iv, (L, _, _) in zip(ivs, cap["corr"]))
+    iv_flat = np.array([[i, a, b] for i, iv in enumerate(ivs) for a, b in iv], dtype=np.int64).reshape(-1, 3)
+    one = cap["syncs"] is None
+    g = dict(sha256=np.array(_funcube.sha256(raw)), offset=np.int64(offset), corrfreq=np.int64(corrfreq), n=np.int64(raw.shape[0]),
+             syncs=np.array([] if one else cap["syncs"], dtype=np.int64), one_maxsync=np.int64(one), useful=np.int64(cap["useful"]),
+             minsync=np.array(mins, dtype=np.int64), maxsync=np.array(maxs, dtype=np.int64),
+             buf_intervals=iv_flat, buf_start=np.array(starts, dtype=np.int64), argmax=np.array(args, dtype=np.int64),
+             nsym=np.int64(nsym), a_first=np.int64(a_idx[0] if nsym else -1), a_diff=_small_int(np.diff(a_idx)),
+             ab_gap=_small_int(a_idx - b_idx),
+             trace_sel=sel, trace_agc=agc_a, trace_phase=phase, trace_freq=freq, trace_stride=np.int64(trace_stride),
+             chunk_offset=np.array(shifts, dtype=np.float64),
+             dopp_start=np.array([m[0] for m in cap["mix"]], dtype=np.float64),
+             dopp_delta=np.array([m[1] for m in cap["mix"]], dtype=np.float64),
+             dopp_current=np.array([m[2] for m in cap["mix"]], dtype=np.float64),
+             dopp_target=np.array([offset + s for s in shifts], dtype=np.float64),
+             ref_cpu_s=np.float64(cap["cpu"]))
+    if not one and cap["syncs"] is not None:
+        assert all(isinstance(s, np.integer) for s in cap["syncs"])
+    path = os.path.join(OUT, "funcube_%s.npz" % name)
+    np.savez_compressed(path, **g)
+    print("funcube %s: n %d, %d symbols, MINSYNC %s, MAXSYNC %s (buffers %s), syncs %s%s, useful %d, chunk offsets %s, cpu %.1f s, "
+          "%d bytes" % (name, raw.shape[0], nsym, mins, maxs, [c[0] for c in cap["corr"]], g["syncs"].tolist(),
+                        " (the reference raised: %s)" % cap["err"] if one else "", cap["useful"], shifts, cap["cpu"],
+                        os.path.getsize(path)))
+
+
+def gen_funcube():
+    """Funcube sync detection (decode_funcube.py:148-306) on the recordings of tests/_funcube.py.   gen_golden.py --funcube [names]"""
+    install_shim()
+    sys.path.insert(0, REF)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import matplotlib
+    matplotlib.use("Agg")
+    import _funcube
+    names = [a for a in sys.argv[2:] if a in _funcube.CASES] or sorted(_funcube.CASES)
+    for name in names:
+        raw, off, corr = _funcube.case(name)
+        big = raw.shape[0] > 20000000
+        _funcube_store(name, raw, off, corr, _funcube_run(raw, off, corr, _funcube.CENTER, _funcube.CHANNEL),
+                       256 if big else 16, 1024 if big else 2048)
+
 
 def main():
+    if "--funcube" in sys.argv:
+        return gen_funcube()
     if "--meteor" in sys.argv:
         return gen_meteor()
     if "--afsk-frames" in sys.argv:
