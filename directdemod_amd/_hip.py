@@ -35,6 +35,7 @@ DD_CHAIN_NCO, DD_CHAIN_FM, DD_CHAIN_U8_INPUT, DD_CHAIN_FORCE_DIRECT, DD_CHAIN_TI
 (DD_KERNEL_NONE, DD_KERNEL_DENSE_F32, DD_KERNEL_DECIM_TILES, DD_KERNEL_DECIM_PERSISTENT, DD_KERNEL_MFMA_WS,
  DD_KERNEL_MFMA_TILES, DD_KERNEL_MFMA_AB, DD_KERNEL_FFT_OS, DD_KERNEL_DECIM_MULTI, DD_KERNEL_COS_RS, DD_KERNEL_DECIM_WAVE,
  DD_KERNEL_DECIM_BLOCKS) = range(12)
+DD_MEDFILT_MAX, DD_MEDFILT_TILE = 255, 1024      # widest dd_medfilt_* window; outputs per workgroup (tests place lengths around it)
 DD_FAMILY_DENSE, DD_FAMILY_TILES, DD_FAMILY_ROWS, DD_FAMILY_COS1K, DD_FAMILY_FFT1K, DD_FAMILY_MFMA = range(6)   # dd_debug_chain_select
 
 
@@ -121,6 +122,14 @@ SIGNATURES = {
     "dd_fm_destroy": (_int, [_p]),
     "dd_fm_reset": (_int, [_p]),
     "dd_fm_discrim_c64": (_int, [_p, _p, _p, _i64, _int, _pi64, _p]),
+    "dd_fmad_create": (_int, [_pp]),
+    "dd_fmad_destroy": (_int, [_p]),
+    "dd_fmad_reset": (_int, [_p]),
+    "dd_fm_angle_diff_c64": (_int, [_p, _p, _p, _i64, _int, _pi64, _p]),
+    "dd_medfilt_f32": (_int, [_p, _p, _i64, _int, _p]),
+    "dd_medfilt_f64": (_int, [_p, _p, _i64, _int, _p]),
+    "dd_conv_same_f64": (_int, [_p, _p, _i64, _p, _int, _p]),
+    "dd_conv_same_c64": (_int, [_p, _p, _i64, _p, _int, _p]),
     "dd_fused_process": (_int, [_p, _p, _p, _p, _i64, _int, _u64, _i64, _int, _int, _int, _int, _pi64, _p]),
     "dd_chain_create": (_int, [_pp, C.POINTER(C.c_double), _int, _u64, _int, _int]),
     "dd_chain_destroy": (_int, [_p]),

@@ -1,5 +1,6 @@
 """
-FM demodulation -- drop-in for the reference's directdemod/demod_fm.py:12-51.
+FM demodulation -- drop-in for the reference's directdemod/demod_fm.py: demod_fm (:12-51) and, at the end of this file,
+demod_fmAD (:57-96).
 
 ``demod(sig)`` = angle(sig[1:] * conj(sig[:-1])) with a one-sample carry between
 calls (first call returns L-1 values, later calls L; quirk Q3).  On the device the
@@ -116,4 +117,78 @@ class demod_fm():
         a = np.asarray(sig)
         self._note_call(len(a))
         out = self._demod_device(DevArray.from_host(a, dtype=np.complex64))
+        return out.to_host().astype(np.float64)
+
+
+_FMAD_POOL = []
+
+
+class demod_fmAD():
+    '''
+    Object for FM demodulation (alternative method using angle differentiation, demod_fm.py:57-96):
+    ``demod(sig)`` = np.diff(np.unwrap(np.angle(sig))) with the last ANGLE carried between calls (first call returns L-1 values,
+    later calls L).  One kernel (dd_fm_angle_diff_c64): float32 arctangents, each difference brought into [-pi, pi] by np.unwrap's
+    rule, the carried angle kept on the device.  Unlike demod_fm, a sample of exactly zero has angle 0 and yields the neighbours'
+    angles, not 0.  (np.angle of a negative-zero real part with a zero imaginary part is +-pi; here it is 0.)
+    '''
+
+    def __init__(self, storeState=True):
+        '''Args:
+            storeState (:obj:`bool`): Store state? Helps if signal is chunked
+        '''
+        self.__storeState = storeState
+        self.__h = None
+
+    def _handle(self):
+        if self.__h is None:
+            _hip.require_gpu()
+            if _FMAD_POOL:
+                p = _FMAD_POOL.pop()
+                check(lib().dd_fmad_reset(p), "dd_fmad_reset")
+            else:
+                p = C.c_void_p()
+                check(lib().dd_fmad_create(C.byref(p)), "dd_fmad_create")
+            self.__h = p
+        return self.__h
+
+    def __del__(self):
+        try:
+            if self.__h is not None:
+                if len(_FMAD_POOL) < 16:
+                    _FMAD_POOL.append(self.__h)
+                else:
+                    lib().dd_fmad_destroy(self.__h)
+                self.__h = None
+        except Exception:
+            pass
+
+    def _demod_device(self, x):
+        if x.dtype != np.dtype(np.complex64):
+            raise TypeError("demod_fmAD expects complex IQ samples")
+        if x.n < 1 and self.__storeState:
+            raise IndexError("index -1 is out of bounds for axis 0 with size 0")   # demod_fm.py:89/93
+        h = self._handle()
+        if not self.__storeState:
+            check(lib().dd_fmad_reset(h), "dd_fmad_reset")
+        out = DevArray(max(1, x.n), np.float32)
+        no = C.c_int64(0)
+        check(lib().dd_fm_angle_diff_c64(h, x.ptr, out.ptr, x.n, 1 if self.__storeState else 0, C.byref(no), None),
+              "dd_fm_angle_diff_c64")
+        return out.view(0, no.value)
+
+    def demod(self, sig):
+        '''FM demod a given complex IQ array
+
+        Args:
+            sig: numpy array (complex) or device array
+
+        Returns:
+            numpy array float64 for numpy input (like the reference), device float32
+            array for device input
+        '''
+        from .comm import flush_all
+        flush_all()
+        if isinstance(sig, DevArray):
+            return self._demod_device(sig)
+        out = self._demod_device(DevArray.from_host(np.asarray(sig), dtype=np.complex64))
         return out.to_host().astype(np.float64)

@@ -348,3 +348,89 @@ class remez(filter):
         if not len(flat) == 2 * len(gains):
             raise ValueError("Invalid bands/gains values")
         super(remez, self).__init__(signal.remez(ntaps, flat, gains, fs=Fs), [1], storeState, zeroPhase, initOut)
+
+
+class blackmanHarrisConv:
+    '''Blackman Harris filter by convolving (filters.py:145-174): scipy.signal.convolve(sig, blackmanharris(n), mode='same'),
+    which is np.convolve(sig, w)[s : s + len(sig)] with s = (n - 1) // 2 for odd and even n and for signals shorter than the window.
+    Stateless.  One kernel (dd_conv_same_*): the signal is read in place, the zeros beyond both ends are formed in the kernel, the
+    window is uploaded once per object.  Real input gives float64, complex input complex64 (sums in float64, rounded once:
+    declared deviation Q6, like ``filter.applyOn``); host input gives a host array, device input a device array.'''
+
+    def __init__(self, n=151):
+        '''Args:
+            n (:obj:`int`, optional): size of the window
+        '''
+        self.__window = _cosine_sum(n, [0.35875, 0.48829, 0.14128, 0.01168])
+        self.__dwin = None
+
+    def applyOn(self, sig):
+        '''Apply the filter to a given array of signal (numpy array or device array)'''
+        from .comm import _convert, flush_all
+        flush_all()
+        host = not isinstance(sig, DevArray)
+        if host:
+            a = np.asarray(sig)
+            d = DevArray.from_host(a, dtype=_C64 if np.iscomplexobj(a) else _F64)
+        else:
+            d = sig
+            if d.dtype == _hip.IQ8 or d.dtype == np.dtype(np.complex128):
+                d = _convert(d, _C64)
+            elif d.dtype == _F32:
+                d = _convert(d, _F64)
+        if d.dtype not in (_C64, _F64):
+            raise TypeError("unsupported dtype %s" % d.dtype)
+        if self.__dwin is None:
+            self.__dwin = DevArray.from_host(self.__window, dtype=_F64)
+        out = DevArray(max(1, d.n), d.dtype)
+        fn, name = (lib().dd_conv_same_c64, "dd_conv_same_c64") if d.dtype == _C64 else (lib().dd_conv_same_f64, "dd_conv_same_f64")
+        check(fn(d.ptr, out.ptr, d.n, self.__dwin.ptr, len(self.__window), None), name)
+        out = out.view(0, d.n)
+        return out.to_host() if host else out
+
+
+class medianFilter:
+    '''Median filter (filters.py:322-326): scipy.signal.medfilt(sig, n), the sliding median of odd width n with zeros beyond both
+    ends, on the device (dd_medfilt_f32 / _f64).  Exact: every output is one of the inputs or the padding zero.  float32 stays
+    float32 and float64 stays float64; a host integer array is widened to float64 on the way in and cast back to its dtype, as
+    SciPy returns it (integers beyond 2**53 do not survive that).  A signal shorter than n is valid.  Widths above MAX_N raise
+    NotImplementedError.  NaN inputs are outside the contract: SciPy's own answer for them depends on the order its selection
+    visits the window; here a window holding a NaN yields some element of that window.
+    Only 1-D signals are supported (SciPy would filter an N-D array with an N-D window; here that is a TypeError).
+    Host input gives a host array, device input -- float32 or float64 -- a device array.'''
+
+    MAX_N = _hip.DD_MEDFILT_MAX
+    TILE = _hip.DD_MEDFILT_TILE         # outputs per workgroup of the kernel
+
+    def __init__(self, n=5):
+        self.__n = n
+
+    def applyOn(self, sig):
+        host = not isinstance(sig, DevArray)
+        a = np.asarray(sig) if host else None
+        dt = a.dtype if host else sig.dtype
+        if not (dt in (_F32, _F64) or (host and np.issubdtype(dt, np.integer))):
+            raise ValueError("dtype=%s is not supported by medfilt" % dt)
+        if host and a.ndim != 1:
+            raise TypeError("The signal array must be 1-D")
+        n = int(self.__n)
+        if n % 2 != 1:
+            raise ValueError("Each element of kernel_size should be odd.")
+        if n > self.MAX_N:
+            raise NotImplementedError("medianFilter: kernel size %d is above the device kernel's %d" % (n, self.MAX_N))
+        from .comm import flush_all
+        flush_all()
+        if host:
+            d = DevArray.from_host(a, dtype=_F32 if dt == _F32 else _F64)
+        else:
+            d = sig
+        out = DevArray(max(1, d.n), d.dtype)
+        if d.dtype == _F32:
+            check(lib().dd_medfilt_f32(d.ptr, out.ptr, d.n, n, None), "dd_medfilt_f32")
+        else:
+            check(lib().dd_medfilt_f64(d.ptr, out.ptr, d.n, n, None), "dd_medfilt_f64")
+        out = out.view(0, d.n)
+        if not host:
+            return out
+        res = out.to_host()
+        return res if res.dtype == dt else res.astype(dt)

@@ -9,8 +9,9 @@ import functools
 
 import numpy as np
 
-from . import _ops, chunker, comm, constants, demod_am, demod_fm, filters
+from . import _ops, comm, constants, demod_am, demod_fm, filters
 from ._hip import DevArray
+from .decode_fm import fm_audio_chunks
 
 
 def sync_needle(sync_bits, samp_rate, positive=True):
@@ -84,20 +85,7 @@ class noaa_sync:
 
     # ---- FM audio in chunks: one fused kernel per chunk (decode_noaa.py:600-629)
     def audio(self, audioFreq=constants.NOAA_CRUDESYNCSAMPRATE, strictness=False, chunkSize=constants.PROC_CHUNKSIZE):
-        src = self.__sigsrc
-        audioOut = comm.commSignal(audioFreq)
-        bhFilter = filters.blackmanHarris(151)
-        fmDemodulator = demod_fm.demod_fm()
-        chunkerObj = chunker.chunker(src, chunkSize)
-        read = src.read_device if hasattr(src, "read_device") else src.read
-        if hasattr(src, "read_device_raw") and src.read_device_raw(0, 1) is not None:
-            read = src.read_device_raw          # the recording stays in HBM as raw pairs; the fused kernel widens them
-        for a, b in chunkerObj.getChunks:
-            sig = comm.commSignal(src.sampFreq, read(a, b), chunkerObj).offsetFreq(self.__offset) \
-                .filter(bhFilter).bwLim(self.__bw, uniq="First").funcApply(fmDemodulator.demod) \
-                .bwLim(audioFreq, strictness)
-            audioOut.extend(sig)
-        return audioOut
+        return fm_audio_chunks(self.__sigsrc, self.__offset, self.__bw, audioFreq, strictness, chunkSize)
 
     # ---- envelope in 240 000-sample blocks (decode_noaa.py:631-657)
     def envelope(self, sig):

@@ -198,6 +198,34 @@ int dd_fm_reset(dd_fm* h);
 int dd_fm_discrim_c64(dd_fm* h, const float* in_c64, float* out, int64_t n, int carry,
                       int64_t* n_out, void* stream);
 
+/* ---- D2: demod_fmAD.demod (demod_fm.py:57-96) -------------------------------- */
+/* np.diff(np.unwrap(np.angle(x))): per-sample angles (angle(0) = 0), each difference moved by 2 pi when its magnitude is
+ * beyond pi.  The carried quantity is the last ANGLE (demod_fm.py:89,93), kept on the device inside the handle: first call
+ * with carry writes n-1 outputs, later calls n; carry=0 always n-1.  *n_out receives the count written.  A sample of exactly
+ * zero gives angle(next) - 0 and 0 - angle(previous) here, where dd_fm_discrim_c64 gives 0 twice. */
+typedef struct dd_fmad dd_fmad;
+int dd_fmad_create(dd_fmad** h);
+int dd_fmad_destroy(dd_fmad* h);
+int dd_fmad_reset(dd_fmad* h);
+int dd_fm_angle_diff_c64(dd_fmad* h, const float* in_c64, float* out, int64_t n, int carry,
+                         int64_t* n_out, void* stream);
+
+/* ---- F5: filters.medianFilter.applyOn -> scipy.signal.medfilt (filters.py:322-326) --- */
+/* sliding median of odd width ksize over a 1-D real signal, zeros beyond both ends; out[i] is one of the inputs (or the
+ * padding zero), bit for bit.  ksize even: DD_ERR_INVALID; ksize > DD_MEDFILT_MAX: DD_ERR_UNSUPPORTED.  n < ksize is valid.
+ * in != out.  A workgroup writes DD_MEDFILT_TILE outputs. */
+#define DD_MEDFILT_MAX  255
+#define DD_MEDFILT_TILE 1024
+int dd_medfilt_f32(const float* in, float* out, int64_t n, int ksize, void* stream);
+int dd_medfilt_f64(const double* in, double* out, int64_t n, int ksize, void* stream);
+
+/* ---- F6: filters.blackmanHarrisConv.applyOn -> scipy.signal.convolve(x, w, mode='same') (filters.py:145-174) --- */
+/* out[i] = sum_k taps[k] in[i + (ntaps-1)/2 - k], in taken as zero outside [0, n) (np.convolve(in, taps)[s : s + n], odd
+ * and even ntaps, n < ntaps included).  taps: ntaps float64 on the DEVICE.  Sums in float64; the complex64 form rounds once
+ * at the store.  Stateless; in != out. */
+int dd_conv_same_f64(const double* in, double* out, int64_t n, const double* taps, int ntaps, void* stream);
+int dd_conv_same_c64(const float* in_c64, float* out_c64, int64_t n, const double* taps, int ntaps, void* stream);
+
 /* ---- fused hot path: offsetFreq -> filter(FIR) -> bwLim(M) -> demod_fm -------
  * (decode_noaa.py:623, decode_fm.py:64-68, decode_afsk1200.py:79-94,
  *  tutorial/3_chunking.py:24-38).  One kernel per chunk; all carried state (NCO
