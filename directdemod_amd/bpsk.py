@@ -1,6 +1,7 @@
 """
 Funcube BPSK sync detection stages -- the reference's decode_funcube.getSyncs (decode_funcube.py:148-306), a Python loop over every
-IQ sample there.  Device stages (dd_funcube.h): the Gardner / agc / costas walk (`Walker`), the per-sample lim values (`Walker.lim`),
+IQ sample there.  Device stages (dd_funcube.h; what the Meteor-M2 decoder shares is in symbolsync.py and dd_symbol_walk.h): the
+Gardner / agc / costas walk (`Walker`, configured here), the per-sample lim values (`Walker.lim`),
 the MINSYNC list (`minsync_list`), the MAXSYNC correlations (`maxsync_argmax`), the mixer with the Doppler ramp (`mix_ramp`) and
 the low-pass in scipy.signal.lfilter's own operation order (`Lowpass`).
 Host stages: the correlation-buffer bookkeeping (`maxsync_buffers`), O(syncs); NumPy restatements of the device arithmetic (`lim`,
@@ -11,9 +12,10 @@ import math
 
 import numpy as np
 
-from . import _hip, qpsk
+from . import symbolsync
 from ._hip import DevArray, check, lib
-from .qpsk import hyp_table, lim, limBin, mix  # noqa: F401  (the reference's two decoders define these alike; mix is offsetFreq)
+from .symbolsync import hyp_table, lim, limBin, mix  # noqa: F401  (the names this module has always offered; mix is offsetFreq)
+from .symbolsync import interval_descriptors, iq_pointers, maxcorr, minsync_fired
 
 SYMBOL_RATE = 12000
 SYNC = "101000110001000000000001010111100"
@@ -54,7 +56,7 @@ def correlate_same_blocks(buf, t, rep=REP):
 
 def costas_coefficients():
     """costas.compAlphaBeta for bw and bw / 2: (alpha, beta, alpha_locked, beta_locked)"""
-    return qpsk.costas_coefficients(bw=COSTAS_BW)
+    return symbolsync.costas_coefficients(COSTAS_BW)
 
 
 class Lowpass:
@@ -85,70 +87,21 @@ class Lowpass:
         return out
 
 
-class Walker:
-    """The symbol walk over a recording of `total` samples at `fs`, fed chunk by chunk in order (`walk`, then `lim`).  Per symbol k (device
-    arrays, `nsym` long once fed): bidx, aidx (sample indices of the B and A samples), agc (agc.adjust of A, gardnerC), ph (the
-    costas phasor the symbol was corrected with: pllObj.output after the step), sym (the corrected symbol, gardnerA after
-    pllObj.loop), pf ((phase, freq) after the step); `lim_values` = the int8 of every sample fed.
-
-    Device memory: room for total / (P / 2) symbols -- twice the nominal count -- at 96 B each, plus 1 B per sample of lim values:
-    about 1.4 GB and 1.2 GB for a 10-minute pass at 2.048 MS/s.  A recording whose timing runs faster than one symbol per P / 2
-    samples (the reference would keep decoding) raises RuntimeError."""
-
-    def __init__(self, fs, total):
-        _hip.require_gpu()
-        P = fs / 12000
-        a0, b0, a1, b1 = costas_coefficients()
-        self.params = np.ascontiguousarray(np.concatenate(([P, P / 2, (P / 2) + 1, a0, b0, a1, b1], hyp_table())), dtype=np.float64)
-        st = np.zeros(1, dtype=qpsk._STATE)
-        st["amean"], st["freq"], st["pmean"], st["alpha"], st["beta"] = 180.0, 0.001, 1.0, a0, b0
-        self.state = DevArray.from_host(st.view(np.uint8))
-        self.total = int(total)
-        self.cap = int(total / (P / 2)) + 64             # a symbol takes at least P/2 samples unless timing is thrown far
-        cap = max(self.cap, 1)
-        self.bidx, self.aidx = DevArray(cap, np.int64), DevArray(cap, np.int64)
-        self.agc, self.ph, self.sym, self.pf = (DevArray(cap, np.complex128) for _ in range(4))
-        self.lim_values = DevArray(max(self.total, 1), np.int8)
-        self.fed = 0
-        self.nsym = 0
-
-    def _state(self):
-        return self.state.to_host().view(qpsk._STATE)[0]
-
-    def walk(self, x):
-        """the symbol walk over the next chunk"""
-        if x.dtype != np.dtype(np.complex128):
-            raise TypeError("complex128 device array expected, got %s" % x.dtype)
-        if self.fed + x.n > self.total:
-            raise ValueError("more samples than the recording holds")
-        dp = C.POINTER(C.c_double)
-        check(lib().dd_funcube_walk(x.ptr, x.n, self.fed, self.state.ptr, self.params.ctypes.data_as(dp), self.cap,
-                                    self.bidx.ptr, self.aidx.ptr, self.agc.ptr, self.ph.ptr, self.sym.ptr, self.pf.ptr, None),
-              "dd_funcube_walk")
-        st = self._state()
-        if st["overflow"]:
-            raise RuntimeError("funcube walk: more symbols than %d (timing thrown by the input)" % self.cap)
-        self.nsym = int(st["ctr"])
-
-    def lim(self, x):
-        """the lim values of the chunk just walked (its samples take the phasors of the symbols walked so far)"""
-        check(lib().dd_funcube_lim(x.ptr, x.n, self.fed, self.aidx.ptr, self.nsym, self.ph.ptr, self.lim_values.ptr, self.total, None),
-              "dd_funcube_lim")
-        self.fed += x.n
-
-    def view(self, name):
-        return getattr(self, name).view(0, self.nsym)
+class Walker(symbolsync.Walker):
+    """symbolsync.Walker for decode_funcube: `lim_values` = the int8 real part of every sample fed.  Device memory: about 1.4 GB of
+    symbols and 1.2 GB of lim values for a 10-minute pass at 2.048 MS/s."""
+    SYMBOL_RATE = SYMBOL_RATE
+    COSTAS_BW = COSTAS_BW
+    AMEAN0 = 180.0
+    LIM_DTYPE = np.int8
+    WALK, LIM = "dd_funcube_walk", "dd_funcube_lim"
+    LABEL = "funcube"
 
 
 def mix_ramp(x, fs, rmp):
     """commSignal.offsetFreq(doppCorrect_freqs) with the reference's arithmetic, the frequencies formed in the kernel from a
     frequency_shift.ramp (dd_funcube_mix_ramp): raw u8 pairs (_hip.IQ8) or complex64 in, complex64 out, k counting from 0"""
-    if x.dtype == _hip.IQ8:
-        raw, c64 = x.ptr, None
-    elif x.dtype == np.dtype(np.complex64):
-        raw, c64 = None, x.ptr
-    else:
-        raise TypeError("raw u8 pairs or complex64 expected, got %s" % x.dtype)
+    raw, c64 = iq_pointers(x)
     if rmp.n != x.n:
         raise ValueError("a ramp of %d samples for a chunk of %d" % (rmp.n, x.n))
     out = DevArray(x.n, np.complex64)
@@ -160,19 +113,7 @@ def mix_ramp(x, fs, rmp):
 
 def minsync_list(w, cap=1 << 20):
     """symbols k >= 329 whose 330-symbol window fires: int64[m, 2] = (k, mismatches), sorted by k (the reference's ctr is k + 1)"""
-    nsym = w.nsym
-    if nsym == 0:
-        return np.zeros((0, 2), dtype=np.int64)
-    bits = DevArray(nsym, np.uint8)
-    sb = np.ascontiguousarray(sync_bits(), dtype=np.uint8)
-    cand = DevArray(2 * cap, np.int64)
-    cnt = DevArray(1, np.uint64)
-    check(lib().dd_funcube_minsync(w.sym.ptr, nsym, sb.ctypes.data, bits.ptr, cap, cand.ptr, cnt.ptr, None), "dd_funcube_minsync")
-    m = int(cnt.to_host()[0])
-    if m > cap:
-        raise RuntimeError("funcube MINSYNC: %d firing windows, more than %d" % (m, cap))
-    c = cand.view(0, 2 * m).to_host().reshape(m, 2) if m else np.zeros((0, 2), dtype=np.int64)
-    return c[np.argsort(c[:, 0], kind="stable")]
+    return minsync_fired("dd_funcube_minsync", w, sync_bits(), 2, cap, "funcube MINSYNC: %d firing windows")[0]
 
 
 def maxsync_buffers(ks, total, a_at, nsym):
@@ -219,23 +160,15 @@ def maxsync_buffers(ks, total, a_at, nsym):
 def maxsync_argmax(lim_values, bufs, rep=REP):
     """[(intervals, start)] -> int64[n, 2] = (argmax, max) of |np.correlate(buffer, np.repeat(template, rep), 'same')| on the
     device; the buffers' int32 prefix sums live in one scratch device array for the call (4 B per buffer entry)"""
-    n = len(bufs)
-    out = np.zeros((n, 2), dtype=np.int64)
-    if n == 0:
-        return out
-    desc = np.zeros((n, 5), dtype=np.int64)
     off = 0
-    for i, (ivs, _) in enumerate(bufs):
-        if len(ivs) > 2:
-            raise ValueError("a correlation buffer spans at most two sample intervals")
-        (lo0, n0), (lo1, n1) = (list(ivs) + [(0, 0)])[:2]
-        if n0 + n1 < NSYNC * rep:
-            raise ValueError("a correlation buffer of %d samples is shorter than the template (%d)" % (n0 + n1, NSYNC * rep))
-        desc[i] = (lo0, n0, lo1, n1, off)
-        off += n0 + n1 + 1
+
+    def scratch_offset(_, length):
+        nonlocal off
+        if length < NSYNC * rep:
+            raise ValueError("a correlation buffer of %d samples is shorter than the template (%d)" % (length, NSYNC * rep))
+        at, off = off, off + length + 1
+        return at
+    desc = interval_descriptors(bufs, scratch_offset)
     sb = np.ascontiguousarray(sync_bits(), dtype=np.uint8)
-    scratch = DevArray(off, np.int32)
-    d = DevArray(2 * n, np.int64)
-    check(lib().dd_funcube_maxcorr(lim_values.ptr, lim_values.n, desc.ctypes.data, n, sb.ctypes.data, int(rep), scratch.ptr, off,
-                                   d.ptr, None), "dd_funcube_maxcorr")
-    return d.to_host().reshape(n, 2)
+    scratch = DevArray(max(off, 1), np.int32)
+    return maxcorr("dd_funcube_maxcorr", lim_values, desc, sb.ctypes.data, int(rep), scratch.ptr, off)

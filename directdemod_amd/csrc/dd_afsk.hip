@@ -79,6 +79,9 @@ extern "C" int dd_afsk_edges_f64(const double* binary_filter, int64_t n, int spb
 // peak pick, bit slicing, frames (decode_afsk1200.py:160-269)
 #include "dd_afsk_frames.h"
 
+// the symbol walk of the two sync detectors below, and what else they share
+#include "dd_symbol_walk.h"
+
 // Meteor-M2 QPSK sync detection (decode_meteorm2.py:229-324)
 #include "dd_meteor.h"
 

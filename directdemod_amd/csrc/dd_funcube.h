@@ -1,12 +1,12 @@
 // Funcube BPSK sync detection (the reference's decode_funcube.getSyncs, decode_funcube.py:148-306), included by dd_afsk.hip after
-// dd_meteor.h (built with -ffp-contract=off: every float64 operation below is the reference's, in its order, rounded on its own).
-// The walk's state and parameters are DDMeteorState / DDMeteorParams; agc.adjust but for its cap, costas.loop from the error on,
-// hyp, lim, the run skipping and the mixer's rotation are dd_meteor.h's device functions.
+// dd_symbol_walk.h, which holds the walk's state and parameters, its body, agc.adjust, costas.loop, hyp, lim, the run skipping and the
+// mixer's rotation (built with -ffp-contract=off: every float64 operation is the reference's, in its order,
+// rounded on its own).  Here: the BPSK policy of the walk, the low-pass, the ramp mixer, the sync scoring and the prefix-sum
+// correlation.
 //
 //   k_funcube_mix_ramp -- the reference's float64 mixer with the frequency ramp of decode_funcube.py:215-226 formed per sample
 //   k_funcube_lowpass  -- scipy.signal.lfilter's recurrence sample by sample in its own operation order: bit for bit its output
-//   k_funcube_walk     -- the Gardner timing walk with agc.adjust on the B and A samples (wave 0) and costas.loop on every A sample
-//                         (wave 1, one tile behind), the two-wave pipeline of k_meteor_walk
+//   k_funcube_walk     -- dd_sym_walk with agc.adjust's cap of 20 and the BPSK error imag * hyp(real) / 255
 //   k_funcube_lim      -- lim(real(x * out) / 2) per sample, out = the Costas phasor active at that sample
 //   k_funcube_minsync  -- limBin(real) per symbol and the 330-bit sync score of every full window; firing symbols are compacted
 //   k_funcube_maxcorr  -- |np.correlate(buffer, np.repeat(template, rep), 'same')| and its first argmax from a prefix sum of the
@@ -21,6 +21,7 @@
 struct DDFuncubeBuf {                 // a correlation buffer: samples [lo0, lo0 + n0) then [lo1, lo1 + n1); its n0 + n1 + 1 prefix sums
     int64_t lo0, n0, lo1, n1, scratch;    // start at scratch[scratch]
 };
+static_assert(sizeof(DDFuncubeBuf) == 5 * sizeof(int64_t), "dd_sym_with_descriptors uploads five words per buffer");
 
 #define DD_FC_IIR_N 7                 // coefficients of butter(fs, bw)'s sixth-order low-pass
 #define DD_FC_IIR_TILE 1024
@@ -88,140 +89,19 @@ __global__ void __launch_bounds__(64) k_funcube_lowpass(const float2* __restrict
     }
 }
 
-// costas.loop (decode_funcube.py:60-81): the BPSK error imag * hyp(real) / 255; returns correctedIn, leaves the phasor it used in o
-__device__ __forceinline__ double2 dd_fc_costas(double2 a, DDMeteorState& s, const DDMeteorParams& p, const double* __restrict__ tbl,
-                                                double2& o) {
-    double sn, cs;
-    sincos(s.phase, &sn, &cs);                                          // np.exp(-1j * phase) = (cos, -sin)
-    o = make_double2(cs, -sn);
-    const double cr = a.x * o.x - a.y * o.y, ci = a.x * o.y + a.y * o.x;
-    dd_met_loop_update(ci * dd_met_hyp(cr, tbl) / 255.0, s, p);
-    return make_double2(cr, ci);
-}
+// decode_funcube's agc.adjust cap and costas.loop error (decode_funcube.py:30, :65)
+struct DDFuncubeBpsk {
+    static constexpr int CAP = 20;
+    static __device__ __forceinline__ double error(double cr, double ci, const double* __restrict__ tbl) {
+        return ci * dd_met_hyp(cr, tbl) / 255.0;
+    }
+};
 
-// k_meteor_walk with decode_funcube's agc and costas: wave 0 stages the tiles and runs the timing chain (Gardner test, timing,
-// agc.adjust on B and A, resync_error), handing each tile's AGC'd A samples to wave 1 through LDS; wave 1's lane 0 runs costas.loop
-// over them while wave 0 walks the next tile.  Runs of plain "timing += 1" samples are taken in one step (dd_met_skip: a jump ends
-// below twice the power of two above the timing, whatever the symbol period, so it crosses one binade at most).
 __global__ void __launch_bounds__(128) k_funcube_walk(const double2* __restrict__ x, int64_t n, int64_t base, DDMeteorState* __restrict__ stp,
                                                        const DDMeteorParams prm, int64_t cap, int64_t* __restrict__ bidx,
                                                        int64_t* __restrict__ aidx, double2* __restrict__ agc, double2* __restrict__ ph,
                                                        double2* __restrict__ sym, double2* __restrict__ pf) {
-    constexpr int R = DD_MET_TILE / 64;
-    __shared__ double2 tile[DD_MET_TILE];
-    __shared__ double2 sbuf[2][DD_MET_TILE];                            // a tile yields at most one symbol per sample
-    __shared__ int64_t sbase[2];
-    __shared__ int scount[2];
-    __shared__ double hyp[256];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    for (int i = threadIdx.x; i < 256; i += 128) hyp[i] = prm.hyp[i];
-    DDMeteorState s = *stp;
-    double2 pre[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const int64_t i = (int64_t)r * 64 + lane;
-        pre[r] = (wave == 0 && i < n) ? x[i] : make_double2(0.0, 0.0);
-    }
-    const int64_t ntiles = (n + DD_MET_TILE - 1) / DD_MET_TILE;
-    for (int64_t it = 0; it <= ntiles; ++it) {
-        const int64_t t0 = it * DD_MET_TILE;
-        if (wave == 0 && it < ntiles) {
-#pragma unroll
-            for (int r = 0; r < R; ++r) tile[r * 64 + lane] = pre[r];
-        }
-        __syncthreads();
-        if (wave == 0) {
-            if (it < ntiles) {
-#pragma unroll
-                for (int r = 0; r < R; ++r) {                           // next tile in flight while lane 0 walks this one
-                    const int64_t i = t0 + DD_MET_TILE + (int64_t)r * 64 + lane;
-                    if (i < n) pre[r] = x[i];
-                }
-                if (lane == 0) {
-                    const int buf = (int)(it & 1);
-                    const int m = (int)min((int64_t)DD_MET_TILE, n - t0);
-                    int cnt = 0;
-                    sbase[buf] = s.ctr;
-                    int j = 0;
-                    while (j < m) {
-                        const double t = s.timing;
-                        if (t >= prm.halfP && t < prm.halfP1) {
-                            const double2 b = dd_met_agc_cap<20>(tile[j], s);
-                            s.b_re = b.x;
-                            s.b_im = b.y;
-                            s.bidx = base + t0 + j;
-                            s.timing = t + 1.0;
-                            ++j;
-                        } else if (t >= prm.P) {
-                            const double2 a = dd_met_agc_cap<20>(tile[j], s);
-                            double tt = t - prm.P;
-                            const double rerr = (a.y - s.c_im) * s.b_im;
-                            tt += rerr * prm.P / 2000000.0;
-                            s.c_re = a.x;
-                            s.c_im = a.y;
-                            const int64_t k = s.ctr;
-                            if (k < cap) {
-                                bidx[k] = s.bidx;
-                                aidx[k] = base + t0 + j;
-                                agc[k] = a;
-                            } else {
-                                s.overflow = 1;
-                            }
-                            sbuf[buf][cnt++] = a;
-                            s.ctr = k + 1;
-                            s.timing = tt + 1.0;
-                            ++j;
-                        } else {
-                            const int mm = t >= 1.0 ? dd_met_skip(t, t < prm.halfP ? prm.halfP : prm.P, m - j) : 0;
-                            if (mm > 0) {
-                                s.timing = t + (double)mm;
-                                j += mm;
-                            } else {
-                                s.timing = t + 1.0;
-                                ++j;
-                            }
-                        }
-                    }
-                    scount[buf] = cnt;
-                }
-            }
-        } else if (it > 0 && lane == 0) {
-            const int buf = (int)((it - 1) & 1);
-            const int cnt = scount[buf];
-            const int64_t k0 = sbase[buf];
-            for (int i = 0; i < cnt; ++i) {
-                double2 o;
-                const double2 c = dd_fc_costas(sbuf[buf][i], s, prm, hyp, o);
-                const int64_t k = k0 + i;
-                if (k < cap) {
-                    ph[k] = o;
-                    sym[k] = c;
-                    pf[k] = make_double2(s.phase, s.freq);
-                }
-            }
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {                                            // the timing chain's fields
-        stp->timing = s.timing;
-        stp->b_re = s.b_re;
-        stp->b_im = s.b_im;
-        stp->c_re = s.c_re;
-        stp->c_im = s.c_im;
-        stp->dc_re = s.dc_re;
-        stp->dc_im = s.dc_im;
-        stp->amean = s.amean;
-        stp->ctr = s.ctr;
-        stp->bidx = s.bidx;
-        stp->overflow = s.overflow;
-    } else if (threadIdx.x == 64) {                                    // the Costas chain's
-        stp->freq = s.freq;
-        stp->phase = s.phase;
-        stp->pmean = s.pmean;
-        stp->alpha = s.alpha;
-        stp->beta = s.beta;
-        stp->lock = s.lock;
-    }
+    dd_sym_walk<DDFuncubeBpsk>(x, n, base, stp, prm, cap, bidx, aidx, agc, ph, sym, pf);
 }
 
 // sample base + j takes pllObj.output as the loop before it left it -- costas.loop sets it on entry, so it is the phasor the last
@@ -324,21 +204,7 @@ __global__ void __launch_bounds__(DD_FC_CORR_THREADS) k_funcube_maxcorr(const si
         if (c < 0) c = -c;
         if (c > best) { best = c; bi = i; }
     }
-    rv[tid] = best;
-    ri[tid] = bi;
-    __syncthreads();
-    for (int w = DD_FC_CORR_THREADS / 2; w > 0; w >>= 1) {
-        if (tid < w) {
-            const long long v2 = rv[tid + w];
-            const int i2 = ri[tid + w];
-            if (v2 > rv[tid] || (v2 == rv[tid] && i2 < ri[tid])) { rv[tid] = v2; ri[tid] = i2; }
-        }
-        __syncthreads();
-    }
-    if (tid == 0) {
-        out[2 * blockIdx.x] = ri[0];
-        out[2 * blockIdx.x + 1] = rv[0];
-    }
+    dd_sym_first_max<DD_FC_CORR_THREADS>(best, bi, rv, ri, out);
 }
 
 // commSignal.offsetFreq with decode_funcube.py:215-226's frequency array: x (complex64) *= np.exp(-1.0j*2.0*np.pi*f*np.arange(n)/fs),
@@ -382,17 +248,7 @@ extern "C" int dd_funcube_lowpass(const void* in_c64, void* out_c128, int64_t n,
 
 extern "C" int dd_funcube_walk(const void* x, int64_t n, int64_t base, void* state, const double* params_host, int64_t cap,
                                int64_t* bidx, int64_t* aidx, void* agc, void* ph, void* sym, void* pf, void* stream) {
-    DD_REQUIRE(n >= 0 && base >= 0 && cap >= 0, "dd_funcube_walk: sizes");
-    DD_REQUIRE(state != nullptr && params_host != nullptr, "dd_funcube_walk: state / params");
-    if (n == 0) return DD_OK;
-    DD_REQUIRE(x != nullptr && bidx != nullptr && aidx != nullptr && agc != nullptr && ph != nullptr && sym != nullptr && pf != nullptr,
-               "dd_funcube_walk: null buffer");
-    DDMeteorParams p;
-    memcpy(&p, params_host, sizeof(p));
-    hipLaunchKernelGGL(k_funcube_walk, dim3(1), dim3(128), 0, dd_stream(stream), (const double2*)x, n, base, (DDMeteorState*)state, p, cap,
-                       bidx, aidx, (double2*)agc, (double2*)ph, (double2*)sym, (double2*)pf);
-    DD_LAUNCH_CHECK();
-    return DD_OK;
+    return dd_sym_walk_launch(k_funcube_walk, "dd_funcube_walk", x, n, base, state, params_host, cap, bidx, aidx, agc, ph, sym, pf, stream);
 }
 
 extern "C" int dd_funcube_lim(const void* x, int64_t n, int64_t base, const int64_t* aidx, int64_t nsym, const void* ph, int8_t* out,
@@ -443,16 +299,8 @@ extern "C" int dd_funcube_maxcorr(const int8_t* lim, int64_t lim_len, const int6
             DD_REQUIRE(d[4] + d[1] + d[3] + 1 <= o[4] || o[4] + o[1] + o[3] + 1 <= d[4], "dd_funcube_maxcorr: overlapping scratch");
         }
     }
-    DDFuncubeBuf* dbufs = nullptr;
-    DD_HIP_CHECK(hipMalloc((void**)&dbufs, (size_t)nbuf * sizeof(DDFuncubeBuf)));
-    int rc = DD_OK;
-    if (hipMemcpyAsync(dbufs, bufs_host, (size_t)nbuf * sizeof(DDFuncubeBuf), hipMemcpyHostToDevice, dd_stream(stream)) != hipSuccess) rc = DD_ERR_HIP;
-    if (rc == DD_OK) {
+    return dd_sym_with_descriptors(bufs_host, nbuf, "dd_funcube_maxcorr", stream, [&](void* dbufs) {
         hipLaunchKernelGGL(k_funcube_maxcorr, dim3((unsigned)nbuf), dim3(DD_FC_CORR_THREADS), 0, dd_stream(stream), (const signed char*)lim,
                            (const DDFuncubeBuf*)dbufs, dd_fc_sync_word(sync_bits_host), rep, (int*)scratch, out);
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(dd_stream(stream)) != hipSuccess) rc = DD_ERR_HIP;
-    }
-    hipFree(dbufs);
-    DD_REQUIRE(rc == DD_OK, "dd_funcube_maxcorr: launch failed");
-    return DD_OK;
+    });
 }

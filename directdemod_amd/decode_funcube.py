@@ -17,89 +17,46 @@ Deviations from the reference:
   - with exactly one MAXSYNC the reference raises ValueError (np.min of an empty np.diff); here getSyncs returns [] with useful 0.
 """
 import logging
-import time
 
 import numpy as np
 
-from . import _hip, bpsk, chunker, comm, frequency_shift
+from . import bpsk, frequency_shift, symbolsync
 from .bpsk import lim, limBin  # noqa: F401  (module-level helpers, as in the reference)
 
 
-class decode_funcube:
+class decode_funcube(symbolsync.SyncDecoder):
     """Object to decode Funcube: decode_funcube(sigsrc, offset, bw, center_frequency, signal_freq, corrfreq) as in the reference
     (bw None -> 7000).  use_device_raw: read the recording as raw u8 pairs resident on the device when the source offers it
-    (source.read_device_raw)."""
+    (source.read_device_raw).
+    `useful`: 1 if two MAXSYNCs lie 4.98 s +- 0.2 s apart; `getSyncs`: np.int64 positions; `getSymbols`: at 12000 Hz.
+    minsyncs: the MINSYNC ctr values; buffers: (intervals, maxBuffStart); ramps: with corrfreq, per chunk (chunk_offset,
+    frequency_shift.ramp, doppCorrect_current after it)."""
+    WALKER = bpsk.Walker
+    STAGES = ("doppler", "mix", "lowpass")
+    SPACING = (4.98, 0.2)
 
     def __init__(self, sigsrc, offset, bw, center_frequency, signal_freq, corrfreq=False, use_device_raw=True):
-        self.__bw = 7000 if bw is None else bw
-        self.__sigsrc = sigsrc
-        self.__offset = offset
-        self.__center_frequency = int(center_frequency)
-        self.__signal_freq = int(signal_freq)
-        self.__corrfreq = corrfreq
-        self.__use_raw = use_device_raw
-        self.__useful = 0
-        self.__result = None
-        self.timings = {}                 # seconds per stage of the last decode: doppler, mix, lowpass, walk, lim (summed over chunks), minsync, maxsync
-        self.minsyncs = []                # MINSYNC ctr values of the last decode
-        self.buffers = []                 # the MAXSYNC correlation buffers: (intervals [(first sample, count)], maxBuffStart)
-        self.argmax = []                  # argmax of each buffer's |correlation|
-        self.ramps = []                   # with corrfreq, per chunk: (chunk_offset, frequency_shift.ramp, doppCorrect_current after it)
+        super().__init__(sigsrc, use_device_raw)
+        self._bw = 7000 if bw is None else bw
+        self._offset = offset
+        self._center_frequency = int(center_frequency)
+        self._signal_freq = int(signal_freq)
+        self._corrfreq = corrfreq
+        self.ramps = []
 
-    @property
-    def useful(self):
-        """1 if two MAXSYNCs lie 4.98 s +- 0.2 s apart, else 0 (0 until getSyncs has run)"""
-        return self.__useful
-
-    @property
-    def getSyncs(self):
-        """The MAXSYNC sample positions (np.int64) but the first"""
-        return list(self._decode()[0])
-
-    @property
-    def getSymbols(self):
-        """The PLL-corrected soft symbols as a device-resident commSignal at 12000 Hz"""
-        return comm.commSignal(bpsk.SYMBOL_RATE, self._decode()[1])
-
-    def walker(self):
-        """the symbol walk of the last decode (bpsk.Walker: per-symbol device arrays)"""
-        return self._decode()[2]
-
-    def _decode(self):
-        if self.__result is not None:
-            return self.__result
-        _hip.require_gpu()
-        src = self.__sigsrc
-        t = {"doppler": 0.0, "mix": 0.0, "lowpass": 0.0, "walk": 0.0, "lim": 0.0}
-        t0 = time.perf_counter()
-
-        def lap(name):
-            nonlocal t0
-            _hip.sync()
-            now = time.perf_counter()
-            t[name] = t.get(name, 0.0) + now - t0
-            t0 = now
-        ck = chunker.chunker(src)
-        bf = bpsk.Lowpass(src.sampFreq, self.__bw)
-        read = src.read
-        if self.__use_raw and hasattr(src, "read_device_raw") and src.length > 0 and src.read_device_raw(0, 1) is not None:
-            read = src.read_device_raw
+    def _front_end(self, src, ck, lap):
+        bf = bpsk.Lowpass(src.sampFreq, self._bw)
         track = ramp = None
-        ramps = []
-        if self.__corrfreq and src.length > 0:
-            track = frequency_shift.dopplerTrack(src, self.__center_frequency, self.__signal_freq, 20000)
-            ramp = frequency_shift.dopplerRamp(self.__offset, src.sampFreq)
+        self.ramps = ramps = []
+        if self._corrfreq and src.length > 0:
+            track = frequency_shift.dopplerTrack(src, self._center_frequency, self._signal_freq, 20000)
+            ramp = frequency_shift.dopplerRamp(self._offset, src.sampFreq)
             track.shift(0, len(ck.getChunks))             # the one device pass over the recording, timed on its own
             lap("doppler")
-        w = bpsk.Walker(src.sampFreq, src.length)
-        for number, (a, b) in enumerate(ck.getChunks):
-            if b <= a:
-                continue
-            d = read(a, b)
-            if not isinstance(d, _hip.DevArray):
-                d = _hip.DevArray.from_host(np.asarray(d), dtype=np.complex64)
+
+        def front(number, a, b, d):
             if track is None:
-                mixed = bpsk.mix(d, src.sampFreq, self.__offset)
+                mixed = bpsk.mix(d, src.sampFreq, self._offset)
             else:
                 chunk_offset = track.shift(number, len(ck.getChunks))
                 logging.info("doppler shift is %f Hz", chunk_offset)
@@ -109,35 +66,18 @@ class decode_funcube:
             lap("mix")
             x = bf.apply(mixed)
             lap("lowpass")
-            w.walk(x)
-            lap("walk")
-            w.lim(x)
-            lap("lim")
+            return x
+        return front
+
+    def _sync_search(self, w, total, a_at, lap):
         mins = bpsk.minsync_list(w)
         lap("minsync")
         for k, m in mins:
             logging.info("MINSYNC: %d %f", k + 1, abs(m - bpsk.WIN / 2))
-        aidx = w.aidx
-
-        def a_at(k):
-            return int(aidx.view(k, 1).to_host()[0])
-        bufs = bpsk.maxsync_buffers(mins[:, 0], src.length, a_at, w.nsym)
+        bufs = bpsk.maxsync_buffers(mins[:, 0], total, a_at, w.nsym)
         am = bpsk.maxsync_argmax(w.lim_values, bufs)
         lap("maxsync")
-        self.timings = t
-        maxSyncs = []
-        for (ivs, start), (arg, _) in zip(bufs, am):
-            v = start + np.int64(arg)
-            logging.info("MAXSYNC %d", v)
-            maxSyncs.append(v)
-        self.minsyncs = [int(k) + 1 for k in mins[:, 0]]
-        self.buffers = bufs
-        self.argmax = [int(a) for a in am[:, 0]]
-        self.ramps = ramps
-        syncs = []
-        if len(maxSyncs) > 1:
-            if np.min(np.abs(np.diff(maxSyncs) - (4.98 * 2048000))) < (0.2 * 2048000):
-                self.__useful = 1
-            syncs = list(maxSyncs)[1:]
-        self.__result = (syncs, w.view("sym"), w)
-        return self.__result
+        return [int(k) + 1 for k in mins[:, 0]], bufs, am
+
+    def _position(self, start, arg):
+        return start + np.int64(arg)

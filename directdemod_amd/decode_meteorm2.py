@@ -15,83 +15,38 @@ Deviations from the reference:
   - with exactly one MAXSYNC the reference raises ValueError (np.min of an empty np.diff); here getSyncs returns [] with useful 0.
 """
 import logging
-import time
 
 import numpy as np
 
-from . import _hip, chunker, comm, filters, qpsk
+from . import comm, filters, qpsk, symbolsync
 from .qpsk import lim, limBin  # noqa: F401  (module-level helpers, as in the reference)
 
 
-class decode_meteorm2:
+class decode_meteorm2(symbolsync.SyncDecoder):
     """Object to decode Meteor m2: decode_meteorm2(sigsrc, offset, bw) as in the reference (bw None -> 70000).
-    use_device_raw: read the recording as raw u8 pairs resident on the device when the source offers it (source.read_device_raw)."""
+    use_device_raw: read the recording as raw u8 pairs resident on the device when the source offers it (source.read_device_raw).
+    `useful`: 1 if two MAXSYNCs lie 0.11 s +- 0.05 s apart; `getSyncs`: np.float64 positions; `getSymbols`: at 72000 Hz.
+    minsyncs: (ctr, template 0 = sync2mhz / 1 = sync2mhz2) per MINSYNC event; buffers: (intervals, maxBuffStart, template)."""
+    WALKER = qpsk.Walker
+    STAGES = ("front_end",)
+    SPACING = (0.11, 0.05)
 
     def __init__(self, sigsrc, offset, bw=None, use_device_raw=True):
-        self.__bw = 70000 if bw is None else bw
-        self.__sigsrc = sigsrc
-        self.__offset = offset
-        self.__use_raw = use_device_raw
-        self.__useful = 0
-        self.__result = None
-        self.timings = {}                 # seconds per stage of the last decode: front_end, walk, lim (summed over chunks), minsync, maxsync
-        self.minsyncs = []                # MINSYNC events of the last decode: (ctr, template 0 = sync2mhz / 1 = sync2mhz2)
-        self.buffers = []                 # the MAXSYNC correlation buffers: (intervals [(first sample, count)], maxBuffStart, template)
-        self.argmax = []                  # argmax of each buffer's |correlation|
+        super().__init__(sigsrc, use_device_raw)
+        self._bw = 70000 if bw is None else bw
+        self._offset = offset
 
-    @property
-    def useful(self):
-        """1 if two MAXSYNCs lie 0.11 s +- 0.05 s apart, else 0 (0 until getSyncs has run)"""
-        return self.__useful
+    def _front_end(self, src, ck, lap):
+        bf = filters.butter(src.sampFreq, self._bw)
 
-    @property
-    def getSyncs(self):
-        """The MAXSYNC sample positions (np.float64) but the first"""
-        return list(self._decode()[0])
-
-    @property
-    def getSymbols(self):
-        """The PLL-corrected soft symbols as a device-resident commSignal at 72000 Hz"""
-        return comm.commSignal(qpsk.SYMBOL_RATE, self._decode()[1])
-
-    def walker(self):
-        """the symbol walk of the last decode (qpsk.Walker: per-symbol device arrays)"""
-        return self._decode()[2]
-
-    def _decode(self):
-        if self.__result is not None:
-            return self.__result
-        _hip.require_gpu()
-        src = self.__sigsrc
-        t = {"front_end": 0.0, "walk": 0.0, "lim": 0.0}
-        t0 = time.perf_counter()
-
-        def lap(name):
-            nonlocal t0
-            _hip.sync()
-            now = time.perf_counter()
-            t[name] = t.get(name, 0.0) + now - t0
-            t0 = now
-        ck = chunker.chunker(src)
-        bf = filters.butter(src.sampFreq, self.__bw)
-        read = src.read
-        if self.__use_raw and hasattr(src, "read_device_raw") and src.length > 0 and src.read_device_raw(0, 1) is not None:
-            read = src.read_device_raw
-        w = qpsk.Walker(src.sampFreq, src.length)
-        for a, b in ck.getChunks:
-            if b <= a:
-                continue
-            d = read(a, b)
-            if not isinstance(d, _hip.DevArray):
-                d = _hip.DevArray.from_host(np.asarray(d), dtype=np.complex64)
-            sig = comm.commSignal(src.sampFreq, qpsk.mix(d, src.sampFreq, self.__offset))
+        def front(number, a, b, d):
+            sig = comm.commSignal(src.sampFreq, qpsk.mix(d, src.sampFreq, self._offset))
             sig.filter(bf)
-            x = sig.device_signal
             lap("front_end")
-            w.walk(x)
-            lap("walk")
-            w.lim(x)
-            lap("lim")
+            return sig.device_signal
+        return front
+
+    def _sync_search(self, w, total, a_at, lap):
         cands, bits = qpsk.minsync_candidates(w)
 
         def fetch(lo, hi):
@@ -101,26 +56,10 @@ class decode_meteorm2:
         lap("minsync")
         for k, _ in events:
             logging.info("MINSYNC: %d", k + 1)
-        aidx = w.aidx
-
-        def a_at(k):
-            return int(aidx.view(k, 1).to_host()[0])
-        bufs = qpsk.maxsync_buffers(events, src.length, a_at, w.nsym)
+        bufs = qpsk.maxsync_buffers(events, total, a_at, w.nsym)
         am = qpsk.maxsync_argmax(w.lim_values, bufs)
         lap("maxsync")
-        self.timings = t
-        maxSyncs = []
-        for (ivs, start, _), (arg, _) in zip(bufs, am):
-            v = start + (np.int64(arg) / 2.0)
-            logging.info("MAXSYNC %d", v)
-            maxSyncs.append(v)
-        self.minsyncs = [(k + 1, tm) for k, tm in events]
-        self.buffers = bufs
-        self.argmax = [int(a) for a in am[:, 0]]
-        syncs = []
-        if len(maxSyncs) > 1:
-            if np.min(np.abs(np.diff(maxSyncs) - (0.11 * 2048000))) < (0.05 * 2048000):
-                self.__useful = 1
-            syncs = list(maxSyncs)[1:]
-        self.__result = (syncs, w.view("sym"), w)
-        return self.__result
+        return [(k + 1, tm) for k, tm in events], bufs, am
+
+    def _position(self, start, arg):
+        return start + (np.int64(arg) / 2.0)

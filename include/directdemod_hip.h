@@ -436,7 +436,8 @@ int dd_afsk_frames_pack(const int8_t* bits, const int8_t* marks, int64_t nbits, 
  * dd_meteor_mix -- out[k] = complex64(x[k] * (cos th, sin th)), th = (w * k) * inv_fs, w = -2 pi f: the reference's offsetFreq
  *     arithmetic in float64; x = raw u8 pairs - 127.5 (raw_u8) or complex64 (c64), exactly one of them given.
  * dd_meteor_walk -- the Gardner / agc / costas walk over x[n] (complex128, absolute sample index base + j), state in *state
- *     (DDMeteorState, carried from chunk to chunk), params_host = DDMeteorParams (7 doubles, then the 256-entry tanh table).
+ *     (DDMeteorState, carried from chunk to chunk), params_host = DDMeteorParams (7 doubles, then the 256-entry tanh table); both
+ *     structs and the walk's body, which dd_funcube_walk shares, are in csrc/dd_symbol_walk.h.
  *     Symbol k (the walk's k-th A sample) writes bidx[k], aidx[k] (sample indices), agc[k] (agc output of A), ph[k] (the costas
  *     phasor active after the step), sym[k] (corrected symbol), pf[k] = (phase, freq) after the step; k >= cap sets the
  *     state's overflow flag instead.

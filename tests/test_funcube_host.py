@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import _funcube
+from _symbolwalk import skip as _skip
 from directdemod_amd import bpsk
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -83,19 +84,6 @@ def test_block_correlation_matches_numpy(rep, L):
         got = bpsk.correlate_same_blocks(buf, t, rep)
         assert len(ref) == L and np.array_equal(got, ref)
         assert int(np.argmax(np.abs(got))) == int(np.argmax(np.abs(ref)))
-
-
-def _skip(t, T, room):
-    """dd_met_skip (dd_meteor.h): how many plain timing += 1 samples the walk takes at once"""
-    _, e = math.frexp(t)
-    U2 = math.ldexp(1.0, e + 1)
-    est = min(T - t, U2 - 1.0 - t)
-    m = 0 if est <= 0 else int(min(math.ceil(est), room))
-    while m > 0 and not (t + (m - 1) < T and t + m < U2):
-        m -= 1
-    while m < room and t + m < T and t + (m + 1) < U2:
-        m += 1
-    return m
 
 
 def test_timing_jump_equals_single_steps_at_funcube_period():

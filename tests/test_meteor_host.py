@@ -1,13 +1,13 @@
 """Meteor-M2 sync detection, host side: the synthesised recordings' hashes, lim / limBin, the sync patterns and templates, the
 block-sum correlation against np.correlate, the MINSYNC gating scan against a direct restatement of the reference's loop, and the
 MAXSYNC buffer model against the buffers the reference built (tests/golden/meteor_*.npz, tools/gen_golden.py --meteor)."""
-import math
 import os
 
 import numpy as np
 import pytest
 
 import _meteor
+from _symbolwalk import skip as _skip
 from directdemod_amd import qpsk
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -127,19 +127,6 @@ def test_maxsync_buffer_model_reproduces_reference(name):
         assert start == int(g["buf_start"][i]) and tm == int(g["template"][i])
         assert start + g["argmax"][i] / 2.0 == g["maxsync"][i]
     assert list(g["maxsync"][1:]) == list(g["syncs"])
-
-
-def _skip(t, T, room):
-    """dd_met_skip (dd_meteor.h): how many plain timing += 1 samples the walk takes at once"""
-    _, e = math.frexp(t)
-    U2 = math.ldexp(1.0, e + 1)
-    est = min(T - t, U2 - 1.0 - t)
-    m = 0 if est <= 0 else int(min(math.ceil(est), room))
-    while m > 0 and not (t + (m - 1) < T and t + m < U2):
-        m -= 1
-    while m < room and t + m < T and t + (m + 1) < U2:
-        m += 1
-    return m
 
 
 def test_timing_jump_equals_single_steps():

@@ -2,14 +2,18 @@
 """
 Is the gfx950 device code of two source trees the same?  For a refactor that must not touch a kernel.
 
-    python tools/compare_device_code.py <tree_a> <tree_b>        (a tree: a checkout of this repository; e.g. `git worktree add`)
+    python tools/compare_device_code.py [--diff] <tree_a> <tree_b>   (a tree: a checkout of this repository; e.g. `git worktree add`)
 
 Every translation unit of __graft_entry__.UNITS is compiled to assembly, device side only, with the unit's own flags; the
 kernels (symbols with an `amdhsa_kernel` descriptor) are compared one by one: the instruction stream from the kernel's label to
 its `.Lfunc_end` (the kernel descriptor included), and the kernel's entry in the `amdgpu_metadata` note (VGPR / SGPR / AGPR counts, LDS, scratch, kernarg size,
 arguments).  Local label numbers, comments and blank lines are normalised away.  Prints one line per unit and the names of the
-kernels that differ or exist on one side only; exit status 0 when every kernel of every unit is identical.
+kernels that differ or exist on one side only; exit status 0 when every kernel of every unit is identical.  A kernel whose body
+differs is classified: whether the metadata entry, the number of instructions and the multiset of opcodes are the same (then only
+register numbers, operand order or the order of instructions moved); --diff adds the unified diff of the two normalised bodies.
 """
+import collections
+import difflib
 import importlib.util
 import os
 import re
@@ -70,10 +74,24 @@ def _kernels(text):
     return {k: (body[k], meta.get(k, [])) for k in names}
 
 
+def _opcodes(body):
+    """the instructions' opcodes: labels, directives and the kernel descriptor left out"""
+    return [ln.split()[0] for ln in body if ln.startswith(("\t", " ")) and not ln.split()[0].startswith(".")]
+
+
+def _classify(a, b):
+    oa, ob = _opcodes(a[0]), _opcodes(b[0])
+    return "metadata %s, %d / %d instructions, opcode multiset %s" % (
+        "identical" if a[1] == b[1] else "DIFFERS", len(oa), len(ob),
+        "identical" if collections.Counter(oa) == collections.Counter(ob) else "DIFFERS")
+
+
 def main():
-    if len(sys.argv) != 3:
+    show = "--diff" in sys.argv
+    args = [a for a in sys.argv[1:] if a != "--diff"]
+    if len(args) != 2:
         sys.exit(__doc__)
-    trees = [os.path.abspath(t) for t in sys.argv[1:]]
+    trees = [os.path.abspath(t) for t in args]
     entries = [_entry(t) for t in trees]
     units = sorted(set(entries[0].UNITS) | set(entries[1].UNITS))
     total = same = 0
@@ -92,6 +110,10 @@ def main():
                 why = "only in " + trees[0 if k in ks[0] else 1] if (k in ks[0]) != (k in ks[1]) else \
                       ("body" if ks[0][k][0] != ks[1][k][0] else "metadata")
                 print("    DIFFERS (%s): %s" % (why, k))
+                if why == "body":
+                    print("        " + _classify(ks[0][k], ks[1][k]))
+                    if show:
+                        print("\n".join(difflib.unified_diff(ks[0][k][0], ks[1][k][0], "a/" + k, "b/" + k, lineterm="", n=1)))
                 bad.append(k)
     print("total: %d units, %d kernels, %d identical, %d differing" % (len(units), total, same, len(bad)))
     return 1 if bad else 0
