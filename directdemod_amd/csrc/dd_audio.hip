@@ -74,7 +74,8 @@ struct DDSyncOnExit {
 // ---------------------------------------------------------------- own float64 cyclic convolution of length 2^17 / 2^18 (dd_hconv_kernels.h)
 #include "dd_hconv_kernels.h"
 static std::mutex g_hc_mu;
-static double2* g_hc_tab[64] = {nullptr};                        // device -> W_512^j (512) | W_{2^18}^j (512) | W_{2^17}^j (256)
+// device -> W_512^j (512) | W_{2^18}^j (512) | W_{2^17}^j (256).  On the heap, never deleted: nothing is freed at exit
+static DDDevBuf<double2>* const g_hc_tab = new DDDevBuf<double2>[64];
 static bool hc_length_ok(int64_t M) { return M == ((int64_t)1 << 17) || M == ((int64_t)1 << 18); }
 // lg: 9 (M = 2^18) or 8 (M = 2^17)
 static int hc_tables(int lg, const double2** TA, const double2** TB) {
@@ -90,11 +91,11 @@ static int hc_tables(int lg, const double2** TA, const double2** TB) {
             h[DD_HC_N + j] = make_double2((double)cosl(tp * j / 262144.0L), (double)-sinl(tp * j / 262144.0L));
         }
         for (int j = 0; j < 256; ++j) h[2 * DD_HC_N + j] = make_double2((double)cosl(tp * j / 131072.0L), (double)-sinl(tp * j / 131072.0L));
-        double2* d = nullptr;
-        DD_HIP_CHECK(hipMalloc((void**)&d, sizeof(double2) * h.size()));
+        DDDevBuf<double2> d;                                     // (the slot takes it once it is filled)
+        DD_HIP_CHECK(d.alloc(h.size()));
         hipError_t e = hipMemcpy(d, h.data(), sizeof(double2) * h.size(), hipMemcpyHostToDevice);
-        if (e != hipSuccess) { (void)hipFree(d); dd_set_error("twiddle table upload: %s", hipGetErrorString(e)); return DD_ERR_HIP; }
-        g_hc_tab[dev] = d;
+        if (e != hipSuccess) { dd_set_error("twiddle table upload: %s", hipGetErrorString(e)); return DD_ERR_HIP; }
+        g_hc_tab[dev] = std::move(d);
     }
     *TA = g_hc_tab[dev];
     *TB = g_hc_tab[dev] + (lg == 9 ? DD_HC_N : 2 * DD_HC_N);

@@ -32,10 +32,10 @@ __global__ void __launch_bounds__(256) k_scale_f64(double* __restrict__ y, int64
 struct dd_rpoly {
     int up, down, ntaps, q;          // q = inputs an output can reach back: ceil(ntaps / up)
     int64_t npr;
-    double* taps;                    // device, ntaps
-    double* hist[2];                 // device, q each (oldest first), ping-pong
-    int hpar, nh;                    // valid history samples
-    int64_t n_in, j_next;            // inputs consumed, next output index
+    DDDevBuf<double> taps;           // device, ntaps
+    DDDevBuf<double> hist[2];        // device, q each (oldest first), ping-pong
+    int hpar = 0, nh = 0;            // valid history samples
+    int64_t n_in = 0, j_next = 0;    // inputs consumed, next output index
 };
 
 __global__ void __launch_bounds__(256) k_rpoly(const double* __restrict__ in, int64_t n, int64_t a, const double* __restrict__ hist, int nh,
@@ -69,14 +69,11 @@ extern "C" int dd_rpoly_create(dd_rpoly** h, const double* taps_host, int ntaps,
     dd_rpoly* r = new dd_rpoly();
     r->up = up; r->down = down; r->ntaps = ntaps; r->npr = n_pre_remove;
     r->q = (ntaps + up - 1) / up;
-    r->taps = nullptr; r->hist[0] = r->hist[1] = nullptr;
-    r->hpar = 0; r->nh = 0; r->n_in = 0; r->j_next = 0;
-    hipError_t e = hipMalloc((void**)&r->taps, sizeof(double) * ntaps);
+    hipError_t e = r->taps.alloc(ntaps);
     if (e == hipSuccess) e = hipMemcpy(r->taps, taps_host, sizeof(double) * ntaps, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc((void**)&r->hist[0], sizeof(double) * (r->q > 0 ? r->q : 1));
-    if (e == hipSuccess) e = hipMalloc((void**)&r->hist[1], sizeof(double) * (r->q > 0 ? r->q : 1));
+    if (e == hipSuccess) e = r->hist[0].alloc(r->q > 0 ? r->q : 1);
+    if (e == hipSuccess) e = r->hist[1].alloc(r->q > 0 ? r->q : 1);
     if (e != hipSuccess) {
-        (void)hipFree(r->taps); (void)hipFree(r->hist[0]); (void)hipFree(r->hist[1]);
         delete r;
         dd_set_error("dd_rpoly_create: %s", hipGetErrorString(e));
         return e == hipErrorNoDevice ? DD_ERR_NODEVICE : DD_ERR_HIP;
@@ -85,7 +82,7 @@ extern "C" int dd_rpoly_create(dd_rpoly** h, const double* taps_host, int ntaps,
     return DD_OK;
 }
 extern "C" int dd_rpoly_destroy(dd_rpoly* r) {
-    if (r) { (void)hipFree(r->taps); (void)hipFree(r->hist[0]); (void)hipFree(r->hist[1]); delete r; }
+    delete r;
     return DD_OK;
 }
 extern "C" int dd_rpoly_reset(dd_rpoly* r) {
@@ -111,7 +108,7 @@ extern "C" int dd_rpoly_process(dd_rpoly* r, const double* in, int64_t n, int fl
     if (n_out) *n_out = cnt;
     if (cnt > 0) {
         DD_REQUIRE(out, "out");
-        hipLaunchKernelGGL(k_rpoly, dim3(grid1(cnt)), dim3(256), 0, s, in, n, r->n_in, r->hist[r->hpar], r->nh, r->taps, r->ntaps,
+        hipLaunchKernelGGL(k_rpoly, dim3(grid1(cnt)), dim3(256), 0, s, in, n, r->n_in, r->hist[r->hpar].get(), r->nh, r->taps.get(), r->ntaps,
                            r->up, r->down, r->npr, r->j_next, cnt, out);
         DD_LAUNCH_CHECK();
         r->j_next += cnt;
@@ -119,7 +116,7 @@ extern "C" int dd_rpoly_process(dd_rpoly* r, const double* in, int64_t n, int fl
     if (n > 0) {
         const int64_t have = (int64_t)r->nh + n;
         const int nh_new = (int)(have < r->q ? have : r->q);
-        hipLaunchKernelGGL(k_rpoly_hist, dim3((nh_new + 255) / 256), dim3(256), 0, s, in, n, r->hist[r->hpar], r->nh, r->hist[r->hpar ^ 1], nh_new);
+        hipLaunchKernelGGL(k_rpoly_hist, dim3((nh_new + 255) / 256), dim3(256), 0, s, in, n, r->hist[r->hpar].get(), r->nh, r->hist[r->hpar ^ 1].get(), nh_new);
         DD_LAUNCH_CHECK();
         r->hpar ^= 1;
         r->nh = nh_new;
@@ -149,20 +146,14 @@ struct DDCztKey {
         return L < o.L;
     }
 };
-struct DDCztTab { double2* w; double2* bspec; double2* bspec_p; };     // bspec_p: bspec / L in the row-pass order of dd_hconv_kernels.h (L = 2^17, 2^18), else null
+struct DDCztTab { DDDevBuf<double2> w, bspec, bspec_p; };     // bspec_p: bspec / L in the row-pass order of dd_hconv_kernels.h (L = 2^17, 2^18), else empty
 static std::mutex g_czt_mu;
-static std::map<DDCztKey, DDCztTab> g_czt;
+static std::map<DDCztKey, DDCztTab>& g_czt = *new std::map<DDCztKey, DDCztTab>();     // (on the heap, never deleted: nothing is freed at exit)
 static void czt_forget_stream(int dev, hipStream_t s) {
     std::lock_guard<std::mutex> lk(g_czt_mu);
     for (auto it = g_czt.begin(); it != g_czt.end();) {
-        if (it->first.dev == dev && it->first.s == s) {
-            (void)hipFree(it->second.w);
-            (void)hipFree(it->second.bspec);
-            if (it->second.bspec_p) (void)hipFree(it->second.bspec_p);
-            it = g_czt.erase(it);
-        } else {
-            ++it;
-        }
+        if (it->first.dev == dev && it->first.s == s) it = g_czt.erase(it);
+        else ++it;
     }
 }
 
@@ -200,7 +191,8 @@ static bool czt_wanted(int64_t n, int64_t num) {
     return largest_prime_factor(n) > 17 && 4 * (num / 2 + 1) <= n;
 }
 
-static int czt_tables(int64_t n, int64_t K, int64_t L, hipStream_t s, DDCztTab* out) {
+// *out: the cache's entry, which stays where it is until its stream is forgotten
+static int czt_tables(int64_t n, int64_t K, int64_t L, hipStream_t s, const DDCztTab** out) {
     int dev = 0;
     DD_HIP_CHECK(hipGetDevice(&dev));
     std::lock_guard<std::mutex> lk(g_czt_mu);
@@ -210,28 +202,25 @@ static int czt_tables(int64_t n, int64_t K, int64_t L, hipStream_t s, DDCztTab* 
         // a chunk loop has one or two lengths.  Tables are never freed (another thread may be using them): past 64 of them the
         // caller takes the library's own transform instead
         if (g_czt.size() >= 64) return 1;
-        DDCztTab t{nullptr, nullptr, nullptr};
-        DD_HIP_CHECK(hipMalloc((void**)&t.w, sizeof(double2) * (size_t)n));
-        hipError_t e = hipMalloc((void**)&t.bspec, sizeof(double2) * (size_t)L);
-        if (e != hipSuccess) { (void)hipFree(t.w); DD_HIP_CHECK(e); }
+        DDCztTab t;                                      // (local: an early return frees what it holds; the cache sees it complete)
+        DD_HIP_CHECK(t.w.alloc((size_t)n));
+        DD_HIP_CHECK(t.bspec.alloc((size_t)L));
         hipfftHandle pl;
         int rc = get_plan(&pl, HIPFFT_Z2Z, L, 1, s);
-        if (rc != DD_OK) { (void)hipFree(t.w); (void)hipFree(t.bspec); return rc; }
-        hipLaunchKernelGGL(k_czt_tables, dim3(grid1(n > L ? n : L)), dim3(256), 0, s, t.w, t.bspec, n, K, L);
-        if (hipfftExecZ2Z(pl, (hipfftDoubleComplex*)t.bspec, (hipfftDoubleComplex*)t.bspec, HIPFFT_FORWARD) != HIPFFT_SUCCESS) {
-            (void)hipFree(t.w); (void)hipFree(t.bspec);
+        if (rc != DD_OK) return rc;
+        hipLaunchKernelGGL(k_czt_tables, dim3(grid1(n > L ? n : L)), dim3(256), 0, s, t.w.get(), t.bspec.get(), n, K, L);
+        if (hipfftExecZ2Z(pl, (hipfftDoubleComplex*)t.bspec.get(), (hipfftDoubleComplex*)t.bspec.get(), HIPFFT_FORWARD) != HIPFFT_SUCCESS) {
             dd_set_error("hipfft exec failed (chirp spectrum)");
             return DD_ERR_HIP;
         }
         if (hc_length_ok(L)) {
-            e = hipMalloc((void**)&t.bspec_p, sizeof(double2) * (size_t)L);
-            if (e != hipSuccess) { (void)hipFree(t.w); (void)hipFree(t.bspec); DD_HIP_CHECK(e); }
-            if (L == ((int64_t)1 << 18)) hipLaunchKernelGGL(k_hc_perm<9>, dim3((unsigned)(L / 256)), dim3(256), 0, s, t.bspec, t.bspec_p, 0, 1.0 / (double)L);
-            else hipLaunchKernelGGL(k_hc_perm<8>, dim3((unsigned)(L / 256)), dim3(256), 0, s, t.bspec, t.bspec_p, 0, 1.0 / (double)L);
+            DD_HIP_CHECK(t.bspec_p.alloc((size_t)L));
+            if (L == ((int64_t)1 << 18)) hipLaunchKernelGGL(k_hc_perm<9>, dim3((unsigned)(L / 256)), dim3(256), 0, s, t.bspec.get(), t.bspec_p.get(), 0, 1.0 / (double)L);
+            else hipLaunchKernelGGL(k_hc_perm<8>, dim3((unsigned)(L / 256)), dim3(256), 0, s, t.bspec.get(), t.bspec_p.get(), 0, 1.0 / (double)L);
         }
-        it = g_czt.emplace(key, t).first;
+        it = g_czt.emplace(key, std::move(t)).first;
     }
-    *out = it->second;
+    *out = &it->second;
     return DD_OK;
 }
 
@@ -334,7 +323,7 @@ static int resample_czt_batch(const void* in, int in_is_f32, const int64_t* in_o
     const bool own = hc_length_ok(L) && !(oenv && atoi(oenv) == 0);
     if (!own && L >= 4 && 3 * (L / 4) >= nmax + K - 1) L = 3 * (L / 4);
     for (int j : idx_all) {                                  // every table first: 1 = not taken, nothing enqueued yet
-        DDCztTab t;
+        const DDCztTab* t;
         const int rc = czt_tables(n_host[j], K, L, s, &t);
         if (rc != DD_OK) return rc;
     }
@@ -344,10 +333,10 @@ static int resample_czt_batch(const void* in, int in_is_f32, const int64_t* in_o
         memset(&jobs, 0, sizeof(jobs));
         for (int b = 0; b < B; ++b) {
             const int j = idx_all[at + b];
-            DDCztTab t;
+            const DDCztTab* t;
             int rc = czt_tables(n_host[j], K, L, s, &t);
             if (rc != DD_OK) return rc;
-            jobs.j[b] = DDCztJob{in_off[j], out_off[j], n_host[j], t.w, own ? t.bspec_p : t.bspec, 1.0 / (double)n_host[j]};
+            jobs.j[b] = DDCztJob{in_off[j], out_off[j], n_host[j], t->w, own ? t->bspec_p.get() : t->bspec.get(), 1.0 / (double)n_host[j]};
         }
         hipfftHandle pz = nullptr, pb;
         int rc = own ? DD_OK : get_plan(&pz, HIPFFT_Z2Z, L, B, s);

@@ -306,7 +306,8 @@ __global__ void __launch_bounds__(256) k_env_hypot(const double* __restrict__ XR
     env[(int64_t)blockIdx.y * n + i] = hypot(XR[(int64_t)blockIdx.y * M + i], YR[(int64_t)blockIdx.y * M + i]);
 }
 
-static std::map<std::pair<int, int64_t>, double2*> g_hilb;      // (device, N) -> spectrum of the padded kernel / M
+// (device, N) -> spectrum of the padded kernel / M.  On the heap, never deleted: nothing is freed at exit
+static std::map<std::pair<int, int64_t>, DDDevBuf<double2>>& g_hilb = *new std::map<std::pair<int, int64_t>, DDDevBuf<double2>>();
 static std::vector<std::pair<int, int64_t>> g_hilb_order;
 // sin(pi num / den) for integers num >= 0, den > 0: the argument is reduced to [0, pi/2] exactly in integers first
 static double dd_sinpi_frac(int64_t num, int64_t den) {
@@ -376,25 +377,26 @@ static void kernel_spectrum_host(const std::vector<double>& img, int64_t M, std:
     }
 }
 // device part: one allocation, one copy
-static int kernel_spectrum_put(const std::vector<double2>& h, double2** out, hipStream_t s) {
-    double2* HH = nullptr;
-    DD_HIP_CHECK(hipMalloc((void**)&HH, sizeof(double2) * h.size()));
+static int kernel_spectrum_put(const std::vector<double2>& h, DDDevBuf<double2>* out, hipStream_t s) {
+    DDDevBuf<double2> HH;
+    DD_HIP_CHECK(HH.alloc(h.size()));
     hipError_t e = hipMemcpyAsync(HH, h.data(), sizeof(double2) * h.size(), hipMemcpyHostToDevice, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);                          // (the staging vector dies with the caller)
-    if (e != hipSuccess) { (void)hipFree(HH); dd_set_error("Hilbert kernel spectrum: %s", hipGetErrorString(e)); return DD_ERR_HIP; }
-    *out = HH;
+    if (e != hipSuccess) { dd_set_error("Hilbert kernel spectrum: %s", hipGetErrorString(e)); return DD_ERR_HIP; }
+    *out = std::move(HH);
     return DD_OK;
 }
-static void hilb_cache_put(std::pair<int, int64_t> key, double2* HH) {
+// the cache takes the uploaded spectrum over; returns its device address
+static double2* hilb_cache_put(std::pair<int, int64_t> key, DDDevBuf<double2>& HH) {
     // (one spectrum per length: up to 8 MB each; a process that walks through recordings of many different lengths keeps the
     // eight most recently built -- the callers hold g_sync_mu and leave nothing in flight when they return (DDSyncOnExit))
     g_hilb_order.push_back(key);
     while (g_hilb_order.size() > 8) {
         auto old = g_hilb.find(g_hilb_order.front());
-        if (old != g_hilb.end()) { (void)hipDeviceSynchronize(); (void)hipFree(old->second); g_hilb.erase(old); }      // (dd_am_envelope_f64 returns with its kernels in flight)
+        if (old != g_hilb.end()) { (void)hipDeviceSynchronize(); g_hilb.erase(old); }      // (dd_am_envelope_f64 returns with its kernels in flight)
         g_hilb_order.erase(g_hilb_order.begin());
     }
-    g_hilb[key] = HH;
+    return (g_hilb[key] = std::move(HH)).get();
 }
 // The spectra on the HOST, kept for the life of the process (at most eight, 3-8 MB each).  Two reasons: dd_noaa_prepare builds them ahead
 // without a device call (its thread runs beside the runtime's first copy and the recording's upload; the call that needs one uploads it,
@@ -448,11 +450,10 @@ static int hilbert_kernel_spectrum(int64_t n, int64_t M, const double2** out, hi
     std::vector<double2> h;
     const std::vector<double2>* hp = hilb_host_find(key);
     if (!hp) { hilbert_kernel_host(n, M, h); hp = hilb_host_keep(key, h); }
-    double2* HH = nullptr;
+    DDDevBuf<double2> HH;
     const int rc = kernel_spectrum_put(hp ? *hp : h, &HH, s);
     if (rc != DD_OK) return rc;
-    hilb_cache_put(key, HH);
-    *out = HH;
+    *out = hilb_cache_put(key, HH);
     return DD_OK;
 }
 
@@ -486,11 +487,10 @@ static int hilbert_split_spectrum(int64_t N, int64_t M, const double2** out_perm
     std::vector<double2> h;
     const std::vector<double2>* hp = hilb_host_find(key);
     if (!hp) { hilbert_split_host(N, M, h); hp = hilb_host_keep(key, h); }
-    double2* HH = nullptr;
+    DDDevBuf<double2> HH;
     const int rc = kernel_spectrum_put(hp ? *hp : h, &HH, s);
     if (rc != DD_OK) return rc;
-    hilb_cache_put(key, HH);
-    *out_perm = HH + (M / 2 + 1);
+    *out_perm = hilb_cache_put(key, HH) + (M / 2 + 1);
     return DD_OK;
 }
 
@@ -639,13 +639,13 @@ extern "C" int dd_debug_sync_envelope(const void* X_dev, int64_t L, int nwin, in
     if (rc != DD_OK) return rc;
     const float2* X = (const float2*)X_dev;
     const int pairs = (nwin + 1) / 2;
-    char* buf = nullptr;
+    DDDevBuf<char> buf;
     const size_t bW = sizeof(double2) * (size_t)pairs * M, bSP = sizeof(double2) * (size_t)nwin * nb, bYR = sizeof(double) * (size_t)nwin * M;
-    DD_HIP_CHECK(hipMalloc((void**)&buf, bW + (route ? bSP + bYR : 0)));
+    DD_HIP_CHECK(buf.alloc(bW + (route ? bSP + bYR : 0)));
     if (route == 0) {
-        rc = hc_envelope(M, X, L, nwin, HH + nb, (double2*)buf, env_dev, s);
+        rc = hc_envelope(M, X, L, nwin, HH + nb, (double2*)buf.get(), env_dev, s);
     } else {
-        double* XR = (double*)buf;
+        double* XR = (double*)buf.get();
         double2* SP = (double2*)(buf + bW);
         double* YR = (double*)(buf + bW + bSP);
         hipfftHandle pf, pb;
@@ -660,8 +660,7 @@ extern "C" int dd_debug_sync_envelope(const void* X_dev, int64_t L, int nwin, in
             if (r1 != HIPFFT_SUCCESS || r2 != HIPFFT_SUCCESS) { dd_set_error("hipfft exec failed (%d, %d)", (int)r1, (int)r2); rc = DD_ERR_HIP; }
         }
     }
-    hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(s);
-    (void)hipFree(buf);
+    hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(s);         // (before buf is freed: every return is behind it)
     if (rc != DD_OK) return rc;
     if (e1 != hipSuccess || e2 != hipSuccess) { dd_set_error("dd_debug_sync_envelope: %s", hipGetErrorString(e1 != hipSuccess ? e1 : e2)); return DD_ERR_HIP; }
     return DD_OK;

@@ -4,39 +4,35 @@
 // Internal; not a stand-alone header.
 // grow-only scratch per device for the audio-rate entry points' intermediates (no allocation in the steady state:
 // a hipMalloc/hipFree pair costs 50-100 us, a dozen of them were half of a correlate + peak-pick call)
-static void* g_sync_scratch[64] = {nullptr};
-static size_t g_sync_scratch_bytes[64] = {0};
+// ... and pinned host staging per device for the entry points' one copy back (grow-only; callers hold g_sync_mu).
+// One pair per device ordinal, on the heap and never deleted: nothing is freed at exit
+struct DDSyncBufs {
+    DDDevBuf<char> scratch;
+    DDPinnedBuf<char> pinned;
+};
+static DDSyncBufs* const g_sync_bufs = new DDSyncBufs[64];
 
-static int sync_scratch(size_t bytes, char** out) {
+static int sync_bufs(DDSyncBufs** out) {
     int dev = 0;
     DD_HIP_CHECK(hipGetDevice(&dev));
     DD_REQUIRE(dev >= 0 && dev < 64, "device index");
-    if (g_sync_scratch_bytes[dev] < bytes) {
-        if (g_sync_scratch[dev]) DD_HIP_CHECK(hipFree(g_sync_scratch[dev]));
-        g_sync_scratch[dev] = nullptr;
-        g_sync_scratch_bytes[dev] = 0;
-        DD_HIP_CHECK(hipMalloc(&g_sync_scratch[dev], bytes));
-        g_sync_scratch_bytes[dev] = bytes;
-    }
-    *out = (char*)g_sync_scratch[dev];
+    *out = &g_sync_bufs[dev];
     return DD_OK;
 }
-
-// pinned host staging per device for the entry points' one copy back (grow-only; callers hold g_sync_mu)
-static void* g_pin[64] = {nullptr};
-static size_t g_pin_bytes[64] = {0};
+static int sync_scratch(size_t bytes, char** out) {
+    DDSyncBufs* b = nullptr;
+    const int rc = sync_bufs(&b);
+    if (rc != DD_OK) return rc;
+    DD_HIP_CHECK(b->scratch.grow(bytes));
+    *out = b->scratch;
+    return DD_OK;
+}
 static int sync_pinned(size_t bytes, char** out) {
-    int dev = 0;
-    DD_HIP_CHECK(hipGetDevice(&dev));
-    DD_REQUIRE(dev >= 0 && dev < 64, "device index");
-    if (g_pin_bytes[dev] < bytes) {
-        if (g_pin[dev]) DD_HIP_CHECK(hipHostFree(g_pin[dev]));
-        g_pin[dev] = nullptr;
-        g_pin_bytes[dev] = 0;
-        DD_HIP_CHECK(hipHostMalloc(&g_pin[dev], bytes, hipHostMallocDefault));
-        g_pin_bytes[dev] = bytes;
-    }
-    *out = (char*)g_pin[dev];
+    DDSyncBufs* b = nullptr;
+    const int rc = sync_bufs(&b);
+    if (rc != DD_OK) return rc;
+    DD_HIP_CHECK(b->pinned.grow(bytes, hipHostMallocDefault));
+    *out = b->pinned;
     return DD_OK;
 }
 

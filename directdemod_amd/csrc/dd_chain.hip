@@ -131,10 +131,10 @@ extern "C" int dd_debug_seam(int withhold_chunk, int spin_log2) {
 // early; the word is final once its stream has been synchronised, and every later fused launch and dd_stream_sync looks again.
 static int seam_look(dd_fir* f) {
     if (!f->seam_pending || !f->seam_err_host) return DD_OK;
-    const unsigned n = *reinterpret_cast<volatile unsigned int*>(f->seam_err_host);
+    const unsigned n = *reinterpret_cast<volatile unsigned int*>(f->seam_err_host.get());
     if (n == 0) return DD_OK;
     f->state_invalid = 1;          // (the faulty launch also committed its carried state: nothing may continue from it)
-    *reinterpret_cast<volatile unsigned int*>(f->seam_err_host) = 0;
+    *reinterpret_cast<volatile unsigned int*>(f->seam_err_host.get()) = 0;
     dd_set_error("chunk-list launch: %u in-launch hand-over wait(s) of the carried FIR / FM state timed out; the outputs of that "
                  "dd_*_process_chunks call are invalid (run the chunks one by one, or raise the bound with dd_debug_seam)", n);
     return DD_ERR_TIMEOUT;
@@ -153,8 +153,8 @@ static void seam_forget(dd_fir* f) {
     std::lock_guard<std::mutex> lk(g_seam_mu);
     for (size_t i = 0; i < g_seam_pending.size(); ++i)
         if (g_seam_pending[i] == f) { g_seam_pending.erase(g_seam_pending.begin() + i); break; }
-    if (f->seam_err_host) { (void)hipDeviceSynchronize(); (void)hipHostFree(f->seam_err_host); }      // (no launch may still count into it)
-    f->seam_err_host = nullptr; f->seam_err = nullptr; f->seam_pending = 0;
+    if (f->seam_err_host) { (void)hipDeviceSynchronize(); f->seam_err_host.reset(); }      // (no launch may still count into it)
+    f->seam_err = nullptr; f->seam_pending = 0;
 }
 // May a launch go on from this filter's carried state?  A chunk-list launch whose in-launch hand-over timed out is reported
 // here (by every fused launch, not only by dd_stream_sync), and the state that launch committed is refused until the filter
@@ -188,17 +188,13 @@ extern "C" int dd_fir_create(dd_fir** h, const double* taps, int ntaps) {
     const int len = niter * R + 6 * R;                    // (k_chain_decim_w reads whole trips of 32 taps: zeros behind the last one)
     std::vector<float> g(len, 0.f);
     for (int j = 0; j < K; ++j) g[j + R - 1] = (float)taps[K - 1 - j];
-    const size_t tb = sizeof(float2) * (size_t)(K > 1 ? K - 1 : 1);
-    hipError_t e = hipMalloc((void**)&f->taps_rev, len * sizeof(float));
+    const int nc = K > 1 ? K - 1 : 1;
+    hipError_t e = f->taps_rev.alloc(len);
     if (e == hipSuccess) e = hipMemcpy(f->taps_rev, g.data(), len * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc((void**)&f->tail[0], tb);
-    if (e == hipSuccess) e = hipMalloc((void**)&f->tail[1], tb);
-    if (e == hipSuccess) e = hipMalloc((void**)&f->tail_const[0], tb);
-    if (e == hipSuccess) e = hipMalloc((void**)&f->tail_const[1], tb);
+    for (int i = 0; i < 4 && e == hipSuccess; ++i) e = (i < 2 ? f->tail[i] : f->tail_const[i - 2]).alloc(nc);
     if (e == hipSuccess) {
-        const int nc = K > 1 ? K - 1 : 1;
-        hipLaunchKernelGGL(k_fill_c64, dim3((nc + 255) / 256), dim3(256), 0, 0, f->tail_const[0], nc, 0.f, 0.f);
-        hipLaunchKernelGGL(k_fill_c64, dim3((nc + 255) / 256), dim3(256), 0, 0, f->tail_const[1], nc, 1.f, 0.f);
+        hipLaunchKernelGGL(k_fill_c64, dim3((nc + 255) / 256), dim3(256), 0, 0, f->tail_const[0].get(), nc, 0.f, 0.f);
+        hipLaunchKernelGGL(k_fill_c64, dim3((nc + 255) / 256), dim3(256), 0, 0, f->tail_const[1].get(), nc, 1.f, 0.f);
         e = hipGetLastError();
     }
     if (e != hipSuccess) {
@@ -222,16 +218,6 @@ extern "C" int dd_fir_destroy(dd_fir* f) {
     if (f->fft) dd_fft_destroy(f->fft);
     if (f->cos) dd_cos1k_destroy(f->cos);
     seam_forget(f);
-    (void)hipFree(f->multi);
-    (void)hipFree(f->dw_taps.dev);
-    (void)hipFree(f->taps_rev);
-    (void)hipFree(f->tail[0]);
-    (void)hipFree(f->tail[1]);
-    (void)hipFree(f->tail_const[0]);
-    (void)hipFree(f->tail_const[1]);
-    (void)hipFree(f->taps_dev);
-    (void)hipFree(f->hist[0]);
-    (void)hipFree(f->hist[1]);
     delete f;
     return DD_OK;
 }
@@ -265,7 +251,7 @@ extern "C" int dd_fir_reset(dd_fir* f, int mode, const float* hist_host, void* s
 extern "C" int dd_fm_create(dd_fm** h) {
     DD_REQUIRE(h, "h");
     dd_fm* f = new dd_fm();
-    hipError_t e = hipMalloc((void**)&f->last, 2 * sizeof(float2));
+    hipError_t e = f->last.alloc(2);
     if (e == hipSuccess) e = hipMemset(f->last, 0, 2 * sizeof(float2));
     if (e != hipSuccess) {
         delete f;
@@ -276,10 +262,7 @@ extern "C" int dd_fm_create(dd_fm** h) {
     return DD_OK;
 }
 extern "C" int dd_fm_destroy(dd_fm* h) {
-    if (h) {
-        (void)hipFree(h->last);
-        delete h;
-    }
+    delete h;
     return DD_OK;
 }
 extern "C" int dd_fm_reset(dd_fm* h) {
@@ -622,9 +605,13 @@ static int fused_chunks_one_launch(dd_fir* fir, dd_fm* fm, const void* in, void*
         spin_log2 = g_seam_spin_log2;
     }
     if (!fir->seam_err) {
-        DD_HIP_CHECK(hipHostMalloc((void**)&fir->seam_err_host, 2 * sizeof(unsigned int), hipHostMallocMapped));
-        fir->seam_err_host[0] = fir->seam_err_host[1] = 0;
-        DD_HIP_CHECK(hipHostGetDevicePointer((void**)&fir->seam_err, fir->seam_err_host, 0));
+        DDPinnedBuf<unsigned int> words;
+        unsigned int* dev = nullptr;
+        DD_HIP_CHECK(words.alloc(2, hipHostMallocMapped));
+        words[0] = words[1] = 0;
+        DD_HIP_CHECK(hipHostGetDevicePointer((void**)&dev, words, 0));
+        fir->seam_err_host = std::move(words);
+        fir->seam_err = dev;
     }
     {
         // (a chunk list whose chunks have no interior run never passes through decim_plan's persistent branch)
@@ -661,17 +648,14 @@ static int fused_chunks_one_launch(dd_fir* fir, dd_fm* fm, const void* in, void*
     const size_t o_ipre = o_seg + al(sizeof(DDSeg) * nchunks), o_epre = o_ipre + al(sizeof(int) * (nchunks + 1));
     const size_t o_tail = o_epre + al(sizeof(int) * (nchunks + 1)), o_last = o_tail + al(sizeof(float2) * (size_t)K1 * nchunks);
     const size_t total = o_last + al(sizeof(float2) * nchunks);
-    if (total > fir->multi_bytes) {
+    if (total > fir->multi.bytes()) {
         DD_HIP_CHECK(hipStreamSynchronize(s));
-        (void)hipFree(fir->multi);
-        fir->multi = nullptr;
-        fir->multi_bytes = 0;
-        DD_HIP_CHECK(hipMalloc((void**)&fir->multi, total));
-        fir->multi_bytes = total;
+        DD_HIP_CHECK(fir->multi.alloc(total));
     }
-    unsigned int* seam_flags = reinterpret_cast<unsigned int*>(fir->multi);
-    float2* seam_tail = reinterpret_cast<float2*>(fir->multi + o_tail);
-    float2* seam_last = reinterpret_cast<float2*>(fir->multi + o_last);
+    char* const multi = fir->multi;
+    unsigned int* seam_flags = reinterpret_cast<unsigned int*>(multi);
+    float2* seam_tail = reinterpret_cast<float2*>(multi + o_tail);
+    float2* seam_last = reinterpret_cast<float2*>(multi + o_last);
     std::vector<char> img(o_tail, 0);                         // (from the seam flags, which start as zeros, to the edge prefix: ONE copy)
     DDChainParams* hP = reinterpret_cast<DDChainParams*>(img.data() + o_par);
     DDSeg* hS = reinterpret_cast<DDSeg*>(img.data() + o_seg);
@@ -702,12 +686,12 @@ static int fused_chunks_one_launch(dd_fir* fir, dd_fm* fm, const void* in, void*
     }
     const int n_int = hI[nchunks], n_edge = hE[nchunks];
     if (per_cu < 1) per_cu = 1;
-    DD_HIP_CHECK(hipMemcpyAsync(fir->multi, img.data(), img.size(), hipMemcpyHostToDevice, s));      // (pageable source: staged before the call returns)
+    DD_HIP_CHECK(hipMemcpyAsync(multi, img.data(), img.size(), hipMemcpyHostToDevice, s));      // (pageable source: staged before the call returns)
     const int grid = persistent_grid(n_int, n_edge, per_cu);
-    const DDChainParams* dP = reinterpret_cast<const DDChainParams*>(fir->multi + o_par);
-    const DDSeg* dS = reinterpret_cast<const DDSeg*>(fir->multi + o_seg);
-    const int* dI = reinterpret_cast<const int*>(fir->multi + o_ipre);
-    const int* dE = reinterpret_cast<const int*>(fir->multi + o_epre);
+    const DDChainParams* dP = reinterpret_cast<const DDChainParams*>(multi + o_par);
+    const DDSeg* dS = reinterpret_cast<const DDSeg*>(multi + o_seg);
+    const int* dI = reinterpret_cast<const int*>(multi + o_ipre);
+    const int* dE = reinterpret_cast<const int*>(multi + o_epre);
     if (u8) hipLaunchKernelGGL(k_chain_decim_multi<true>, dim3(grid + n_edge), dim3(DD_DECIM_THREADS), lds_p, s, dP, dS, dI, dE, nchunks, grid);
     else hipLaunchKernelGGL(k_chain_decim_multi<false>, dim3(grid + n_edge), dim3(DD_DECIM_THREADS), lds_p, s, dP, dS, dI, dE, nchunks, grid);
     DD_LAUNCH_CHECK();
@@ -776,8 +760,7 @@ struct dd_chain {
     uint64_t cyc = 0;
     int M = 1, flags = 0;
     int64_t abs_index = 0;
-    void* scratch = nullptr;    // discarded outputs of dd_chain_prime
-    size_t scratch_bytes = 0;
+    DDDevBuf<char> scratch;     // discarded outputs of dd_chain_prime (grow-only)
 };
 
 extern "C" int dd_chain_create(dd_chain** h, const double* taps, int ntaps, uint64_t cycles_q64,
@@ -802,7 +785,6 @@ extern "C" int dd_chain_destroy(dd_chain* c) {
     if (!c) return DD_OK;
     dd_fir_destroy(c->fir);
     dd_fm_destroy(c->fm);
-    (void)hipFree(c->scratch);
     delete c;
     return DD_OK;
 }
@@ -892,15 +874,11 @@ extern "C" int dd_chain_prime(dd_chain* c, const void* halo_in, int64_t n_halo, 
     if (rc != DD_OK) return rc;
     const int64_t no = dd_chain_out_count(c, n_halo);
     const size_t ob = (size_t)(no > 0 ? no : 1) * out_elem_size(c->fm);
-    if (ob > c->scratch_bytes) {
+    if (ob > c->scratch.bytes()) {
         DD_HIP_CHECK(hipStreamSynchronize(s));
-        (void)hipFree(c->scratch);
-        c->scratch = nullptr;
-        c->scratch_bytes = 0;
-        DD_HIP_CHECK(hipMalloc(&c->scratch, ob));
-        c->scratch_bytes = ob;
+        DD_HIP_CHECK(c->scratch.alloc(ob));
     }
-    return dd_chain_process(c, halo_in, c->scratch, n_halo, nullptr, stream);
+    return dd_chain_process(c, halo_in, c->scratch.get(), n_halo, nullptr, stream);
 }
 
 // dd_code_warmup (dd_runtime.hip): the runtime loads a translation unit's code object when one of its kernels is first named

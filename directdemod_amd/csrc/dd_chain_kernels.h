@@ -10,9 +10,9 @@
 struct dd_fir {
     int K = 0;
     std::vector<double> taps;
-    float* taps_rev = nullptr;                     // device: reversed taps, zero padded (direct-form kernels)
-    float2* tail[2] = {nullptr, nullptr};          // device: K-1 past inputs (complex64), ping-pong
-    float2* tail_const[2] = {nullptr, nullptr};    // device: constant histories (all zeros / all ones) for launch-free resets
+    DDDevBuf<float> taps_rev;                      // device: reversed taps, zero padded (direct-form kernels)
+    DDDevBuf<float2> tail[2];                      // device: K-1 past inputs (complex64), ping-pong
+    DDDevBuf<float2> tail_const[2];                // device: constant histories (all zeros / all ones) for launch-free resets
     const float2* tail_override = nullptr;         // non-null: the next launch reads this history instead of tail[parity]
     int parity = 0;
     // one lazily created state per M = 1 kernel family other than the dense one (dd_chain.hip, chain_select): the f16-limb
@@ -23,20 +23,19 @@ struct dd_fir {
     void* cos = nullptr;
     int mfma_tried = 0, fft_tried = 0, cos_tried = 0;
     // float64 real path (audio rate)
-    double* taps_dev = nullptr;
-    double* hist[2] = {nullptr, nullptr};
+    DDDevBuf<double> taps_dev;
+    DDDevBuf<double> hist[2];
     int hpar = 0;
     int hist_mode = DD_HIST_ONES;
     int last_kernel = DD_KERNEL_NONE;   // DD_KERNEL_* of the last fused launch through this filter
     long long launches = 0;             // fused kernel launches through this filter (dd_fir_launch_count)
     DDDecimWTaps dw_taps;               // k_chain_decim_w's padded taps (M = 0 mod 4), lazy
-    char* multi = nullptr;              // chunk-list launches: seam flags, per-chunk parameter blocks, prefix tables, seam state (grow-only)
-    size_t multi_bytes = 0;
+    DDDevBuf<char> multi;               // chunk-list launches: seam flags, per-chunk parameter blocks, prefix tables, seam state (grow-only)
     // chunk-list launches: a hand-over wait that gives up (dd_seam_wait) counts itself, with a system-scope atomic, into word [0]
     // of two words of pinned, mapped host memory (word [1]: where dd_debug_seam sends a withheld flag).  No copy, no event: the
     // host reads the word -- every fused launch through this filter and dd_stream_sync look at it -- and it is final once the
     // launch's stream has been synchronised.
-    unsigned int* seam_err_host = nullptr;   // the two words, host address
+    DDPinnedBuf<unsigned int> seam_err_host; // the two words, host address (freed by seam_forget, behind a device synchronise)
     unsigned int* seam_err = nullptr;        // the same words, device address
     int seam_pending = 0;                    // a chunk-list launch has been made: the word is looked at until the filter is destroyed
     int state_invalid = 0;                   // a chunk-list launch through this filter timed out: the carried history and last FM sample it
@@ -45,7 +44,7 @@ struct dd_fir {
 
 // demod_fm object: carried last sample (demod_fm.py:43-49)
 struct dd_fm {
-    float2* last = nullptr; // device: [2] ping-pong
+    DDDevBuf<float2> last;  // device: [2] ping-pong
     int parity = 0;
     int has_last = 0;       // host mirror of "self.__last is not None"
 };

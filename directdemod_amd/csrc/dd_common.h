@@ -7,6 +7,7 @@
 #include <math.h>
 #include "../../include/directdemod_hip.h"
 #include "../../include/directdemod_hip_debug.h"
+#include "dd_devbuf.h"      // DDDevBuf / DDPinnedBuf: who owns device and pinned memory in the host layer
 
 void dd_set_error(const char* fmt, ...);
 int dd_seam_poll_all(void);         // (dd_chain.hip) chunk-list launches whose in-launch hand-over timed out: DD_OK or DD_ERR_TIMEOUT

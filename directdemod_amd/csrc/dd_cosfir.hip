@@ -754,8 +754,8 @@ __global__ void __launch_bounds__(64 * C1_WAVES, 2) k_chain_cos1k(const DDCos1kA
 
 // ============================================================================ host side
 struct DDCos1kState {
-    double a0, a1;
-    DDCos1kLane* lane_tab;
+    double a0 = 0.0, a1 = 0.0;
+    DDDevBuf<DDCos1kLane> lane_tab;
 };
 
 int dd_cos1k_supported(const double* taps, int K, int M, int flags) {
@@ -776,16 +776,14 @@ int dd_cos1k_create(void** st, const double* taps, int K) {
     DDCos1kState* s = new DDCos1kState();
     s->a0 = f.a[0];
     s->a1 = f.a[1];
-    s->lane_tab = nullptr;
     DDCos1kLane h[64];
     const long double phi16 = 16.0L * 2.0L * 3.14159265358979323846264338327950288L / (long double)(C1_K - 1);
     for (int l = 0; l < 64; ++l) {
         h[l].b15c = (float)cosl(phi16 * ((l & 15) + 1)); h[l].b15s = (float)sinl(phi16 * ((l & 15) + 1));
     }
-    hipError_t e = hipMalloc((void**)&s->lane_tab, sizeof(h));
+    hipError_t e = s->lane_tab.alloc(64);
     if (e == hipSuccess) e = hipMemcpy(s->lane_tab, h, sizeof(h), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
-        if (s->lane_tab) (void)hipFree(s->lane_tab);
         delete s;
         dd_set_error("dd_cos1k_create: %s", hipGetErrorString(e));
         return DD_ERR_HIP;
@@ -795,10 +793,7 @@ int dd_cos1k_create(void** st, const double* taps, int K) {
 }
 
 void dd_cos1k_destroy(void* stv) {
-    DDCos1kState* s = reinterpret_cast<DDCos1kState*>(stv);
-    if (!s) return;
-    if (s->lane_tab) (void)hipFree(s->lane_tab);
-    delete s;
+    delete reinterpret_cast<DDCos1kState*>(stv);
 }
 
 // where the row grid sits and how many rows and waves a chunk takes (host arithmetic, also reachable without a GPU: dd_debug_cos1k_plan)

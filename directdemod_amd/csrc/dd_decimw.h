@@ -6,8 +6,8 @@ struct DDChainParams;
 // kept with a filter: the taps as a PAD launch meets them (zeros over the gaps of the padded LDS image), for one (M, tap shift) at a time
 #define DD_DECIMW_TAPS_CAP 640
 struct DDDecimWTaps {
-    float* dev = nullptr;
-    int key = -1;
+    DDDevBuf<float> dev;
+    int key = -1;                        // what dev holds; -1: nothing (an upload that failed leaves it so, and the next launch uploads again)
     float host[DD_DECIMW_TAPS_CAP];      // the copy's source: lives as long as the filter (the copy is asynchronous)
 };
 // even M in [8, 64], 2 <= K <= 256, complex64 (8-byte aligned) or raw u8 (2-byte aligned) input, FM or complex64 output

@@ -1303,41 +1303,34 @@ int dd_decimw_launch(const DDChainParams& P, const float* taps_g0, const double*
     DWPlan pl;
     decimw_plan(P.abs0, P.Ld, P.K, P.M, P.off, dd_cu_count(), pl);
     const float* taps = taps_g0 - pl.e;
-    if (pl.bsum) {
-        // the taps as the matrix instruction takes them, for (M, e): [set][register g][lane 4 t + m] = h[M (4 set + m) + d], d = M - 1 + e - j the
-        // distance of block sample j = 16 g + t from the block's kept sample (0 outside the block and beyond h[K - 1]); kept with the filter
-        const int key = 0x10000 | (P.M << 1) | pl.e;
+    if (pl.bsum || pl.pad) {
+        // a small device buffer kept with the filter, rewritten in stream order when the key (kernel family, M, e) changes
         static_assert(640 <= DD_DECIMW_TAPS_CAP, "block-sum taps");
-        if (!cache->dev) DD_HIP_CHECK(hipMalloc((void**)&cache->dev, sizeof(float) * DD_DECIMW_TAPS_CAP));
-        if (cache->key != key) {
-            float* const t = cache->host;
-            for (int j = 0; j < DD_DECIMW_TAPS_CAP; ++j) t[j] = 0.f;
-            for (int j = 0; j < 80; ++j)
-                for (int i = 0; i < 8; ++i) {
-                    const int d = P.M - 1 + pl.e - j;
-                    if (d < 0 || d > P.M - 1 || P.M * i + d >= P.K) continue;
-                    t[320 * (i >> 2) + 64 * (j >> 4) + 4 * (j & 15) + (i & 3)] = (float)taps_host[P.M * i + d];
-                }
-            DD_HIP_CHECK(hipMemcpyAsync(cache->dev, t, sizeof(float) * DD_DECIMW_TAPS_CAP, hipMemcpyHostToDevice, stream));
-            cache->key = key;
-        }
-        taps = cache->dev;
-    } else if (pl.pad) {
-        // the padded taps of (M, e): a small device buffer kept with the filter, rewritten in stream order when the key changes
-        const int key = (P.M << 1) | pl.e;
-        const int cap = DD_DECIMW_TAPS_CAP;
         static_assert(256 + 1 + 2 * 32 + 2 * DW_TRIP <= DD_DECIMW_TAPS_CAP, "padded taps");
-        if (!cache->dev) DD_HIP_CHECK(hipMalloc((void**)&cache->dev, sizeof(float) * cap));
+        const int key = (pl.bsum ? 0x10000 : 0) | (P.M << 1) | pl.e;
         if (cache->key != key) {
             // (an earlier copy out of this array -- another key -- may still be queued on another stream: one caller thread and one stream per
             //  filter is the contract; on the same stream the runtime has staged pageable memory by the time the call returns)
             float* const t = cache->host;
-            for (int j = 0; j < cap; ++j) t[j] = 0.f;
-            for (int j = 0; j < P.K; ++j) {                    // g[j] = h[K-1-j] at logical window sample j + e
-                const int w = j + pl.e;
-                t[w + 2 * (w / P.M)] = (float)taps_host[P.K - 1 - j];
+            for (int j = 0; j < DD_DECIMW_TAPS_CAP; ++j) t[j] = 0.f;
+            if (pl.bsum) {
+                // the taps as the matrix instruction takes them: [set][register g][lane 4 t + m] = h[M (4 set + m) + d], d = M - 1 + e - j the
+                // distance of block sample j = 16 g + t from the block's kept sample (0 outside the block and beyond h[K - 1])
+                for (int j = 0; j < 80; ++j)
+                    for (int i = 0; i < 8; ++i) {
+                        const int d = P.M - 1 + pl.e - j;
+                        if (d < 0 || d > P.M - 1 || P.M * i + d >= P.K) continue;
+                        t[320 * (i >> 2) + 64 * (j >> 4) + 4 * (j & 15) + (i & 3)] = (float)taps_host[P.M * i + d];
+                    }
+            } else {
+                for (int j = 0; j < P.K; ++j) {                // the padded taps: g[j] = h[K-1-j] at logical window sample j + e
+                    const int w = j + pl.e;
+                    t[w + 2 * (w / P.M)] = (float)taps_host[P.K - 1 - j];
+                }
             }
-            DD_HIP_CHECK(hipMemcpyAsync(cache->dev, t, sizeof(float) * cap, hipMemcpyHostToDevice, stream));
+            DD_HIP_CHECK(cache->dev.grow(DD_DECIMW_TAPS_CAP));
+            cache->key = -1;
+            DD_HIP_CHECK(hipMemcpyAsync(cache->dev, t, sizeof(float) * DD_DECIMW_TAPS_CAP, hipMemcpyHostToDevice, stream));
             cache->key = key;
         }
         taps = cache->dev;

@@ -769,22 +769,22 @@ __global__ void __launch_bounds__(64 * F1_WAVES, 3) k_chain_fft1k(const DDChainP
 // ============================================================================ host side
 #define F1_HP_SLOTS 4
 struct DDFftState {
-    int K;
+    int K = 0;
     std::vector<double> taps;
-    float2* tw1;        // [64][16]  W1024^{t k}
-    float2* tw2;        // [4][16]   W64^{n0 k}
+    DDDevBuf<float2> tw1;       // [64][16]  W1024^{t k}
+    DDDevBuf<float2> tw2;       // [4][16]   W64^{n0 k}
     // the tap spectrum for the frequency in `cyc`, as pass 3 multiplies it ([16][64]): a ring of device tables, each with a
     // pinned staging copy and an event, so that a caller that retunes from chunk to chunk (a Doppler-tracking loop, cf.
     // decode_funcube.py:228) never stalls the stream: the new spectrum is computed on the host, copied asynchronously in
     // stream order into the NEXT slot, and a slot is only rewritten once everything that used it has finished
-    float2* hp[F1_HP_SLOTS];
-    float2* hp_host[F1_HP_SLOTS];
-    hipEvent_t hp_ev[F1_HP_SLOTS];
-    int hp_ev_set[F1_HP_SLOTS];
-    int cur;
-    uint64_t cyc;
-    int have_h;
-    int nco;
+    DDDevBuf<float2> hp[F1_HP_SLOTS];
+    DDPinnedBuf<float2> hp_host[F1_HP_SLOTS];
+    hipEvent_t hp_ev[F1_HP_SLOTS] = {};
+    int hp_ev_set[F1_HP_SLOTS] = {};
+    int cur = 0;
+    uint64_t cyc = 0;
+    int have_h = 0;
+    int nco = 0;
 };
 
 static void fft_pow2(std::vector<std::complex<double>>& v) {
@@ -818,12 +818,6 @@ int dd_fft_create(void** st, const double* taps, int K) {
     DDFftState* s = new DDFftState();
     s->K = K;
     s->taps.assign(taps, taps + K);
-    s->tw1 = s->tw2 = nullptr;
-    for (int i = 0; i < F1_HP_SLOTS; ++i) { s->hp[i] = nullptr; s->hp_host[i] = nullptr; s->hp_ev[i] = nullptr; s->hp_ev_set[i] = 0; }
-    s->cur = 0;
-    s->cyc = 0;
-    s->have_h = 0;
-    s->nco = 0;
     std::vector<float2> u1(64 * 16), u2(4 * 16);
     for (int t = 0; t < 64; ++t)
         for (int k = 0; k < 16; ++k) {
@@ -835,11 +829,11 @@ int dd_fft_create(void** st, const double* taps, int K) {
             const double ang = -2.0 * M_PI * (double)((n0 * k) % 64) / 64.0;
             u2[n0 * 16 + k] = make_float2((float)cos(ang), (float)sin(ang));
         }
-    hipError_t e = hipMalloc((void**)&s->tw1, u1.size() * sizeof(float2));
-    if (e == hipSuccess) e = hipMalloc((void**)&s->tw2, u2.size() * sizeof(float2));
+    hipError_t e = s->tw1.alloc(u1.size());
+    if (e == hipSuccess) e = s->tw2.alloc(u2.size());
     for (int i = 0; i < F1_HP_SLOTS && e == hipSuccess; ++i) {
-        e = hipMalloc((void**)&s->hp[i], 64 * 16 * sizeof(float2));
-        if (e == hipSuccess) e = hipHostMalloc((void**)&s->hp_host[i], 64 * 16 * sizeof(float2), hipHostMallocDefault);
+        e = s->hp[i].alloc(64 * 16);
+        if (e == hipSuccess) e = s->hp_host[i].alloc(64 * 16, hipHostMallocDefault);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&s->hp_ev[i], hipEventDisableTiming);
     }
     if (e == hipSuccess) e = hipMemcpy(s->tw1, u1.data(), u1.size() * sizeof(float2), hipMemcpyHostToDevice);
@@ -856,13 +850,8 @@ int dd_fft_create(void** st, const double* taps, int K) {
 void dd_fft_destroy(void* stv) {
     DDFftState* s = reinterpret_cast<DDFftState*>(stv);
     if (!s) return;
-    if (s->tw1) (void)hipFree(s->tw1);
-    if (s->tw2) (void)hipFree(s->tw2);
-    for (int i = 0; i < F1_HP_SLOTS; ++i) {
-        if (s->hp[i]) (void)hipFree(s->hp[i]);
-        if (s->hp_host[i]) (void)hipHostFree(s->hp_host[i]);
+    for (int i = 0; i < F1_HP_SLOTS; ++i)
         if (s->hp_ev[i]) (void)hipEventDestroy(s->hp_ev[i]);
-    }
     delete s;
 }
 

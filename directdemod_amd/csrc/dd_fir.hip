@@ -15,14 +15,18 @@ __global__ void k_fill_f64(double* p, int n, double v) {
 
 static int fir_f64_state(dd_fir* f, hipStream_t s) {
     if (f->taps_dev) return DD_OK;
-    DD_HIP_CHECK(hipMalloc((void**)&f->taps_dev, sizeof(double) * f->K));
-    DD_HIP_CHECK(hipMemcpy(f->taps_dev, f->taps.data(), sizeof(double) * f->K, hipMemcpyHostToDevice));
+    DDDevBuf<double> taps, h0, h1;                   // (the filter sees them once the taps are up and the history is filled)
+    DD_HIP_CHECK(taps.alloc(f->K));
+    DD_HIP_CHECK(hipMemcpy(taps, f->taps.data(), sizeof(double) * f->K, hipMemcpyHostToDevice));
     const int nh = f->K > 1 ? f->K - 1 : 1;
-    DD_HIP_CHECK(hipMalloc((void**)&f->hist[0], sizeof(double) * nh));
-    DD_HIP_CHECK(hipMalloc((void**)&f->hist[1], sizeof(double) * nh));
-    hipLaunchKernelGGL(k_fill_f64, dim3((nh + 255) / 256), dim3(256), 0, s, f->hist[0], nh,
+    DD_HIP_CHECK(h0.alloc(nh));
+    DD_HIP_CHECK(h1.alloc(nh));
+    hipLaunchKernelGGL(k_fill_f64, dim3((nh + 255) / 256), dim3(256), 0, s, h0.get(), nh,
                        f->hist_mode == DD_HIST_ONES ? 1.0 : 0.0);
     DD_LAUNCH_CHECK();
+    f->taps_dev = std::move(taps);
+    f->hist[0] = std::move(h0);
+    f->hist[1] = std::move(h1);
     return DD_OK;
 }
 
@@ -40,7 +44,7 @@ int dd_fir_reset_f64(dd_fir* f, int mode, const float* hist_host, hipStream_t s)
         DD_HIP_CHECK(hipMemcpyAsync(f->hist[f->hpar], hr.data(), sizeof(double) * nh, hipMemcpyHostToDevice, s));
         DD_HIP_CHECK(hipStreamSynchronize(s));
     } else {
-        hipLaunchKernelGGL(k_fill_f64, dim3((nh + 255) / 256), dim3(256), 0, s, f->hist[f->hpar], nh,
+        hipLaunchKernelGGL(k_fill_f64, dim3((nh + 255) / 256), dim3(256), 0, s, f->hist[f->hpar].get(), nh,
                            mode == DD_HIST_ONES ? 1.0 : 0.0);
         DD_LAUNCH_CHECK();
     }
@@ -90,19 +94,20 @@ extern "C" int dd_fir_f64(dd_fir* f, const double* in, double* out, int64_t n, i
     hipStream_t s = dd_stream(stream);
     int rc = fir_f64_state(f, s);
     if (rc != DD_OK) return rc;
+    const double* const taps = f->taps_dev;
+    double* const hist = f->hist[f->hpar];
     if (dd_ff_tiled_ok(f->K, sizeof(double)) && in != out) {
         // LDS-tiled, register-blocked form (dd_filtfilt_kernels.h), same summation order as the plain kernel
         hipLaunchKernelGGL((k_filtfilt_tile<double, 2>), dim3((unsigned)((n + DD_FF_TILE - 1) / DD_FF_TILE), 1), dim3(DD_FF_THREADS),
-                           dd_ff_lds_bytes(f->K), s, in, out, n, 0, f->taps_dev, f->K, (int64_t)0, (int64_t)0,
-                           (const double*)f->hist[f->hpar]);
+                           dd_ff_lds_bytes(f->K), s, in, out, n, 0, taps, f->K, (int64_t)0, (int64_t)0,
+                           (const double*)hist);
     } else {
-        hipLaunchKernelGGL(k_fir_f64, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, in, out, n, f->taps_dev, f->K,
-                           f->hist[f->hpar]);
+        hipLaunchKernelGGL(k_fir_f64, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, in, out, n, taps, f->K, hist);
     }
     DD_LAUNCH_CHECK();
     if (carry && f->K > 1) {
-        hipLaunchKernelGGL(k_hist_update_f64, dim3((f->K + 254) / 256), dim3(256), 0, s, in, n, f->K,
-                           f->hist[f->hpar], f->hist[f->hpar ^ 1]);
+        hipLaunchKernelGGL(k_hist_update_f64, dim3((f->K + 254) / 256), dim3(256), 0, s, in, n, f->K, hist,
+                           f->hist[f->hpar ^ 1].get());
         DD_LAUNCH_CHECK();
         f->hpar ^= 1;
     }
@@ -172,11 +177,10 @@ struct dd_iir {
     int n;
     double b[DD_IIR_MAXN], a[DD_IIR_MAXN];
     double zi[DD_IIR_MAXN];
-    double* state;          // device: 2 * (n-1) doubles (re, im)
-    double* mats;           // device: block-parallel path, [M_hi, M_lo, MG_hi, MG_lo] each IIR_S x IIR_S (see below), short blocks
-    double* mats_long;      //         the same for the long block length
-    double* scratch;        // device: block / group vectors of the block-parallel path (grow-only)
-    size_t scratch_bytes;
+    DDDevBuf<double> state;       // device: 2 * (n-1) doubles (re, im)
+    DDDevBuf<double> mats;        // device: block-parallel path, [M_hi, M_lo, MG_hi, MG_lo] each IIR_S x IIR_S (see below), short blocks
+    DDDevBuf<double> mats_long;   //         the same for the long block length
+    DDDevBuf<char> scratch;       // device: block / group vectors of the block-parallel path (grow-only)
 };
 struct DDIirCoef {
     int n;
@@ -249,12 +253,7 @@ extern "C" int dd_iir_create(dd_iir** h, const double* b, const double* a, int n
         f->a[k] = k < n ? a[k] / a[0] : 0.0;
         f->zi[k] = (zi_host && k < n - 1) ? zi_host[k] : 0.0;
     }
-    f->state = nullptr;
-    f->mats = nullptr;
-    f->mats_long = nullptr;
-    f->scratch = nullptr;
-    f->scratch_bytes = 0;
-    hipError_t e = hipMalloc((void**)&f->state, sizeof(double) * 2 * (DD_IIR_MAXN - 1));
+    hipError_t e = f->state.alloc(2 * (DD_IIR_MAXN - 1));
     if (e != hipSuccess) {
         delete f;
         dd_set_error("dd_iir_create: %s", hipGetErrorString(e));
@@ -262,7 +261,6 @@ extern "C" int dd_iir_create(dd_iir** h, const double* b, const double* a, int n
     }
     int rc = iir_set_state(f, nullptr);
     if (rc != DD_OK) {
-        (void)hipFree(f->state);
         delete f;
         return rc;
     }
@@ -271,13 +269,7 @@ extern "C" int dd_iir_create(dd_iir** h, const double* b, const double* a, int n
 }
 
 extern "C" int dd_iir_destroy(dd_iir* h) {
-    if (h) {
-        (void)hipFree(h->state);
-        if (h->mats) (void)hipFree(h->mats);
-        if (h->mats_long) (void)hipFree(h->mats_long);
-        if (h->scratch) (void)hipFree(h->scratch);
-        delete h;
-    }
+    delete h;
     return DD_OK;
 }
 
@@ -922,27 +914,25 @@ static int iir_parallel(dd_iir* h, const double* in, double* out, int64_t n, int
     const int64_t nb = (n + lb - 1) / lb, ng = (nb + IIR_G1 - 1) / IIR_G1;
     const bool three = ng > 2 * IIR_G2;
     const int64_t ns = three ? (ng + IIR_G2 - 1) / IIR_G2 : 0;
-    double*& mats = (lb == IIR_LB_LONG) ? h->mats_long : h->mats;
-    if (!mats) {                                            // first input of this length class on this handle
+    DDDevBuf<double>& mats_slot = (lb == IIR_LB_LONG) ? h->mats_long : h->mats;
+    if (!mats_slot) {                                       // first input of this length class on this handle
         double hm[6 * IIR_MAT];
         iir_block_matrices(h, lb, hm);
-        DD_HIP_CHECK(hipMalloc((void**)&mats, sizeof(hm)));
-        DD_HIP_CHECK(hipMemcpy(mats, hm, sizeof(hm), hipMemcpyHostToDevice));
+        DDDevBuf<double> up;                                // (the handle sees the matrices once they are on the device)
+        DD_HIP_CHECK(up.alloc(6 * IIR_MAT));
+        DD_HIP_CHECK(hipMemcpy(up, hm, sizeof(hm), hipMemcpyHostToDevice));
+        mats_slot = std::move(up);
     }
+    const double* const mats = mats_slot;
+    double* const state = h->state;
     // block and group vectors live in a scratch buffer kept on the handle (allocation and release cost ~0.4 ms per call)
     const size_t blk_bytes = (sizeof(double) * IIR_S * nb * ncomp + 255) & ~(size_t)255;
     const size_t grp_bytes = (sizeof(double) * IIR_S * ng * ncomp + 255) & ~(size_t)255;
     const size_t need = blk_bytes + grp_bytes + sizeof(double) * IIR_S * (ns + 1) * ncomp;
-    if (h->scratch_bytes < need) {
-        if (h->scratch) DD_HIP_CHECK(hipFree(h->scratch));
-        h->scratch = nullptr;
-        h->scratch_bytes = 0;
-        DD_HIP_CHECK(hipMalloc((void**)&h->scratch, need));
-        h->scratch_bytes = need;
-    }
-    double* blk = h->scratch;
-    double* grp = (double*)((char*)h->scratch + blk_bytes);
-    double* sup = (double*)((char*)h->scratch + blk_bytes + grp_bytes);
+    DD_HIP_CHECK(h->scratch.grow(need));
+    double* blk = (double*)h->scratch.get();
+    double* grp = (double*)(h->scratch + blk_bytes);
+    double* sup = (double*)(h->scratch + blk_bytes + grp_bytes);
     DDIirCoef C;
     iir_coef(h, &C);
     const unsigned gb = (unsigned)((nb * ncomp + 255) / 256);
@@ -957,7 +947,7 @@ static int iir_parallel(dd_iir* h, const double* in, double* out, int64_t n, int
             DD_HIP_CHECK(hipFuncSetAttribute((const void*)k_iir_blocks_t<SS, WR>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_t)); \
             attr_set.mark();                                                                                         \
         }                                                                                                            \
-        hipLaunchKernelGGL((k_iir_blocks_t<SS, WR>), dim3(gbt), dim3(256), lds_t, s, in, out, n, ncomp, C, blk, nb, h->state, SAVE, lb); \
+        hipLaunchKernelGGL((k_iir_blocks_t<SS, WR>), dim3(gbt), dim3(256), lds_t, s, in, out, n, ncomp, C, blk, nb, state, SAVE, lb); \
     } break;
 #define DD_IIR_BLOCKS_ALL(WR, SAVE)                                                                                  \
     switch (S) {                                                                                                     \
@@ -979,7 +969,7 @@ static int iir_parallel(dd_iir* h, const double* in, double* out, int64_t n, int
             attr_w.mark();                                                                                           \
         }                                                                                                            \
         hipLaunchKernelGGL((k_iir_blocks_w<SS, WR>), dim3(gbw), dim3(64), lds_w, s, reinterpret_cast<const double2*>(in), \
-                           reinterpret_cast<double2*>(out), n, C, blk, nb, h->state, SAVE, lb);                      \
+                           reinterpret_cast<double2*>(out), n, C, blk, nb, state, SAVE, lb);                      \
     } break;
 #define DD_IIR_BLOCKS_W_ALL(WR, SAVE)                                                                                \
     switch (S) {                                                                                                     \
@@ -1000,7 +990,7 @@ static int iir_parallel(dd_iir* h, const double* in, double* out, int64_t n, int
             attr_w32.mark();                                                                                         \
         }                                                                                                            \
         hipLaunchKernelGGL((k_iir_blocks_w32<SS, WR, CHW>), dim3(gbw), dim3(64), lds_w32, s, reinterpret_cast<const float2*>(in), \
-                           reinterpret_cast<double2*>(out), n, C, blk, nb, h->state, SAVE, lb);                      \
+                           reinterpret_cast<double2*>(out), n, C, blk, nb, state, SAVE, lb);                      \
     } break;
 #define DD_IIR_BLOCKS_W32_ALL(WR, SAVE)                                                                              \
     switch (S) {                                                                                                     \
@@ -1013,7 +1003,7 @@ static int iir_parallel(dd_iir* h, const double* in, double* out, int64_t n, int
     if (in32) { DD_IIR_BLOCKS_W32_ALL(false, 0) }
     else if (wave) { DD_IIR_BLOCKS_W_ALL(false, 0) }
     else if (staged) { DD_IIR_BLOCKS_ALL(false, 0) }
-    else hipLaunchKernelGGL(k_iir_blocks, dim3(gb), dim3(256), 0, s, in, out, n, ncomp, C, blk, nb, 0, h->state, 0, lb);
+    else hipLaunchKernelGGL(k_iir_blocks, dim3(gb), dim3(256), 0, s, in, out, n, ncomp, C, blk, nb, 0, state, 0, lb);
     // the state size is a compile-time constant of the scan kernels: with a run-time S the unrolled
     // double-double loops kept all 15 x 15 predicated products (~4 us per block step)
 #define DD_IIR_SCAN(SS)                                                                                              \
@@ -1024,10 +1014,10 @@ static int iir_parallel(dd_iir* h, const double* in, double* out, int64_t n, int
         hipLaunchKernelGGL(k_iir_groups<SS>, dim3(gg), dim3(64), 0, s, blk, grp, nb, ncomp, mats, 0, IIR_G1);     \
         if (three) {                                                                                                 \
             hipLaunchKernelGGL(k_iir_groups<SS>, dim3(gs), dim3(64), 0, s, grp, sup, ng, ncomp, mats + 2 * IIR_MAT, 0, IIR_G2); \
-            hipLaunchKernelGGL(k_iir_group_sweep<SS>, dim3(1), dim3(64), 0, s, sup, ns, ncomp, mats + 4 * IIR_MAT, h->state, zero); \
+            hipLaunchKernelGGL(k_iir_group_sweep<SS>, dim3(1), dim3(64), 0, s, sup, ns, ncomp, mats + 4 * IIR_MAT, state, zero); \
             hipLaunchKernelGGL(k_iir_groups<SS>, dim3(gs), dim3(64), 0, s, grp, sup, ng, ncomp, mats + 2 * IIR_MAT, 2, IIR_G2); \
         } else {                                                                                                     \
-            hipLaunchKernelGGL(k_iir_group_sweep<SS>, dim3(1), dim3(64), 0, s, grp, ng, ncomp, mats + 2 * IIR_MAT, h->state, zero); \
+            hipLaunchKernelGGL(k_iir_group_sweep<SS>, dim3(1), dim3(64), 0, s, grp, ng, ncomp, mats + 2 * IIR_MAT, state, zero); \
         }                                                                                                            \
         hipLaunchKernelGGL(k_iir_groups<SS>, dim3(gg), dim3(64), 0, s, blk, grp, nb, ncomp, mats, 2, IIR_G1);     \
     } break;
@@ -1040,7 +1030,7 @@ static int iir_parallel(dd_iir* h, const double* in, double* out, int64_t n, int
     if (in32) { DD_IIR_BLOCKS_W32_ALL(true, carry ? 1 : 0) }
     else if (wave) { DD_IIR_BLOCKS_W_ALL(true, carry ? 1 : 0) }
     else if (staged) { DD_IIR_BLOCKS_ALL(true, carry ? 1 : 0) }
-    else hipLaunchKernelGGL(k_iir_blocks, dim3(gb), dim3(256), 0, s, in, out, n, ncomp, C, blk, nb, 1, h->state, carry ? 1 : 0, lb);
+    else hipLaunchKernelGGL(k_iir_blocks, dim3(gb), dim3(256), 0, s, in, out, n, ncomp, C, blk, nb, 1, state, carry ? 1 : 0, lb);
 #undef DD_IIR_BLOCKS_W32_ALL
 #undef DD_IIR_BLOCKS_W32
 #undef DD_IIR_BLOCKS_W_ALL
@@ -1060,9 +1050,9 @@ extern "C" int dd_iir_f64(dd_iir* h, const double* in, double* out, int64_t n, i
     iir_coef(h, &C);
     if (!carry) {        // plain lfilter: zero state, nothing kept (filters.py:75)
         for (int k = 0; k < DD_IIR_MAXN; ++k) C.zi[k] = 0.0;
-        hipLaunchKernelGGL(k_iir_df2t, dim3(1), dim3(64), 0, dd_stream(stream), in, out, n, is_complex ? 2 : 1, C, h->state, 1, 0, 0);
+        hipLaunchKernelGGL(k_iir_df2t, dim3(1), dim3(64), 0, dd_stream(stream), in, out, n, is_complex ? 2 : 1, C, h->state.get(), 1, 0, 0);
     } else {
-        hipLaunchKernelGGL(k_iir_df2t, dim3(1), dim3(64), 0, dd_stream(stream), in, out, n, is_complex ? 2 : 1, C, h->state, 0, 0, 1);
+        hipLaunchKernelGGL(k_iir_df2t, dim3(1), dim3(64), 0, dd_stream(stream), in, out, n, is_complex ? 2 : 1, C, h->state.get(), 0, 0, 1);
     }
     DD_LAUNCH_CHECK();
     return DD_OK;
@@ -1088,9 +1078,9 @@ extern "C" int dd_iir_c64(dd_iir* h, const void* in_c64, double* out_c128, int64
     iir_coef(h, &C);
     if (!carry) {
         for (int k = 0; k < DD_IIR_MAXN; ++k) C.zi[k] = 0.0;
-        hipLaunchKernelGGL(k_iir_df2t, dim3(1), dim3(64), 0, s, out_c128, out_c128, n, 2, C, h->state, 1, 0, 0);
+        hipLaunchKernelGGL(k_iir_df2t, dim3(1), dim3(64), 0, s, out_c128, out_c128, n, 2, C, h->state.get(), 1, 0, 0);
     } else {
-        hipLaunchKernelGGL(k_iir_df2t, dim3(1), dim3(64), 0, s, out_c128, out_c128, n, 2, C, h->state, 0, 0, 1);
+        hipLaunchKernelGGL(k_iir_df2t, dim3(1), dim3(64), 0, s, out_c128, out_c128, n, 2, C, h->state.get(), 0, 0, 1);
     }
     DD_LAUNCH_CHECK();
     return DD_OK;
@@ -1112,26 +1102,24 @@ extern "C" int dd_iir_filtfilt_f64(dd_iir* h, const double* in, double* out, int
     hipStream_t s = dd_stream(stream);
     const int nc = is_complex ? 2 : 1;
     const int64_t N = n + 2 * (int64_t)edge;
-    double *ext = nullptr, *y1 = nullptr;
-    DD_HIP_CHECK(hipMalloc((void**)&ext, sizeof(double) * N * nc));
-    hipError_t e = hipMalloc((void**)&y1, sizeof(double) * N * nc);
-    if (e != hipSuccess) {
-        (void)hipFree(ext);
+    DDDevBuf<double> ext_buf, y1_buf;
+    DD_HIP_CHECK(ext_buf.alloc((size_t)N * nc));
+    if (const hipError_t e = y1_buf.alloc((size_t)N * nc)) {
         dd_set_error("hipMalloc: %s", hipGetErrorString(e));
         return DD_ERR_NOMEM;
     }
+    double* const ext = ext_buf;
+    double* const y1 = y1_buf;
     DDIirCoef C;
     iir_coef(h, &C);
     if (is_complex) hipLaunchKernelGGL(k_odd_ext<double2>, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, (const double2*)in, (double2*)ext, n, edge);
     else hipLaunchKernelGGL(k_odd_ext<double>, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, in, ext, n, edge);
     // forward pass with zi * ext[0]; backward pass over y1 with zi * y1[N-1], written in place order
-    hipLaunchKernelGGL(k_iir_df2t, dim3(1), dim3(64), 0, s, ext, y1, N, nc, C, h->state, 1, 0, 0);
-    hipLaunchKernelGGL(k_iir_df2t, dim3(1), dim3(64), 0, s, y1, ext, N, nc, C, h->state, 1, 1, 0);
+    hipLaunchKernelGGL(k_iir_df2t, dim3(1), dim3(64), 0, s, ext, y1, N, nc, C, h->state.get(), 1, 0, 0);
+    hipLaunchKernelGGL(k_iir_df2t, dim3(1), dim3(64), 0, s, y1, ext, N, nc, C, h->state.get(), 1, 1, 0);
     hipError_t le = hipGetLastError();
     hipError_t ce = hipMemcpyAsync(out, ext + (int64_t)edge * nc, sizeof(double) * n * nc, hipMemcpyDeviceToDevice, s);
-    hipError_t se = hipStreamSynchronize(s);
-    (void)hipFree(ext);
-    (void)hipFree(y1);
+    hipError_t se = hipStreamSynchronize(s);              // (before the two buffers are freed: every return below is behind it)
     DD_HIP_CHECK(le);
     DD_HIP_CHECK(ce);
     DD_HIP_CHECK(se);

@@ -445,7 +445,7 @@ __device__ __forceinline__ float dd_wave_max(float m) {
 // ============================================================================
 struct DDMfmaState {
     int nks = 0;
-    v8h* frag = nullptr;        // device
+    DDDevBuf<v8h> frag;         // device
     float inv_tapscale = 1.f;
 };
 
@@ -491,10 +491,10 @@ int dd_mfma_create(void** st, const double* taps, int K) {
     DDMfmaState* s = new DDMfmaState();
     s->nks = nks;
     s->inv_tapscale = (float)(1.0 / tapscale);
-    hipError_t e = hipMalloc((void**)&s->frag, frag.size() * sizeof(_Float16));
+    static_assert(sizeof(v8h) == 8 * sizeof(_Float16), "fragment size");
+    hipError_t e = s->frag.alloc(frag.size() / 8);
     if (e == hipSuccess) e = hipMemcpy(s->frag, frag.data(), frag.size() * sizeof(_Float16), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
-        if (s->frag) (void)hipFree(s->frag);
         delete s;
         dd_set_error("dd_mfma_create: %s", hipGetErrorString(e));
         return DD_ERR_HIP;
@@ -504,10 +504,7 @@ int dd_mfma_create(void** st, const double* taps, int K) {
 }
 
 void dd_mfma_destroy(void* st) {
-    DDMfmaState* s = reinterpret_cast<DDMfmaState*>(st);
-    if (!s) return;
-    (void)hipFree(s->frag);
-    delete s;
+    delete reinterpret_cast<DDMfmaState*>(st);
 }
 
 template <int NKS>

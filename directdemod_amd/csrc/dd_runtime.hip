@@ -101,8 +101,7 @@ struct DDScratchEntry {
     std::mutex mu;
     int dev;
     hipStream_t stream;
-    char* buf = nullptr;
-    size_t bytes = 0;
+    DDDevBuf<char> buf;
     unsigned long long last_use = 0;
 };
 static std::mutex g_scr_mu;                                   // the table only; never held while an entry is in use
@@ -130,7 +129,7 @@ int DDScratchLock::get(size_t bytes, hipStream_t s) {
                     }
                 if (victim != g_scr.size()) {
                     DDScratchEntry* v = g_scr[victim];
-                    if (v->buf) (void)hipFree(v->buf);
+                    v->buf.reset();
                     v->mu.unlock();
                     delete v;
                     g_scr.erase(g_scr.begin() + (long)victim);
@@ -145,17 +144,8 @@ int DDScratchLock::get(size_t bytes, hipStream_t s) {
     }
     e->mu.lock();
     entry = e;
-    if (e->bytes < bytes) {
-        if (e->buf) {
-            const hipError_t fe = hipFree(e->buf);              // (waits for the device: earlier users of the buffer are done)
-            e->buf = nullptr;
-            e->bytes = 0;
-            DD_HIP_CHECK(fe);
-        }
-        const size_t want = (bytes + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1);
-        DD_HIP_CHECK(hipMalloc((void**)&e->buf, want));
-        e->bytes = want;
-    }
+    // (growing frees first, and hipFree waits for the device: earlier users of the buffer are done)
+    if (e->buf.bytes() < bytes) DD_HIP_CHECK(e->buf.alloc((bytes + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1)));
     ptr = e->buf;
     return DD_OK;
 }
@@ -167,7 +157,7 @@ void dd_scratch_forget_stream(hipStream_t s) {
     for (size_t i = 0; i < g_scr.size();) {
         DDScratchEntry* c = g_scr[i];
         if (c->stream == s && c->mu.try_lock()) {
-            if (c->buf) (void)hipFree(c->buf);
+            c->buf.reset();
             c->mu.unlock();
             delete c;
             g_scr.erase(g_scr.begin() + (long)i);
@@ -217,15 +207,14 @@ extern "C" int dd_memcpy_d2d(void* dst, const void* src, size_t bytes, void* str
 // the library and looks at no seam word (dd_stream_sync does).
 extern "C" int dd_copy_warmup(void) {
     const size_t big = (size_t)1 << 20;
-    void* d = nullptr;
-    DD_HIP_CHECK(hipMalloc(&d, big));
+    DDDevBuf<char> d;
+    DD_HIP_CHECK(d.alloc(big));
     // (kept for the life of the process: the runtime pins the source of a copy this large in place, and returning pinned pages to the system
     //  has stalled later copies -- DESIGN.md 4.5, round 6)
     static char* const zeros = static_cast<char*>(calloc(1, big));
-    if (!zeros) { (void)hipFree(d); dd_set_error("dd_copy_warmup: out of host memory"); return DD_ERR_NOMEM; }
+    if (!zeros) { dd_set_error("dd_copy_warmup: out of host memory"); return DD_ERR_NOMEM; }
     hipError_t e = hipMemcpy(d, zeros, 4096, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d, zeros, big, hipMemcpyHostToDevice);
-    (void)hipFree(d);
+    if (e == hipSuccess) e = hipMemcpy(d, zeros, big, hipMemcpyHostToDevice);      // (synchronous: done before d is freed)
     DD_HIP_CHECK(e);
     return DD_OK;
 }
@@ -306,21 +295,18 @@ __global__ void k_fill_nco_table(float2* t) {
 }
 
 static std::mutex g_tbl_mu;
-static float2* g_tbl[64] = {nullptr};
+static DDDevBuf<float2>* const g_tbl = new DDDevBuf<float2>[64];      // per device ordinal; on the heap, never deleted: nothing is freed at exit
 
 const float2* dd_nco_table(void) {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
     std::lock_guard<std::mutex> lk(g_tbl_mu);
     if (!g_tbl[dev]) {
-        float2* p = nullptr;
-        if (hipMalloc((void**)&p, sizeof(float2) * DD_NCO_TSIZE) != hipSuccess) return nullptr;
-        hipLaunchKernelGGL(k_fill_nco_table, dim3(DD_NCO_TSIZE / 256), dim3(256), 0, 0, p);
-        if (hipDeviceSynchronize() != hipSuccess) {
-            (void)hipFree(p);
-            return nullptr;
-        }
-        g_tbl[dev] = p;
+        DDDevBuf<float2> p;                                  // (the slot takes it once it is filled)
+        if (p.alloc(DD_NCO_TSIZE) != hipSuccess) return nullptr;
+        hipLaunchKernelGGL(k_fill_nco_table, dim3(DD_NCO_TSIZE / 256), dim3(256), 0, 0, p.get());
+        if (hipDeviceSynchronize() != hipSuccess) return nullptr;
+        g_tbl[dev] = std::move(p);
     }
     return g_tbl[dev];
 }

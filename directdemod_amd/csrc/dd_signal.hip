@@ -154,7 +154,7 @@ extern "C" int dd_conv_same_c64(const float* in_c64, float* out_c64, int64_t n, 
 // difference (the kernel is bound by its 12 bytes per sample, not by the second polynomial).  Lane 0 of the launch leaves angle(x[n - 1])
 // for the next call, in the other word of the handle's pair.
 struct dd_fmad {
-    float* last = nullptr;  // device: [2] ping-pong
+    DDDevBuf<float> last;   // device: [2] ping-pong
     int parity = 0;
     int has_last = 0;       // host mirror of "self.__last is not None" (demod_fm.py:88)
 };
@@ -186,7 +186,7 @@ __global__ void __launch_bounds__(DD_SIG_THREADS) k_fm_angle_diff(const float2* 
 extern "C" int dd_fmad_create(dd_fmad** h) {
     DD_REQUIRE(h, "h");
     dd_fmad* f = new dd_fmad();
-    hipError_t e = hipMalloc((void**)&f->last, 2 * sizeof(float));
+    hipError_t e = f->last.alloc(2);
     if (e == hipSuccess) e = hipMemset(f->last, 0, 2 * sizeof(float));
     if (e != hipSuccess) {
         delete f;
@@ -197,10 +197,7 @@ extern "C" int dd_fmad_create(dd_fmad** h) {
     return DD_OK;
 }
 extern "C" int dd_fmad_destroy(dd_fmad* h) {
-    if (h) {
-        (void)hipFree(h->last);
-        delete h;
-    }
+    delete h;
     return DD_OK;
 }
 extern "C" int dd_fmad_reset(dd_fmad* h) {

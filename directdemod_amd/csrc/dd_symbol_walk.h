@@ -288,16 +288,14 @@ static int dd_sym_walk_launch(Kernel kernel, const char* who, const void* x, int
 // launch(that array) enqueues the correlation kernel, and the stream is drained before the array is freed
 template <class Launch>
 static int dd_sym_with_descriptors(const int64_t* bufs_host, int64_t nbuf, const char* who, void* stream, Launch launch) {
-    const size_t bytes = (size_t)nbuf * 5 * sizeof(int64_t);
-    void* dbufs = nullptr;
-    DD_HIP_CHECK(hipMalloc(&dbufs, bytes));
+    DDDevBuf<int64_t> dbufs;
+    DD_HIP_CHECK(dbufs.alloc((size_t)nbuf * 5));
     int rc = DD_OK;
-    if (hipMemcpyAsync(dbufs, bufs_host, bytes, hipMemcpyHostToDevice, dd_stream(stream)) != hipSuccess) rc = DD_ERR_HIP;
+    if (hipMemcpyAsync(dbufs, bufs_host, dbufs.bytes(), hipMemcpyHostToDevice, dd_stream(stream)) != hipSuccess) rc = DD_ERR_HIP;
     if (rc == DD_OK) {
-        launch(dbufs);
+        launch(dbufs.get());
         if (hipGetLastError() != hipSuccess || hipStreamSynchronize(dd_stream(stream)) != hipSuccess) rc = DD_ERR_HIP;
     }
-    hipFree(dbufs);
     DD_SYM_REQUIRE(rc == DD_OK, who, "launch failed");
     return DD_OK;
 }

@@ -456,3 +456,111 @@ def test_padded_chunk_list_in_one_launch_equals_the_chunk_loop_after_lds_fills(g
         assert list(nout) == counts
         diff = int((out[:tot].view(t.int32) != ref[:tot].view(t.int32)).sum())
         assert diff == 0, "%d of %d output words differ from the chunk loop (fill %#x)" % (diff, tot, pat)
+
+
+# ---- who owns device memory: handles created, used once and destroyed over and over; grow-only buffers before and after growing
+def _bits_equal(got, ref, what):
+    assert got.dtype == ref.dtype and got.shape == ref.shape, what
+    assert np.array_equal(got.view(np.uint8), ref.view(np.uint8)), "%s: bits differ" % (what,)
+
+
+def test_handles_survive_create_use_destroy_rounds(g):
+    """Twenty rounds; each creates, uses once and drops one handle of every family: the M = 1 chain with the running-sum state
+    (hamming(255)), the transform state (hamming(200)) and the MFMA fragments (hamming(63)), the block-sum decimator with its
+    tap cache and dd_fm (blackmanHarris(151), / 34, FM), dd_iir on its one-lane path (3000 samples) and its block-parallel
+    path (5000 samples; matrices and scratch), dd_rpoly, dd_fmad, and a raw dd_fir + dd_fm pair through the C ABI.
+    filters.pool_clear() ends every round: without it the pool keeps the dd_fir handles and dd_fir_destroy never runs.
+    Every round's outputs are the first round's, bit for bit."""
+    hip = g.hip
+    import directdemod_amd.comm as comm
+    import directdemod_amd.demod_fm as demod_fm
+    import directdemod_amd.filters as filters
+    import directdemod_amd.resample as resample
+    fs2 = 2048000
+    x = O.grid_c64(O.synth_iq_fm(70000, FS, 41, f_carrier=25e3))
+    x2 = O.grid_c64(O.synth_iq_fm(70000, fs2, 42, f_carrier=30e3))
+    a = np.abs(x).astype(np.float32)
+    xd = g.bench.make_input(g.torch, 70000, 0, g.dev, 44)
+
+    def one_round(first):
+        outs = []
+        f255, f200, f63, bh = filters.hamming(255), filters.hamming(200), filters.hamming(63), filters.blackmanHarris(151)
+        fm, fm2 = demod_fm.demod_fm(), demod_fm.demod_fm()
+        outs.append(comm.commSignal(FS, x).offsetFreq(25000.0).filter(f255).funcApply(fm.demod).signal)
+        outs.append(comm.commSignal(FS, x[:20000]).offsetFreq(25000.0).filter(f200).signal)
+        outs.append(comm.commSignal(FS, x[:20001]).filter(f63).signal)
+        outs.append(comm.commSignal(fs2, x2).offsetFreq(30000.0).filter(bh).bwLim(60000, uniq="First").funcApply(fm2.demod).signal)
+        if first:
+            assert f255._last_kernel() == hip.DD_KERNEL_COS_RS
+            assert f200._last_kernel() == hip.DD_KERNEL_FFT_OS
+            assert f63._last_kernel() in (hip.DD_KERNEL_MFMA_AB, hip.DD_KERNEL_MFMA_TILES)
+            assert bh._last_kernel() == hip.DD_KERNEL_DECIM_BLOCKS
+        outs.append(comm.commSignal(FS, a[:3000]).filter(filters.butter(FS, 4160.0)).signal)
+        outs.append(comm.commSignal(FS, a[:5000]).filter(filters.butter(FS, 4160.0)).signal)
+        outs.append(comm.commSignal(FS, a[:30000]).resamplePoly(resample.polyResampler(FS, 20800)).signal)
+        outs.append(demod_fm.demod_fmAD().demod(x[:4096]))
+        out, got, kern = _fused_once(g, O.win_blackmanharris(151), 34, True, xd, 8, 70000, 0, 0, 0)
+        assert kern == hip.DD_KERNEL_DECIM_BLOCKS and got > 0
+        outs.append(out[:got].cpu().numpy())
+        outs = [np.asarray(v).copy() for v in outs]
+        del f255, f200, f63, bh, fm, fm2
+        filters.pool_clear()
+        return outs
+
+    ref = one_round(True)
+    for k, v in enumerate(ref):
+        assert v.size > 0 and np.all(np.isfinite(v)), k
+    for rnd in range(1, 20):
+        for k, (got, want) in enumerate(zip(one_round(False), ref)):
+            _bits_equal(got, want, "round %d, output %d" % (rnd, k))
+
+
+def test_grow_only_buffers_give_the_same_bits_after_growing(g):
+    """The grow-only buffers on the handles, before and after they grow: dd_iir's scratch (one butter handle at 5000, 70 000 and
+    5000 samples again, storeState=False, block-parallel path each time) and dd_fir's chunk-list image (one handle: a list of 2
+    chunks, of 16, of 2 again through k_chain_decim_multi).  Each result is what a fresh handle gives for that input, bit for bit."""
+    t, lib, hip = g.torch, g.lib, g.hip
+    import directdemod_amd.filters as filters
+    x = O.grid_c64(O.synth_iq_fm(70000, FS, 43, f_carrier=25e3))
+    flt = filters.butter(FS, 40000.0, storeState=False)
+    for n in (5000, 70000, 5000):
+        got = np.asarray(flt.applyOn(x[:n]))
+        want = np.asarray(filters.butter(FS, 40000.0, storeState=False).applyOn(x[:n]))
+        assert got.shape == (n,) and np.all(np.isfinite(got.view(np.float64)))
+        _bits_equal(got, want, "butter, %d samples" % n)
+
+    n, M, taps = 64000, 5, _hamming(63)
+    xd = g.bench.make_input(t, n, 0, g.dev, 99)
+    cyc = hip.cycles_q64(25000.0, FS)
+    lists = ([0, 30001, n], list(range(0, n + 1, 4000)), [0, 30001, n])
+    assert [len(c) - 1 for c in lists] == [2, 16, 2]
+
+    def run(fir, fmh, cuts):
+        bounds = (C.c_int64 * len(cuts))(*cuts)
+        nout = (C.c_int64 * (len(cuts) - 1))()
+        out = t.full((n // M + 8,), float("nan"), dtype=t.float32, device=g.dev)
+        hip.check(lib.dd_fused_process_chunks(fir, fmh, xd.data_ptr(), out.data_ptr(), bounds, len(cuts) - 1, 1, cyc, 0, M, 0, 0, nout,
+                                              g.stream), "dd_fused_process_chunks")
+        t.cuda.synchronize()
+        assert lib.dd_fir_last_kernel(fir) == hip.DD_KERNEL_DECIM_MULTI
+        tot = sum(nout)
+        assert tot > 0 and bool(t.isfinite(out[:tot]).all())
+        return out[:tot].cpu().numpy(), list(nout)
+
+    fir, fmh = _fused_handles(g, taps, True)
+    try:
+        for cuts in lists:
+            hip.check(lib.dd_fir_reset(fir, hip.DD_HIST_ZEROS, None, g.stream), "dd_fir_reset")
+            hip.check(lib.dd_fm_reset(fmh), "dd_fm_reset")
+            got, cnt = run(fir, fmh, cuts)
+            f2, m2 = _fused_handles(g, taps, True)
+            try:
+                want, cnt2 = run(f2, m2, cuts)
+            finally:
+                lib.dd_fir_destroy(f2)
+                lib.dd_fm_destroy(m2)
+            assert cnt == cnt2
+            _bits_equal(got, want, "chunk list of %d" % (len(cuts) - 1))
+    finally:
+        lib.dd_fir_destroy(fir)
+        lib.dd_fm_destroy(fmh)
