@@ -1,8 +1,9 @@
 // Audio-rate rows of the NOAA tail (R2, A1, X1, X2, and 8f-2 / P: the accurate-sync windows and the crude tail), float64 on the
 // device so that sync index picks stay bit-exact (H7).  Sizes here are 1e5 .. 1e7 samples.  This file holds what the families share -- the FFT
-// library's plan cache (the stand-alone class routes only), the own float64 cyclic convolution of 2^17 / 2^18 points (dd_hconv_kernels.h) and
-// its tables -- and includes the six parts (dd_audio_envelope.h, dd_audio_resample.h, dd_audio_xcorr.h, dd_audio_sync.h, dd_audio_crude.h, dd_audio_apt.h):
-// one translation unit, split by entry-point family in round 6.
+// library's plan cache (the stand-alone class routes only), the sync entry points' mutex and scratch buffers, the own float64 cyclic
+// convolution of 2^17 / 2^18 points (dd_hconv_kernels.h) and its tables -- and includes the six parts (dd_audio_envelope.h,
+// dd_audio_resample.h, dd_audio_xcorr.h, dd_audio_sync.h, dd_audio_crude.h, dd_audio_apt.h): one translation unit, split by entry-point
+// family in round 6.  The parts are layers: each uses only this file and the parts included before it.
 #include "dd_common.h"
 #include <hipfft/hipfft.h>
 #include <map>
@@ -70,6 +71,43 @@ struct DDSyncOnExit {
     void done() { armed = false; }
     ~DDSyncOnExit() { if (armed) (void)hipStreamSynchronize(s); }
 };
+
+// ---------------------------------------------------------------- the sync entry points' mutex and buffers
+// One mutex serialises the entry points that use the buffers below or the Hilbert-kernel spectra cache (dd_audio_envelope.h).
+static std::mutex g_sync_mu;
+// grow-only scratch per device for the audio-rate entry points' intermediates (no allocation in the steady state:
+// a hipMalloc/hipFree pair costs 50-100 us, a dozen of them were half of a correlate + peak-pick call)
+// ... and pinned host staging per device for the entry points' one copy back (grow-only; callers hold g_sync_mu).
+// One pair per device ordinal, on the heap and never deleted: nothing is freed at exit
+struct DDSyncBufs {
+    DDDevBuf<char> scratch;
+    DDPinnedBuf<char> pinned;
+};
+static DDSyncBufs* const g_sync_bufs = new DDSyncBufs[64];
+
+static int sync_bufs(DDSyncBufs** out) {
+    int dev = 0;
+    DD_HIP_CHECK(hipGetDevice(&dev));
+    DD_REQUIRE(dev >= 0 && dev < 64, "device index");
+    *out = &g_sync_bufs[dev];
+    return DD_OK;
+}
+static int sync_scratch(size_t bytes, char** out) {
+    DDSyncBufs* b = nullptr;
+    const int rc = sync_bufs(&b);
+    if (rc != DD_OK) return rc;
+    DD_HIP_CHECK(b->scratch.grow(bytes));
+    *out = b->scratch;
+    return DD_OK;
+}
+static int sync_pinned(size_t bytes, char** out) {
+    DDSyncBufs* b = nullptr;
+    const int rc = sync_bufs(&b);
+    if (rc != DD_OK) return rc;
+    DD_HIP_CHECK(b->pinned.grow(bytes, hipHostMallocDefault));
+    *out = b->pinned;
+    return DD_OK;
+}
 
 // ---------------------------------------------------------------- own float64 cyclic convolution of length 2^17 / 2^18 (dd_hconv_kernels.h)
 #include "dd_hconv_kernels.h"
@@ -153,9 +191,9 @@ void dd_audio_forget_stream(hipStream_t s) {
 }
 
 // ---------------------------------------------------------------- the entry-point families (round 6: one file each, one translation unit)
-#include "dd_audio_envelope.h"      // A1   dd_am_envelope_f64
+#include "dd_audio_envelope.h"      // A1   dd_am_envelope_f64; the Hilbert-kernel spectra and the block envelope every part uses
 #include "dd_audio_resample.h"      // R2   dd_resample_fft_f64 / _chunks, dd_rpoly_*
-#include "dd_audio_xcorr.h"         // X1, X2   dd_xcorr_norm_f64, dd_find_peaks_f64
+#include "dd_audio_xcorr.h"         // X1, X2   dd_xcorr_norm_f64, dd_find_peaks_f64; the scan, the run-length correlation and the peak pick
 #include "dd_audio_sync.h"          // 8f-2  dd_noaa_sync_windows(_multi), dd_noaa_prepare
 #include "dd_audio_crude.h"         // P     dd_noaa_crude_tail
 #include "dd_audio_apt.h"           // APT image: dd_median_segments_f64, dd_apt_lines_f64, dd_apt_map_u8, dd_apt_color_u8

@@ -1,7 +1,6 @@
 // R2: commSignal.bwLim(strict) = scipy.signal.resample (comm.py:110-116): dd_resample_fft_f64, dd_resample_fft_chunks, the chirp-z form, and the polyphase extension dd_rpoly_*
-// One of the five parts of dd_audio.hip (round 6: the 2600-line unit split along its entry-point families; still ONE translation unit --
-// the parts share the plan cache, the float64 transform and the scratch buffers of dd_audio.hip and are included there, in this order).
-// Internal; not a stand-alone header.
+// One of the six parts of dd_audio.hip (one translation unit: the parts share the plan cache, the float64 transform and the scratch
+// buffers of dd_audio.hip and are included there, each using only the parts before it).  Internal; not a stand-alone header.
 // ---------------------------------------------------------------- R2: scipy.signal.resample (real input)
 // X = rfft(x); Y[:nyq] = X[:nyq] (nyq = min(num,Nx)/2 + 1), Nyquist bin doubled when
 // down-sampling / halved when up-sampling an even N; y = irfft(Y, num) * num / Nx.

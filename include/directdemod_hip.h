@@ -343,8 +343,10 @@ int dd_xcorr_norm_f64(const double* h, int64_t n, const double* needle_host, int
                       double* out, void* stream);
 
 /* ---- X2: peak pick of decode_noaa.__correlateAndFindPeaks (decode_noaa.py:713-751) */
-/* cor: n float64 on device.  Writes up to max_peaks int64 indices (already shifted
- * by -needle_len/2, sorted) to peaks_host and their count to n_peaks.  Synchronous. */
+/* cor: n float64 on device, n < 2^31 (the selection and candidate kernels count in 32 bits; DD_ERR_INVALID beyond).  Writes up to
+ * max_peaks int64 indices (already shifted by -needle_len/2, sorted) to peaks_host and their count to n_peaks.  The kernels are
+ * those of dd_noaa_crude_tail, run for one needle with the threshold computed on the host: no limit on the expected peak count
+ * or on the number of candidates.  Synchronous. */
 int dd_find_peaks_f64(const double* cor, int64_t n, double samp_rate, int needle_len,
                       int64_t* peaks_host, int max_peaks, int* n_peaks, void* stream);
 

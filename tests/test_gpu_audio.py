@@ -120,8 +120,8 @@ def test_xcorr_and_peaks_3s_golden(dd, noaa_inputs):
 
 
 def test_crude_tail_in_one_call_equals_the_staged_route(dd, noaa_inputs):
-    """dd_noaa_crude_tail (envelope by a real transform pair, prefix sums once, both needles, selection + threshold +
-    candidates in one persistent launch with grid-wide barriers) against the stage-by-stage entry points on the same audio:
+    """dd_noaa_crude_tail (envelope block by block, prefix sums once, both needles per launch, selection + threshold +
+    candidates in a dozen launches that never come back to the host) against the stage-by-stage entry points on the same audio:
     identical index lists for both sync words (and equal to the reference's golden lists), envelope to 1e-12; odd lengths and
     a length below one block included (the last block of the chunker rule is ragged)."""
     g, raw = noaa_inputs
@@ -190,15 +190,19 @@ def test_crude_tail_many_candidates(dd):
     for n in (20 * rate + 17, 8 * rate + 3, 6 * rate, 5 * rate + 1, 4 * rate, 3 * rate + 5, 2 * rate, rate + 999):
         a = np.ascontiguousarray(rng.normal(0.0, 0.3, n))
         sig = ns.envelope(dd.comm.commSignal(rate, a))
-        counts = []
+        counts, staged = [], []
         for nd in needles:                      # values above the threshold, from the staged correlation
-            cor = np.sort(dd.ops.xcorr_norm(sig.device_signal, nd).to_host())
+            cor_h = dd.ops.xcorr_norm(sig.device_signal, nd).to_host()
+            staged.append(cor_h)
+            cor = np.sort(cor_h)
             K = int(2 * (n / rate)) + 2
             avgpk = np.mean(cor[-K:])
             counts.append(int(np.count_nonzero(cor > avgpk - 0.25 * (avgpk - np.mean(cor[:K])))))
         res = dd.ops.crude_tail(dd.hip.DevArray.from_host(a), rate, needles)
         if max(counts) > 65536:
             assert res is None, (n, counts)
+            for bits, cor_h, nd in zip((O.NOAA_SYNCA, O.NOAA_SYNCB), staged, needles):      # the staged route the caller then takes
+                assert np.array_equal(ns.correlate_and_find_peaks(sig, bits), O.find_peaks(cor_h, rate, len(nd))), (n, counts)
             seen.add("declined")
             continue
         assert res is not None, (n, counts)
@@ -855,6 +859,58 @@ def test_xcorr_norm_silent_stretch(dd):
     bad_ref = ~np.isfinite(ref)
     assert bad_ref.sum() > 3000 and np.array_equal(~np.isfinite(got), bad_ref)
     assert np.max(np.abs(got[~bad_ref] - ref[~bad_ref])) < 1e-9
+
+
+@pytest.mark.parametrize("n,runs,rep", [(1023, 5, 17), (1025, 5, 17), (4097, 5, 17), (1023, 7, 23), (1025, 7, 23), (4097, 7, 23),
+                                        (1025, 64, 16), (4097, 64, 16), (4097, 37, 83), (4097, 48, 64)])
+def test_xcorr_runs_form_edges(dd, n, runs, rep):
+    """The run-length form at its edges: signals one short of, one past and four tiles past its 1024-output tile; 5 and 7 runs (the
+    tail of the run loop unrolled by four), 64 runs of 16 (the most the form takes, m = 16 runs exactly), and the needle lengths on
+    both sides of the LDS staging, m = 3071 (37 x 83, staged) and 3072 (48 x 64, straight from memory).  (A needle longer than the
+    signal is rejected by the entry, so n = 1023 has no 1024-sample case.)"""
+    rng = np.random.default_rng(17)
+    h = np.abs(rng.standard_normal(n)) + 0.2
+    needle = np.repeat(rng.standard_normal(runs), rep)
+    assert len(needle) <= n and runs <= 64 and len(needle) >= 16 * runs and np.all(np.diff(needle[::rep]) != 0)
+    got = dd.ops.xcorr_norm(dd.hip.DevArray.from_host(h), needle).to_host()
+    ref = O.xcorr_norm(h, needle)
+    assert got.shape == ref.shape
+    assert np.max(np.abs(got - ref)) < 1e-9 * np.max(np.abs(ref))
+
+
+# ----------------------------------------------------------------------------- X2: the peak pick by itself
+@pytest.mark.parametrize("n,rate,quant,reaches", [
+    (1500, 100, 0, "short"),                   # n below the 2048 wave stretches: empty stretches, partial histogram workgroups
+    (1500, 100, 8, "ties"),                    # tens of ties at the K-th largest and K-th smallest
+    (2049, 64, 0, "short"),                    # one value past a tile and a stretch boundary
+    (110000, 100, 0, "big K"),                 # K = 2202: more than the fused entry's in-kernel sort holds
+    (110000, 100, 16, "big K ties"),           # ... with about a thousand ties at each key
+    (700000, 4000, 0, "second copy"),          # more candidates than the 24 576 of the head block
+    (700000, 100, 0, "big K overflow"),        # K = 14 002 and more than 65 536 candidates
+])
+def test_find_peaks_small_shapes(dd, n, rate, quant, reaches):
+    """dd_find_peaks_f64 alone against the oracle's peak pick (decode_noaa.py:713-751) on noise, where it runs the kernels it shares
+    with dd_noaa_crude_tail outside that entry's limits; where K is beyond them the fused entry still declines."""
+    c = np.random.default_rng(5).normal(0, 0.3, n)
+    if quant:
+        c = np.round(c * quant) / quant
+    K = int(2 * (n / rate)) + 2
+    s = np.sort(c)
+    thr = np.mean(s[-K:]) - 0.25 * (np.mean(s[-K:]) - np.mean(s[:K]))
+    ncand = int(np.count_nonzero(c > thr))
+    if "ties" in reaches:
+        assert min(np.count_nonzero(c == s[-K]), np.count_nonzero(c == s[K - 1])) >= 10
+    if "big K" in reaches:
+        assert K > 2048
+        needles = [O.sync_needle(O.NOAA_SYNCA, 40960), O.sync_needle(O.NOAA_SYNCB, 40960)]
+        if not quant:
+            assert dd.ops.crude_tail(dd.hip.DevArray.from_host(c), rate, needles) is None
+    if reaches == "second copy":
+        assert 24576 < ncand <= 65536
+    if "overflow" in reaches:
+        assert ncand > 65536
+    got = dd.ops.find_peaks(dd.hip.DevArray.from_host(c), rate, 56)
+    assert np.array_equal(got, O.find_peaks(c, rate, 56))
 
 
 # ----------------------------------------------------------------------------- demod_amFLT (demod_am.py:35-62)
