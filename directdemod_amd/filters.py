@@ -310,7 +310,7 @@ class gaussian(filter):
 class butter(filter):
     '''Butterworth filter (filters.py:232-273).  IIR: a float64 transposed direct form II
     recurrence on the device -- one lane per component for short (audio-rate) inputs, the
-    block-parallel form (dd_fir.hip: block end states, two-level scan of the start states,
+    block-parallel form (csrc/dd_iir.h: block end states, two-level scan of the start states,
     re-run) from 4096 samples up, which is what full-rate IQ through a butter takes
     (decode_funcube.py:160,230).'''
 

@@ -824,6 +824,106 @@ def test_iir_complex64_input_read_in_place_equals_the_widened_route(dd, n):
     assert np.max(np.abs(np.concatenate([a, b]) - whole)) <= 1e-7 * np.max(np.abs(whole))      # (other block boundaries: the conditioning above)
 
 
+# (order, cutoff as a fraction of Nyquist) -> {kind: error relative to the peak} that the commit before the block passes were folded into
+# one wave walk measured against scipy.signal.lfilter on an MI355X.  The tests allow TWICE these: seed and input are fixed, so the factor
+# covers a different host BLAS in the checker and nothing else.  c64 is bit for bit c128 (asserted), so they share a figure.
+_IIR_ROUTE_MEASURED = {
+    (1, 0.004): {"f64": 4.502e-16, "f64_view1": 4.502e-16, "c128": 5.616e-16, "c64": 5.616e-16},
+    (2, 0.01): {"f64": 6.552e-15, "f64_view1": 6.552e-15, "c128": 2.303e-14, "c64": 2.303e-14},
+    (8, 0.1): {"f64": 3.747e-11, "f64_view1": 3.747e-11, "c128": 3.836e-11, "c64": 3.836e-11},
+    (9, 0.1): {"f64": 1.805e-10, "f64_view1": 1.805e-10, "c128": 2.307e-10, "c64": 2.307e-10},
+    (15, 0.2): {"f64": 4.149e-10, "f64_view1": 4.149e-10, "c128": 4.288e-10, "c64": 4.288e-10},
+}
+_IIR_ROUTE_N, _IIR_ROUTE_TAIL = 256 * 33 + 101, 1000
+_iir_route_refs = {}
+
+
+def _iir_route_ref(order, wn, cplx):
+    """input and lfilter's output (zi = lfilter_zi) for one filter, computed once; the complex samples are complex64 values, so that the
+    complex64 and the complex128 route filter the same numbers"""
+    import scipy.signal as ss
+    key = (order, cplx)
+    if key not in _iir_route_refs:
+        rng = np.random.default_rng(100 * order + cplx)
+        m = _IIR_ROUTE_N + _IIR_ROUTE_TAIL
+        if cplx:
+            x = (rng.standard_normal(m) + 1j * rng.standard_normal(m)).astype(np.complex64).astype(np.complex128)
+        else:
+            x = rng.standard_normal(m)
+        b, a = ss.butter(order, wn)
+        ref = ss.lfilter(b, a, x, zi=ss.lfilter_zi(b, a).astype(x.dtype))[0]
+        x.setflags(write=False)
+        ref.setflags(write=False)
+        _iir_route_refs[key] = (x, ref)
+    return _iir_route_refs[key]
+
+
+def _iir_two_chunks(dd, order, wn, x, shift=0):
+    """a first chunk that takes the block-parallel route and a second that takes the one-lane kernel, the state carried between them; `shift`:
+    the first chunk sits `shift` elements into its device array (1: a float64 input that is 8-byte aligned only)"""
+    n = _IIR_ROUTE_N
+    f = dd.filters.butter(2.0, wn, n=order)
+    head = dd.hip.DevArray.from_host(np.r_[np.zeros(shift, dtype=x.dtype), x[:n]]).view(shift, n)
+    a = f.applyOn(head).to_host()
+    b = f.applyOn(dd.hip.DevArray.from_host(x[n:])).to_host()
+    return np.concatenate([a, b])
+
+
+@pytest.mark.parametrize("kind", ["f64", "f64_view1", "c128", "c64"])
+@pytest.mark.parametrize("order,wn", sorted(_IIR_ROUTE_MEASURED))
+def test_iir_every_route_small_shapes(dd, order, wn, kind):
+    """Every block kernel at both ends of the order table (1, 15) and where the scan goes from 8 to 16 lanes per chain (8 -> 9), at the
+    smallest size with a whole and a ragged wave workgroup: 8549 samples = 34 blocks of 256, the last one of 101 samples, odd length (the
+    last 16-byte unit holds one sample); then 1000 samples more through the one-lane kernel with the state carried.  The cutoffs keep the
+    256-step block map from vanishing (max |A^256| = 4e-2, 9e-2, 2e-2, 4e2, 4e6), so a wrong scan shows.
+      f64        k_iir_blocks_t (workgroup, LDS staged)
+      f64_view1  k_iir_blocks (one lane per block): input one element into its array, 8-byte aligned only; also within 1e-12 of the
+                 peak of the f64 route (the same recurrence, only contraction may differ)
+      c128       k_iir_blocks_w (one wave, LDS-DMA)
+      c64        k_iir_blocks_w32 (read pass 64 samples per step, write pass 32); also bit for bit the widened complex128 call
+    Checker: one scipy.signal.lfilter call over both chunks with zi = lfilter_zi.  Measured before the refactor, error / peak:
+      order, cutoff   f64 = f64_view1   c128 = c64
+      1, 0.004        4.502e-16         5.616e-16
+      2, 0.01         6.552e-15         2.303e-14
+      8, 0.1          3.747e-11         3.836e-11
+      9, 0.1          1.805e-10         2.307e-10
+      15, 0.2         4.149e-10         4.288e-10
+    (f64_view1 equalled f64 bit for bit.)  The bound of each case is twice its figure.
+    (float64 lfilter itself against an 80-bit evaluation: 7e-16, 3e-14, 2e-11, 2e-10, 4e-10)"""
+    cplx = kind in ("c128", "c64")
+    x, ref = _iir_route_ref(order, wn, cplx)
+    got = _iir_two_chunks(dd, order, wn, x.astype(np.complex64) if kind == "c64" else x, shift=1 if kind == "f64_view1" else 0)
+    assert got.dtype == ref.dtype
+    err = rel_err(got, ref)
+    print("iir route order %d cutoff %g %s: error / peak = %.3e" % (order, wn, kind, err))
+    if kind == "c64":
+        assert np.array_equal(got, _iir_two_chunks(dd, order, wn, x))
+    if kind == "f64_view1":
+        same = _iir_two_chunks(dd, order, wn, x)
+        print("iir route order %d cutoff %g f64_view1 against f64: %.3e" % (order, wn, rel_err(got, same)))
+        assert np.max(np.abs(got - same)) <= 1e-12 * np.max(np.abs(same))
+    assert err <= 2 * _IIR_ROUTE_MEASURED[(order, wn)][kind]
+
+
+_IIR_SMALLEST_MEASURED = {False: 5.849e-9, True: 5.973e-9}
+
+
+@pytest.mark.parametrize("cplx", [False, True])
+def test_iir_smallest_block_parallel_input(dd, cplx):
+    """4096 samples exactly, order 6, no state kept: the smallest input that takes the block-parallel route -- 16 blocks, one partial
+    workgroup, one group.  Bounds: twice what the commit before the one order dispatch measured against
+    lfilter on an MI355X, relative to the peak: 5.849e-9 real, 5.973e-9 complex128 (poles within 0.03 of the unit circle)."""
+    import scipy.signal as ss
+    rng = np.random.default_rng(6 + cplx)
+    x = rng.standard_normal(4096) + (1j * rng.standard_normal(4096) if cplx else 0)
+    x = x.astype(np.complex128 if cplx else np.float64)
+    f = dd.filters.butter(2048000, 20000.0, storeState=False)
+    got = f.applyOn(dd.hip.DevArray.from_host(x)).to_host()
+    err = rel_err(got, ss.lfilter(np.asarray(f.getB), np.asarray(f.getA), x))
+    print("iir smallest block-parallel input, %s: error / peak = %.3e" % ("complex128" if cplx else "real", err))
+    assert err <= 2 * _IIR_SMALLEST_MEASURED[cplx]
+
+
 # ----------------------------------------------------------------------------- X1: both forms of the correlation
 @pytest.mark.parametrize("kind", ["runs_even", "runs_odd", "dense", "many_runs"])
 def test_xcorr_norm_forms_vs_oracle(dd, kind):
