@@ -115,8 +115,9 @@ static std::mutex g_hc_mu;
 // device -> W_512^j (512) | W_{2^18}^j (512) | W_{2^17}^j (256).  On the heap, never deleted: nothing is freed at exit
 static DDDevBuf<double2>* const g_hc_tab = new DDDevBuf<double2>[64];
 static bool hc_length_ok(int64_t M) { return M == ((int64_t)1 << 17) || M == ((int64_t)1 << 18); }
-// lg: 9 (M = 2^18) or 8 (M = 2^17)
-static int hc_tables(int lg, const double2** TA, const double2** TB) {
+static int hc_lg(int64_t M) { return M == ((int64_t)1 << 18) ? 9 : 8; }      // rows of 2^lg points: 9 (M = 2^18) or 8 (M = 2^17)
+// the device's table; W_512^j is its head, the row pass's W_M^j follows at DD_HC_N (M = 2^18) or 2 DD_HC_N (M = 2^17)
+static int hc_tables(const double2** tab) {
     int dev = 0;
     DD_HIP_CHECK(hipGetDevice(&dev));
     DD_REQUIRE(dev >= 0 && dev < 64, "device index");
@@ -135,41 +136,46 @@ static int hc_tables(int lg, const double2** TA, const double2** TB) {
         if (e != hipSuccess) { dd_set_error("twiddle table upload: %s", hipGetErrorString(e)); return DD_ERR_HIP; }
         g_hc_tab[dev] = std::move(d);
     }
-    *TA = g_hc_tab[dev];
-    *TB = g_hc_tab[dev] + (lg == 9 ? DD_HC_N : 2 * DD_HC_N);
+    *tab = g_hc_tab[dev];
     return DD_OK;
 }
-// the column passes take 64 KB of dynamic LDS: once per device and instantiation
-template <int LG, typename SRC, typename DST>
-static int hc_ready() {
-    static DDOncePerDevice once;
+template <int LG, typename SRC, typename SPEC, typename DST>
+static int hc_run_lg(const SRC& src, const SPEC& spec, const DST& dst, double2* T, int jobs, hipStream_t s) {
+    const double2* tab = nullptr;
+    const int rc = hc_tables(&tab);
+    if (rc != DD_OK) return rc;
+    static DDOncePerDevice once;                                 // the column passes take 64 KB of dynamic LDS: once per device and instantiation
     if (once.need()) {
         DD_HIP_CHECK((hc_set_lds_attr<LG, SRC, DST>()));
         once.mark();
     }
+    hc_convolve<LG>(src, spec, dst, T, jobs, tab, tab + (LG == 9 ? 1 : 2) * DD_HC_N, s);
     return DD_OK;
+}
+// THE door to the transform: `jobs` cyclic convolutions of M points (hc_length_ok(M)), src -> times spec -> dst, through the image T [jobs][M]
+template <typename SRC, typename SPEC, typename DST>
+static int hc_run(int64_t M, const SRC& src, const SPEC& spec, const DST& dst, double2* T, int jobs, hipStream_t s) {
+    return hc_lg(M) == 9 ? hc_run_lg<9>(src, spec, dst, T, jobs, s) : hc_run_lg<8>(src, spec, dst, T, jobs, s);
+}
+// a spectrum of M bins into the row pass's order, scaled
+static void hc_perm(int64_t M, const double2* in, double2* out, int hermitian, double scale, hipStream_t s) {
+    if (hc_lg(M) == 9) hipLaunchKernelGGL(k_hc_perm<9>, dim3((unsigned)(M / 256)), dim3(256), 0, s, in, out, hermitian, scale);
+    else hipLaunchKernelGGL(k_hc_perm<8>, dim3((unsigned)(M / 256)), dim3(256), 0, s, in, out, hermitian, scale);
 }
 // envelope of `nwin` windows (two per image) through the three launches; HHp: the kernel spectrum in row-pass order
 static int hc_envelope(int64_t M, const float2* X, int64_t L, int nwin, const double2* HHp, double2* W, double* ENV, hipStream_t s) {
-    const int lg = M == ((int64_t)1 << 18) ? 9 : 8;
-    const double2 *TA = nullptr, *TB = nullptr;
-    int rc = hc_tables(lg, &TA, &TB);
-    if (rc != DD_OK) return rc;
     const HcEnvIO io = {X, L, L - 1, nwin, ENV};
-    const HcOneSpec sp = {HHp};
-    const int pairs = (nwin + 1) / 2;
-    if (lg == 9) {
-        rc = hc_ready<9, HcEnvIO, HcEnvIO>();
-        if (rc == DD_OK) hc_convolve<9>(io, sp, io, W, pairs, TA, TB, s);
-    } else {
-        rc = hc_ready<8, HcEnvIO, HcEnvIO>();
-        if (rc == DD_OK) hc_convolve<8>(io, sp, io, W, pairs, TA, TB, s);
-    }
-    return rc;
+    return hc_run(M, io, HcOneSpec{HHp}, io, W, (nwin + 1) / 2, s);
 }
 
-struct DDCztKey;
-static void czt_forget_stream(int dev, hipStream_t s);
+// ---------------------------------------------------------------- the entry-point families (round 6: one file each, one translation unit)
+#include "dd_audio_envelope.h"      // A1   dd_am_envelope_f64; the Hilbert-kernel spectra and the block envelope every part uses
+#include "dd_audio_resample.h"      // R2   dd_resample_fft_f64 / _chunks, dd_rpoly_*
+#include "dd_audio_xcorr.h"         // X1, X2   dd_xcorr_norm_f64, dd_find_peaks_f64; the scan, the run-length correlation and the peak pick
+#include "dd_audio_sync.h"          // 8f-2  dd_noaa_sync_windows(_multi), dd_noaa_prepare
+#include "dd_audio_crude.h"         // P     dd_noaa_crude_tail
+#include "dd_audio_apt.h"           // APT image: dd_median_segments_f64, dd_apt_lines_f64, dd_apt_map_u8, dd_apt_color_u8
+
 // the stream is about to be destroyed (dd_stream_destroy, after it has been synchronised): its plans (with their work areas) and
 // its chirp-z tables go with it -- a later stream that happens to get the same address must not inherit a plan bound to a dead
 // stream, and dead entries must not fill the 64-entry chirp-z cache
@@ -189,14 +195,6 @@ void dd_audio_forget_stream(hipStream_t s) {
     }
     czt_forget_stream(dev, s);
 }
-
-// ---------------------------------------------------------------- the entry-point families (round 6: one file each, one translation unit)
-#include "dd_audio_envelope.h"      // A1   dd_am_envelope_f64; the Hilbert-kernel spectra and the block envelope every part uses
-#include "dd_audio_resample.h"      // R2   dd_resample_fft_f64 / _chunks, dd_rpoly_*
-#include "dd_audio_xcorr.h"         // X1, X2   dd_xcorr_norm_f64, dd_find_peaks_f64; the scan, the run-length correlation and the peak pick
-#include "dd_audio_sync.h"          // 8f-2  dd_noaa_sync_windows(_multi), dd_noaa_prepare
-#include "dd_audio_crude.h"         // P     dd_noaa_crude_tail
-#include "dd_audio_apt.h"           // APT image: dd_median_segments_f64, dd_apt_lines_f64, dd_apt_map_u8, dd_apt_color_u8
 
 // dd_code_warmup (dd_runtime.hip): the runtime loads a translation unit's code object when one of its kernels is first named
 int dd_code_touch_audio(void) {

@@ -1,15 +1,80 @@
 // A1: demod_am.demod -- abs(hilbert(x)) per block (demod_am.py:18-29, decode_noaa.py:644-653): dd_am_envelope_f64, and everything about
-// Hilbert envelopes that more than one part uses: the Hilbert-kernel spectra (closed forms, host transform, device and host caches)
-// and the block envelope through the own float64 transform (hc_block_envelope).
+// Hilbert envelopes that more than one part uses.  In the order of the file:
+//   * the block walk's PLAN (DDEnvWalk, envelope_plan): the chunker rule, the route of the full blocks and of the ragged last one, the
+//     work areas -- pure host code, which tests/host/envelope_plan_check.cpp compiles alone (DD_ENVELOPE_PLAN_ONLY);
+//   * the Hilbert-kernel spectra (closed forms, host transform, ONE walk through the device and host caches: hilbert_spectrum);
+//   * the four routes of one group of equal blocks -- own split / own plain (hc_block_envelope), the library's real transform pair
+//     (envelope_real_pair) and its zero-padded real convolution (envelope_padded, which the accurate-sync windows' stage shares);
+//   * the RUNNER envelope_walk, which dd_am_envelope_f64 (here) and dd_noaa_crude_tail call; dd_noaa_prepare reads the plan only.
 // The first of the six parts of dd_audio.hip (one translation unit: the parts share the plan cache, the float64 transform and the
 // scratch buffers of dd_audio.hip and are included there, each using only the parts before it).  Internal; not a stand-alone header.
-// ---------------------------------------------------------------- A1: abs(hilbert(x)) per block
+// ---------------------------------------------------------------- the block walk's plan (host only)
+static int64_t largest_prime_factor(int64_t n) {
+    int64_t best = 1;
+    for (int64_t p = 2; p * p <= n; ++p)
+        while (n % p == 0) { best = p; n /= p; }
+    return n > 1 ? n : best;
+}
+// cyclic length of dd_hconv_kernels.h for the envelope of a block of N real samples, 0 = not on this route; *split: the even / odd form
+static int64_t hc_block_len(int64_t N, bool* split) {
+    *split = false;
+    if (N < 2) return 0;
+    if ((N & 1) == 0 && N - 1 <= ((int64_t)1 << 18)) { *split = true; return N - 1 <= ((int64_t)1 << 17) ? (int64_t)1 << 17 : (int64_t)1 << 18; }
+    if (2 * N + 2 <= ((int64_t)1 << 17)) return (int64_t)1 << 17;
+    if (2 * N + 2 <= ((int64_t)1 << 18)) return (int64_t)1 << 18;
+    return 0;
+}
+// Route of a group of equal blocks.  Blocks that fit the own float64 transform go through it (a 240 000-sample block by the even / odd
+// split of the Hilbert kernel): no FFT-library plan, whose creation costs a process's first call 0.9 s.  The others, and all under
+// DD_AM_HILBERT=lib (tools / tests), take the library's real-to-complex / complex-to-real pair -- half the transform work of the complex
+// pair -- except a ragged last block whose length has a prime factor above 17 (under lib, 14 100 = 2^2 3 5^2 47 for a minute of audio): the library
+// would run Bluestein's algorithm, twenty launches, so it takes the zero-padded cyclic convolution with the Hilbert kernel that the
+// accurate-sync windows use, four launches and two power-of-two transforms.
+enum DDEnvRoute { DD_ENV_NONE = 0, DD_ENV_OWN_SPLIT, DD_ENV_OWN_PLAIN, DD_ENV_LIB_PAIR, DD_ENV_LIB_PADDED };
+struct DDEnvGroup {
+    DDEnvRoute route;
+    int64_t N, M;                     // block length; cyclic length (0 on DD_ENV_LIB_PAIR)
+};
+struct DDEnvWalk {
+    int64_t block, nfull, batch;      // nfull full blocks of `block` samples, and how many of them one group takes (16; own plain form: 1)
+    DDEnvGroup full, last;            // full.route = DD_ENV_NONE without full blocks; last.N = the remainder, 1 .. block
+    size_t T_elems, spec_elems, y_elems;      // work areas: complex image T (c128), spectrum (c128), real scratch y (f64)
+};
+static DDEnvGroup envelope_route(int64_t N, bool own_ok, bool last) {
+    bool split = false;
+    const int64_t M = own_ok ? hc_block_len(N, &split) : 0;
+    if (M) return DDEnvGroup{split ? DD_ENV_OWN_SPLIT : DD_ENV_OWN_PLAIN, N, M};
+    if (!(last && N >= 2 && largest_prime_factor(N) > 17)) return DDEnvGroup{DD_ENV_LIB_PAIR, N, 0};
+    int64_t Mp = 1;
+    while (Mp < 2 * N + 2) Mp <<= 1;
+    return DDEnvGroup{DD_ENV_LIB_PADDED, N, Mp};
+}
+// block list by the chunker rule (decode_noaa.py:644-653 via chunker.py:36-45): full blocks while one more fits strictly inside, then
+// the remainder (a full-size last block when n is an exact multiple).  n >= 1, block >= 1.
+static DDEnvWalk envelope_plan(int64_t n, int64_t block) {
+    static const char* amh_env = getenv("DD_AM_HILBERT");
+    const bool own_ok = !(amh_env && !strcmp(amh_env, "lib"));
+    DDEnvWalk w = {};
+    w.block = block;
+    w.nfull = (n - 1) / block;
+    w.last = envelope_route(n - w.nfull * block, own_ok, true);
+    if (w.nfull) w.full = envelope_route(block, own_ok, false);
+    w.batch = w.full.route == DD_ENV_OWN_PLAIN ? 1 : std::min<int64_t>(w.nfull, 16);
+    const DDEnvGroup* g[2] = {&w.full, &w.last};
+    for (int i = 0; i < 2; ++i) {
+        const int64_t jobs = i ? 1 : w.batch, N = g[i]->N, M = g[i]->M;
+        size_t T = 0, sp = 0, y = 0;
+        if (g[i]->route == DD_ENV_OWN_SPLIT || g[i]->route == DD_ENV_OWN_PLAIN) T = (size_t)(jobs * M);
+        if (g[i]->route == DD_ENV_LIB_PAIR) { sp = (size_t)(jobs * (N / 2 + 1)); y = (size_t)(jobs * N); }
+        if (g[i]->route == DD_ENV_LIB_PADDED) { sp = (size_t)(M / 2 + 1); y = (size_t)(2 * M); }
+        w.T_elems = std::max(w.T_elems, T); w.spec_elems = std::max(w.spec_elems, sp); w.y_elems = std::max(w.y_elems, y);
+    }
+    return w;
+}
+#ifndef DD_ENVELOPE_PLAN_ONLY
+// ---------------------------------------------------------------- abs(hilbert(x)) as scipy computes it (the accurate-sync windows' "fft" route)
 // scipy.signal.hilbert: Xf = fft(x); h[0] = 1, h[1..(N-1)/2 or N/2-1] = 2, h[N/2] = 1 (N even),
 // 0 elsewhere; ifft(Xf * h); demod_am takes the magnitude (demod_am.py:29).
-__global__ void __launch_bounds__(256) k_real_to_cplx(const double* __restrict__ in, double2* __restrict__ out, int64_t n) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) out[i] = make_double2(in[i], 0.0);
-}
 // blockIdx.y = block (or window) of the batch
 __global__ void __launch_bounds__(256) k_hilbert_mask_b(double2* __restrict__ X, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -113,7 +178,7 @@ static void kernel_spectrum_host(const std::vector<double>& img, int64_t M, std:
     const double sc = 1.0 / (double)M;
     for (int64_t k = 0; k < nb; ++k) h[(size_t)k] = make_double2(v[(size_t)k].real() * sc, v[(size_t)k].imag() * sc);
     if (own) {
-        const int lg = M == ((int64_t)1 << 18) ? 9 : 8;
+        const int lg = hc_lg(M);
         for (int64_t i = 0; i < M; ++i) {
             const int64_t k = (i >> lg) + DD_HC_N * (i & (((int64_t)1 << lg) - 1));
             h[(size_t)(nb + i)] = make_double2(v[(size_t)k].real() * sc, v[(size_t)k].imag() * sc);
@@ -174,7 +239,6 @@ static int lg_of(int64_t M) {
 // hh[n] = imag(ifft(h))[n] = (2/N) sum_{k=1..m} sin(2 pi k n / N), m = the number of doubled bins of scipy's mask
 // ((N-1)/2 for odd N, N/2 - 1 for even N) = (2/N) sin(pi m n/N) sin(pi (m+1) n/N) / sin(pi n/N): a closed form, so no
 // length-N (Bluestein) plan is ever built for it; accurate to a few 1e-17 (checked against a long-double sum).
-static std::pair<int, int64_t> hilbert_kernel_key(int dev, int64_t n, int64_t M) { return std::make_pair(dev, (n << 6) | lg_of(M)); }      // (length and cyclic length)
 static void hilbert_kernel_host(int64_t n, int64_t M, std::vector<double2>& h) {
     const int64_t m = (n & 1) ? (n - 1) / 2 : n / 2 - 1;
     std::vector<double> host((size_t)M, 0.0);                 // buf[j mod M] = hh[j mod N], j in [-(N-1), N-1]
@@ -185,29 +249,12 @@ static void hilbert_kernel_host(int64_t n, int64_t M, std::vector<double2>& h) {
     }
     kernel_spectrum_host(host, M, h);
 }
-static int hilbert_kernel_spectrum(int64_t n, int64_t M, const double2** out, hipStream_t s) {
-    int dev = 0;
-    DD_HIP_CHECK(hipGetDevice(&dev));
-    const auto key = hilbert_kernel_key(dev, n, M);
-    auto it = g_hilb.find(key);
-    if (it != g_hilb.end()) { *out = it->second; return DD_OK; }
-    std::vector<double2> h;
-    const std::vector<double2>* hp = hilb_host_find(key);
-    if (!hp) { hilbert_kernel_host(n, M, h); hp = hilb_host_keep(key, h); }
-    DDDevBuf<double2> HH;
-    const int rc = kernel_spectrum_put(hp ? *hp : h, &HH, s);
-    if (rc != DD_OK) return rc;
-    *out = hilb_cache_put(key, HH);
-    return DD_OK;
-}
-
 // The Hilbert kernel of an EVEN length N is zero at even lags, hh[2j] = 0, hh[2j+1] = (2/N) cot(pi (2j+1) / N) =: g[j]: the length-N circular
 // convolution falls apart into two of length N/2 with the same kernel,
 //     H(x)[2m+1] = (g (*) x_even)[m]        H(x)[2m] = (g (*) x_odd)[m-1]        (indices mod N/2)
 // and z = x_even + j x_odd carries both through ONE complex convolution.  decode_noaa.py:647-653 takes the envelope in blocks of 240 000
 // samples: two length-120 000 convolutions fit the cyclic length 2^18 of dd_hconv_kernels.h (>= 2 (N/2) - 1), the block itself does not
 // (it would need 2^19).  This is g's spectrum for that image -- g[j mod N/2] at lags j in [-(N/2 - 1), N/2 - 1] -- in row-pass order.
-static std::pair<int, int64_t> hilbert_split_key(int dev, int64_t N, int64_t M) { return std::make_pair(dev, -((N << 6) | lg_of(M))); }    // (negative: the split kernel of length N, beside the full ones)
 static void hilbert_split_host(int64_t N, int64_t M, std::vector<double2>& h) {
     const int64_t N2 = N / 2;
     std::vector<double> host((size_t)M, 0.0);
@@ -222,22 +269,33 @@ static void hilbert_split_host(int64_t N, int64_t M, std::vector<double2>& h) {
     }
     kernel_spectrum_host(host, M, h);
 }
-static int hilbert_split_spectrum(int64_t N, int64_t M, const double2** out_perm, hipStream_t s) {
+// (length and cyclic length; negative: the split kernel of length n, beside the full ones)
+static std::pair<int, int64_t> hilbert_key(int dev, int64_t n, int64_t M, bool split) {
+    const int64_t k = (n << 6) | lg_of(M);
+    return std::make_pair(dev, split ? -k : k);
+}
+static void hilbert_host(int64_t n, int64_t M, bool split, std::vector<double2>& h) {
+    if (split) hilbert_split_host(n, M, h); else hilbert_kernel_host(n, M, h);
+}
+// ONE walk for both kernels: device cache, host cache, build, keep, upload, put.  *out: the M/2 + 1 bins of the library's real
+// transforms; for the lengths of dd_hconv_kernels.h the row-pass order follows at *out + M/2 + 1.  The caller holds g_sync_mu.
+static int hilbert_spectrum(int64_t n, int64_t M, bool split, const double2** out, hipStream_t s) {
     int dev = 0;
     DD_HIP_CHECK(hipGetDevice(&dev));
-    const auto key = hilbert_split_key(dev, N, M);
+    const auto key = hilbert_key(dev, n, M, split);
     auto it = g_hilb.find(key);
-    if (it != g_hilb.end()) { *out_perm = it->second + (M / 2 + 1); return DD_OK; }
+    if (it != g_hilb.end()) { *out = it->second; return DD_OK; }
     std::vector<double2> h;
     const std::vector<double2>* hp = hilb_host_find(key);
-    if (!hp) { hilbert_split_host(N, M, h); hp = hilb_host_keep(key, h); }
+    if (!hp) { hilbert_host(n, M, split, h); hp = hilb_host_keep(key, h); }
     DDDevBuf<double2> HH;
     const int rc = kernel_spectrum_put(hp ? *hp : h, &HH, s);
     if (rc != DD_OK) return rc;
-    *out_perm = hilb_cache_put(key, HH) + (M / 2 + 1);
+    *out = hilb_cache_put(key, HH);
     return DD_OK;
 }
 
+// ---------------------------------------------------------------- the four routes of one group of equal blocks
 // a block of real float64 audio as the source and its envelope as the sink of the three launches; job = block.
 // Split form (even block length N): element n of the image = (x[2n], x[2n+1]), n < N/2; result element m = (H(x)[2m+1], H(x)[2(m+1)]).
 struct HcBlkSplitIO {
@@ -269,56 +327,85 @@ struct HcBlkRealIO {
     __device__ void put(int, int64_t i, double2 y) const { if (i < n) env[i] = hypot(x[i], y.x); }
 };
 // envelope of `jobs` blocks of N samples each (x + job N) through dd_hconv_kernels.h; T: [jobs][M] c128 work buffer.  split: the
-// even / odd form above (N even, N - 1 <= M); else the plain form (one block, 2 N + 2 <= M).  DD_ERR_UNSUPPORTED: the caller's other route.
+// even / odd form above (N even, N - 1 <= M); else the plain form (one block, 2 N + 2 <= M).  M: hc_block_len's.
 static int hc_block_envelope(const double* x, double* env, int64_t N, int jobs, bool split, int64_t M, double2* T, hipStream_t s) {
-    if (!hc_length_ok(M)) return DD_ERR_UNSUPPORTED;
-    const int lg = M == ((int64_t)1 << 18) ? 9 : 8;
-    const double2 *TA = nullptr, *TB = nullptr;
-    int rc = hc_tables(lg, &TA, &TB);
+    const double2* HH = nullptr;
+    const int rc = hilbert_spectrum(N, M, split, &HH, s);
     if (rc != DD_OK) return rc;
-    const double2* HHp = nullptr;
+    const HcOneSpec sp = {HH + (M / 2 + 1)};
     if (split) {
-        rc = hilbert_split_spectrum(N, M, &HHp, s);
-        if (rc != DD_OK) return rc;
         const HcBlkSplitIO io = {x, env, N, N / 2};
-        const HcOneSpec sp = {HHp};
-        if (lg == 9) { rc = hc_ready<9, HcBlkSplitIO, HcBlkSplitIO>(); if (rc == DD_OK) hc_convolve<9>(io, sp, io, T, jobs, TA, TB, s); }
-        else { rc = hc_ready<8, HcBlkSplitIO, HcBlkSplitIO>(); if (rc == DD_OK) hc_convolve<8>(io, sp, io, T, jobs, TA, TB, s); }
-    } else {
-        const double2* HH = nullptr;
-        rc = hilbert_kernel_spectrum(N, M, &HH, s);
-        if (rc != DD_OK) return rc;
-        HHp = HH + (M / 2 + 1);
-        const HcBlkRealIO io = {x, env, N};
-        const HcOneSpec sp = {HHp};
-        if (lg == 9) { rc = hc_ready<9, HcBlkRealIO, HcBlkRealIO>(); if (rc == DD_OK) hc_convolve<9>(io, sp, io, T, 1, TA, TB, s); }
-        else { rc = hc_ready<8, HcBlkRealIO, HcBlkRealIO>(); if (rc == DD_OK) hc_convolve<8>(io, sp, io, T, 1, TA, TB, s); }
+        return hc_run(M, io, sp, io, T, jobs, s);
     }
-    return rc;
+    const HcBlkRealIO io = {x, env, N};
+    return hc_run(M, io, sp, io, T, 1, s);
 }
 
-// cyclic length of dd_hconv_kernels.h for the envelope of a block of N real samples, 0 = not on this route; *split: the even / odd form
-static int64_t hc_block_len(int64_t N, bool* split) {
-    if (N < 2) return 0;
-    if ((N & 1) == 0 && N - 1 <= ((int64_t)1 << 18)) { *split = true; return N - 1 <= ((int64_t)1 << 17) ? (int64_t)1 << 17 : (int64_t)1 << 18; }
-    *split = false;
-    if (2 * N + 2 <= ((int64_t)1 << 17)) return (int64_t)1 << 17;
-    if (2 * N + 2 <= ((int64_t)1 << 18)) return (int64_t)1 << 18;
-    return 0;
+// The library's real pair: envelope = hypot(x, H x) with H x from a real-to-complex / complex-to-real transform pair per block (bin k of
+// the spectrum times -j for 0 < k < N/2, zero at DC and Nyquist: the imaginary part of scipy.signal.hilbert's analytic signal), `batch`
+// consecutive blocks of N samples in one batched pair.  spec: [batch][N/2 + 1], y: [batch][N]
+__global__ void __launch_bounds__(256) k_hilb_bins(double2* __restrict__ S, int64_t nb, int64_t N) {
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= nb) return;
+    double2* p = S + (int64_t)blockIdx.y * nb + k;
+    const double2 v = *p;
+    const bool zero = k == 0 || (2 * k == N);
+    *p = zero ? make_double2(0.0, 0.0) : make_double2(v.y, -v.x);          // -j X[k]
 }
-
-// `batch` consecutive blocks of n samples each: one batched transform pair
-static int envelope_blocks(const double* in, double* out, int64_t n, int batch, double2* work, hipStream_t s) {
-    hipfftHandle plan;
-    int rc = get_plan(&plan, HIPFFT_Z2Z, n, batch, s);
+__global__ void __launch_bounds__(256) k_env_hypot_flat(const double* __restrict__ x, const double* __restrict__ y, double* __restrict__ env, int64_t n, double inv_n) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) env[i] = hypot(x[i], y[i] * inv_n);
+}
+static int envelope_real_pair(const double* x, double* env, int64_t N, int batch, double2* spec, double* y, hipStream_t s) {
+    hipfftHandle pf, pb;
+    int rc = get_plan(&pf, HIPFFT_D2Z, N, batch, s);
+    if (rc == DD_OK) rc = get_plan(&pb, HIPFFT_Z2D, N, batch, s);
     if (rc != DD_OK) return rc;
-    hipLaunchKernelGGL(k_real_to_cplx, dim3(grid1(n * batch)), dim3(256), 0, s, in, work, n * batch);
-    DD_FFT_CHECK(hipfftExecZ2Z(plan, (hipfftDoubleComplex*)work, (hipfftDoubleComplex*)work, HIPFFT_FORWARD));
-    hipLaunchKernelGGL(k_hilbert_mask_b, dim3(grid1(n), batch), dim3(256), 0, s, work, n);
-    DD_FFT_CHECK(hipfftExecZ2Z(plan, (hipfftDoubleComplex*)work, (hipfftDoubleComplex*)work, HIPFFT_BACKWARD));
-    hipLaunchKernelGGL(k_cplx_abs_b, dim3(grid1(n), batch), dim3(256), 0, s, work, out, n, 1.0 / (double)n);
-    DD_LAUNCH_CHECK();
+    const int64_t nb = N / 2 + 1;
+    DD_FFT_CHECK(hipfftExecD2Z(pf, (hipfftDoubleReal*)x, (hipfftDoubleComplex*)spec));
+    hipLaunchKernelGGL(k_hilb_bins, dim3(grid1(nb), batch), dim3(256), 0, s, spec, nb, N);
+    DD_FFT_CHECK(hipfftExecZ2D(pb, (hipfftDoubleComplex*)spec, (hipfftDoubleReal*)y));
+    hipLaunchKernelGGL(k_env_hypot_flat, dim3(grid1(N * batch)), dim3(256), 0, s, x, y, env, N * batch, 1.0 / (double)N);
     return DD_OK;
+}
+// The zero-padded real convolution behind its pad kernel: XR [batch][M] holds the padded images (k_pad_f64 here, k_sync_fm_pad for the
+// accurate-sync windows), HH the kernel spectrum of hilbert_spectrum(n, M, false); SP: [batch][M/2 + 1], YR: [batch][M]; env: [batch][n]
+__global__ void __launch_bounds__(256) k_pad_f64(const double* __restrict__ x, int64_t n, double* __restrict__ XR, int64_t M) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j < M) XR[j] = j < n ? x[j] : 0.0;
+}
+static int envelope_padded(double* XR, double2* SP, double* YR, const double2* HH, int64_t M, int64_t n, int batch, double* env, hipStream_t s) {
+    hipfftHandle pf, pb;
+    int rc = get_plan(&pf, HIPFFT_D2Z, M, batch, s);
+    if (rc == DD_OK) rc = get_plan(&pb, HIPFFT_Z2D, M, batch, s);
+    if (rc != DD_OK) return rc;
+    const int64_t nb = M / 2 + 1;
+    DD_FFT_CHECK(hipfftExecD2Z(pf, XR, (hipfftDoubleComplex*)SP));
+    hipLaunchKernelGGL(k_spec_mul, dim3(grid1(nb), batch), dim3(256), 0, s, SP, HH, nb);
+    DD_FFT_CHECK(hipfftExecZ2D(pb, (hipfftDoubleComplex*)SP, YR));
+    hipLaunchKernelGGL(k_env_hypot, dim3(grid1(n), batch), dim3(256), 0, s, XR, YR, M, n, env);
+    return DD_OK;
+}
+
+// ---------------------------------------------------------------- the runner
+static int envelope_group(const DDEnvGroup& g, const double* x, double* env, int jobs, double2* T, double2* spec, double* y, hipStream_t s) {
+    if (g.route == DD_ENV_LIB_PAIR) return envelope_real_pair(x, env, g.N, jobs, spec, y, s);
+    if (g.route != DD_ENV_LIB_PADDED) return hc_block_envelope(x, env, g.N, jobs, g.route == DD_ENV_OWN_SPLIT, g.M, T, s);
+    const double2* HH = nullptr;
+    const int rc = hilbert_spectrum(g.N, g.M, false, &HH, s);
+    if (rc != DD_OK) return rc;
+    hipLaunchKernelGGL(k_pad_f64, dim3(grid1(g.M)), dim3(256), 0, s, x, g.N, y, g.M);
+    return envelope_padded(y, spec, y + g.M, HH, g.M, g.N, 1, env, s);
+}
+// enqueues the whole envelope of x [n] by the plan w = envelope_plan(n, block); T, spec, y: w's element counts.  The caller holds
+// g_sync_mu (the spectrum cache) and keeps the three work areas until the stream has run
+static int envelope_walk(const DDEnvWalk& w, const double* x, double* env, double2* T, double2* spec, double* y, hipStream_t s) {
+    int rc = DD_OK;
+    for (int64_t b0 = 0; b0 < w.nfull && rc == DD_OK; b0 += w.batch)
+        rc = envelope_group(w.full, x + b0 * w.block, env + b0 * w.block, (int)std::min(w.nfull - b0, w.batch), T, spec, y, s);
+    if (rc == DD_OK) rc = envelope_group(w.last, x + w.nfull * w.block, env + w.nfull * w.block, 1, T, spec, y, s);
+    if (rc == DD_OK) DD_LAUNCH_CHECK();
+    return rc;
 }
 
 extern "C" int dd_am_envelope_f64(const double* in, double* out, int64_t n, int64_t block, void* stream) {
@@ -326,45 +413,13 @@ extern "C" int dd_am_envelope_f64(const double* in, double* out, int64_t n, int6
     if (n == 0) return DD_OK;
     DD_REQUIRE(in && out, "null buffer");
     hipStream_t s = dd_stream(stream);
-    // block list by the chunker rule (decode_noaa.py:644-653 via chunker.py:36-45): full blocks while one more
-    // fits strictly inside, then the remainder (a full-size last block when n is an exact multiple)
-    int64_t nfull = 0;
-    while ((nfull + 1) * block < n) ++nfull;
-    const int64_t rem = n - nfull * block;                  // 1 .. block
-    const int GB = 16;                                       // full blocks per batched transform
-    const int64_t gb = nfull < GB ? nfull : GB;
-    // Round 5: blocks that fit the own float64 transform go through it (hc_block_envelope: a 240 000-sample block by the even / odd split
-    // of the Hilbert kernel) -- no FFT-library plan, whose creation costs a process's first call 0.9 s.  DD_AM_HILBERT=lib: the library.
-    static const char* amh_env = getenv("DD_AM_HILBERT");
-    const bool own_ok = !(amh_env && !strcmp(amh_env, "lib"));
-    bool split_b = false, split_r = false;
-    const int64_t Mb = (own_ok && nfull > 0) ? hc_block_len(block, &split_b) : 0;
-    const int64_t Mr = own_ok ? hc_block_len(rem, &split_r) : 0;
-    const int64_t wlen = nfull ? std::max<int64_t>(Mb ? (split_b ? gb * Mb : Mb) : 0, Mb ? 0 : gb * block) : 0;
-    const int64_t wrem = Mr ? Mr : rem;
-    DDScratchLock scr;                      // held until this entry point has enqueued everything
-    int rc = scr.get(sizeof(double2) * (size_t)(wlen > wrem ? wlen : wrem), s);
-    char* base = scr.ptr;
+    const DDEnvWalk w = envelope_plan(n, block);
+    auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t o_spec = al(sizeof(double2) * w.T_elems), o_y = o_spec + al(sizeof(double2) * w.spec_elems);
+    DDScratchLock scr;                      // held until this entry point has enqueued everything; it returns with the work in flight
+    const int rc = scr.get(o_y + sizeof(double) * w.y_elems, s);
     if (rc != DD_OK) return rc;
-    double2* work = reinterpret_cast<double2*>(base);
-    if (Mb) {
-        std::lock_guard<std::mutex> lk(g_sync_mu);           // (the kernel-spectrum cache)
-        const int per = split_b ? (int)gb : 1;
-        for (int64_t b0 = 0; b0 < nfull && rc == DD_OK; b0 += per)
-            rc = hc_block_envelope(in + b0 * block, out + b0 * block, block, (int)(nfull - b0 < per ? nfull - b0 : per), split_b, Mb, work, s);
-    } else {
-        for (int64_t b0 = 0; b0 < nfull && rc == DD_OK; b0 += GB) {
-            const int nbk = (int)(nfull - b0 < GB ? nfull - b0 : GB);
-            rc = envelope_blocks(in + b0 * block, out + b0 * block, block, nbk, work, s);
-        }
-    }
-    if (rc == DD_OK) {
-        if (Mr) {
-            std::lock_guard<std::mutex> lk(g_sync_mu);
-            rc = hc_block_envelope(in + nfull * block, out + nfull * block, rem, 1, split_r, Mr, work, s);
-        } else {
-            rc = envelope_blocks(in + nfull * block, out + nfull * block, rem, 1, work, s);
-        }
-    }
-    return rc;
+    std::lock_guard<std::mutex> lk(g_sync_mu);
+    return envelope_walk(w, in, out, (double2*)scr.ptr, (double2*)(scr.ptr + o_spec), (double*)(scr.ptr + o_y), s);
 }
+#endif  // DD_ENVELOPE_PLAN_ONLY

@@ -1,25 +1,20 @@
-// R2: commSignal.bwLim(strict) = scipy.signal.resample (comm.py:110-116): dd_resample_fft_f64, dd_resample_fft_chunks, the chirp-z form, and the polyphase extension dd_rpoly_*
+// R2: commSignal.bwLim(strict) = scipy.signal.resample (comm.py:110-116): dd_resample_fft_chunks -- per target length one chirp-z batch for
+// the lengths the library would transform by Bluestein (its convolution through hc_run where the length fits), batched library plans
+// per (length, target) group for the rest -- and dd_resample_fft_f64, which is that entry's arithmetic for one chunk; the Nyquist rule
+// (dd_rs_nyquist) and the scatter (k_rs_scatter) exist once for both routes.  And the polyphase extension dd_rpoly_*.
 // One of the six parts of dd_audio.hip (one translation unit: the parts share the plan cache, the float64 transform and the scratch
 // buffers of dd_audio.hip and are included there, each using only the parts before it).  Internal; not a stand-alone header.
 // ---------------------------------------------------------------- R2: scipy.signal.resample (real input)
 // X = rfft(x); Y[:nyq] = X[:nyq] (nyq = min(num,Nx)/2 + 1), Nyquist bin doubled when
 // down-sampling / halved when up-sampling an even N; y = irfft(Y, num) * num / Nx.
-__global__ void __launch_bounds__(256) k_resample_bins(const double2* __restrict__ X, double2* __restrict__ Y, int64_t nx_bins,
-                                                       int64_t ny_bins, int64_t N, int64_t num, int64_t Nx) {
-    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (k >= ny_bins) return;
-    const int64_t nyq = N / 2 + 1;
-    double2 v = make_double2(0.0, 0.0);
-    if (k < nyq && k < nx_bins) v = X[k];
+// THE Nyquist rule: v = bin k of the kept ones, N = min(num, n).  The kept Nyquist bin of an even N collects both halves when
+// down-sampling (num < n) and is shared between two bins when up-sampling (n < num)
+__device__ __forceinline__ double2 dd_rs_nyquist(double2 v, int64_t k, int64_t N, bool down, bool up) {
     if ((N & 1) == 0 && k == N / 2) {
-        if (num < Nx) { v.x *= 2.0; v.y *= 2.0; }
-        else if (Nx < num) { v.x *= 0.5; v.y *= 0.5; }
+        if (down) { v.x *= 2.0; v.y *= 2.0; }
+        else if (up) { v.x *= 0.5; v.y *= 0.5; }
     }
-    Y[k] = v;
-}
-__global__ void __launch_bounds__(256) k_scale_f64(double* __restrict__ y, int64_t n, double f) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) y[i] *= f;
+    return v;
 }
 
 // ---------------------------------------------------------------- polyphase rational resampler (stream form)
@@ -178,12 +173,6 @@ __global__ void __launch_bounds__(256) k_czt_tables(double2* __restrict__ w, dou
     }
 }
 
-static int64_t largest_prime_factor(int64_t n) {
-    int64_t best = 1;
-    for (int64_t p = 2; p * p <= n; ++p)
-        while (n % p == 0) { best = p; n /= p; }
-    return n > 1 ? n : best;
-}
 // the chirp-z route pays when the library would run Bluestein itself (radices up to 17 are native) and few bins are kept
 static bool czt_wanted(int64_t n, int64_t num) {
     if (!(num < n && n >= 256)) return false;
@@ -214,8 +203,7 @@ static int czt_tables(int64_t n, int64_t K, int64_t L, hipStream_t s, const DDCz
         }
         if (hc_length_ok(L)) {
             DD_HIP_CHECK(t.bspec_p.alloc((size_t)L));
-            if (L == ((int64_t)1 << 18)) hipLaunchKernelGGL(k_hc_perm<9>, dim3((unsigned)(L / 256)), dim3(256), 0, s, t.bspec.get(), t.bspec_p.get(), 0, 1.0 / (double)L);
-            else hipLaunchKernelGGL(k_hc_perm<8>, dim3((unsigned)(L / 256)), dim3(256), 0, s, t.bspec.get(), t.bspec_p.get(), 0, 1.0 / (double)L);
+            hc_perm(L, t.bspec.get(), t.bspec_p.get(), 0, 1.0 / (double)L, s);
         }
         it = g_czt.emplace(key, std::move(t)).first;
     }
@@ -230,7 +218,11 @@ struct DDCztJob {
     double scale;                                          // 1 / n
 };
 #define DD_CZT_MAXB 16
-struct DDCztJobs { DDCztJob j[DD_CZT_MAXB]; };             // passed by value: no upload per call
+struct DDCztJobs {                                         // passed by value: no upload per call
+    DDCztJob j[DD_CZT_MAXB];
+    __device__ int64_t out_off(int b) const { return j[b].out_off; }
+    __device__ double scale(int b) const { return j[b].scale; }
+};
 // source, spectrum and sink of the chirp convolution as three launches of dd_hconv_kernels.h: a[m] = x[m] w[m] (m < n, zero
 // beyond), times the chirp's spectrum (1 / L folded in), and of the result the K lowest elements times w[k] -- k_czt_pre, k_czt_mul
 // and k_czt_bins inside the column and row passes, the library's two length-L transforms replaced
@@ -256,9 +248,8 @@ struct HcCztDst : HcCztIO {
     __device__ void put(int job, int64_t k, double2 c) const {
         if (k >= K) return;
         const double2 w = jobs.j[job].w[k];
-        double2 v = make_double2(c.x * w.x - c.y * w.y, c.x * w.y + c.y * w.x);
-        if ((num & 1) == 0 && k == num / 2) { v.x *= 2.0; v.y *= 2.0; }
-        Y[(int64_t)job * K + k] = v;
+        const double2 v = make_double2(c.x * w.x - c.y * w.y, c.x * w.y + c.y * w.x);
+        Y[(int64_t)job * K + k] = dd_rs_nyquist(v, k, num, true, false);
     }
 };
 struct HcCztSpec {
@@ -287,7 +278,7 @@ __global__ void __launch_bounds__(256) k_czt_mul(double2* __restrict__ A, const 
     *p = make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
 }
 // bins 0 .. num/2 of the length-n transform -> the half spectrum the length-num inverse takes (scipy.signal.resample, real
-// input, downsampling: the kept Nyquist bin of an even num collects both halves; same rule as k_rs_bins_b)
+// input; the chirp-z route only down-samples: dd_rs_nyquist)
 __global__ void __launch_bounds__(256) k_czt_bins(const double2* __restrict__ A, const DDCztJobs jobs, int64_t L, double2* __restrict__ Y, int64_t ny_bins,
                                                   int64_t num) {
     const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -296,13 +287,14 @@ __global__ void __launch_bounds__(256) k_czt_bins(const double2* __restrict__ A,
     const double2 c = A[(int64_t)blockIdx.y * L + k];
     const double2 w = j.w[k];
     const double il = 1.0 / (double)L;
-    double2 v = make_double2((c.x * w.x - c.y * w.y) * il, (c.x * w.y + c.y * w.x) * il);
-    if ((num & 1) == 0 && k == num / 2) { v.x *= 2.0; v.y *= 2.0; }
-    Y[(int64_t)blockIdx.y * ny_bins + k] = v;
+    const double2 v = make_double2((c.x * w.x - c.y * w.y) * il, (c.x * w.y + c.y * w.x) * il);
+    Y[(int64_t)blockIdx.y * ny_bins + k] = dd_rs_nyquist(v, k, num, true, false);
 }
-__global__ void __launch_bounds__(256) k_czt_scatter(const double* __restrict__ src, const DDCztJobs jobs, int64_t num, double* __restrict__ out) {
+// results [batch][num] -> out at every job's offset, times its scale; JOBS: DDCztJobs (by value) or DDRsJobs (the uploaded table)
+template <typename JOBS>
+__global__ void __launch_bounds__(256) k_rs_scatter(const double* __restrict__ src, const JOBS jobs, int64_t num, double* __restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < num) out[jobs.j[blockIdx.y].out_off + i] = src[(int64_t)blockIdx.y * num + i] * jobs.j[blockIdx.y].scale;
+    if (i < num) out[jobs.out_off(blockIdx.y) + i] = src[(int64_t)blockIdx.y * num + i] * jobs.scale(blockIdx.y);
 }
 
 // chunks idx[0..B) (all with target length num, every one wanted by czt_wanted), at most DD_CZT_MAXB per batch
@@ -357,13 +349,8 @@ static int resample_czt_batch(const void* in, int in_is_f32, const int64_t* in_o
             src.in = in; src.in_is_f32 = in_is_f32; src.jobs = jobs; src.Y = Y; src.K = K; src.num = num;
             static_cast<HcCztIO&>(dst) = static_cast<const HcCztIO&>(src);
             sp.jobs = jobs;
-            const double2 *TA = nullptr, *TB = nullptr;
-            const int lg = L == ((int64_t)1 << 18) ? 9 : 8;
-            rc = hc_tables(lg, &TA, &TB);
-            if (rc == DD_OK) rc = lg == 9 ? hc_ready<9, HcCztSrc, HcCztDst>() : hc_ready<8, HcCztSrc, HcCztDst>();
+            rc = hc_run(L, src, sp, dst, A, B, s);
             if (rc != DD_OK) return rc;
-            if (lg == 9) hc_convolve<9>(src, sp, dst, A, B, TA, TB, s);
-            else hc_convolve<8>(src, sp, dst, A, B, TA, TB, s);
         } else {
             if (in_is_f32) hipLaunchKernelGGL(k_czt_pre<float>, dim3(grid1(L), B), dim3(256), 0, s, (const float*)in, jobs, L, A);
             else hipLaunchKernelGGL(k_czt_pre<double>, dim3(grid1(L), B), dim3(256), 0, s, (const double*)in, jobs, L, A);
@@ -373,52 +360,13 @@ static int resample_czt_batch(const void* in, int in_is_f32, const int64_t* in_o
             hipLaunchKernelGGL(k_czt_bins, dim3(grid1(K), B), dim3(256), 0, s, A, jobs, L, Y, K, num);
         }
         const hipfftResult r3 = hipfftExecZ2D(pb, (hipfftDoubleComplex*)Y, res);
-        hipLaunchKernelGGL(k_czt_scatter, dim3(grid1(num), B), dim3(256), 0, s, res, jobs, num, out);
+        hipLaunchKernelGGL(k_rs_scatter<DDCztJobs>, dim3(grid1(num), B), dim3(256), 0, s, res, jobs, num, out);
         if (r1 != HIPFFT_SUCCESS || r2 != HIPFFT_SUCCESS || r3 != HIPFFT_SUCCESS) {
             dd_set_error("hipfft exec failed (%d, %d, %d)", (int)r1, (int)r2, (int)r3);
             return DD_ERR_HIP;
         }
         DD_LAUNCH_CHECK();
     }
-    return DD_OK;
-}
-
-extern "C" int dd_resample_fft_f64(const double* in, double* out, int64_t n, int64_t num, void* stream) {
-    DD_REQUIRE(n >= 1 && num >= 1, "n/num");
-    DD_REQUIRE(in && out, "null buffer");
-    hipStream_t s = dd_stream(stream);
-    if (czt_wanted(n, num)) {
-        const int64_t zero = 0;
-        const int rc = resample_czt_batch(in, 0, &zero, &n, out, &zero, num, std::vector<int>{0}, s);
-        if (rc != 1) return rc;
-    }
-    hipfftHandle pf, pb;
-    int rc = get_plan(&pf, HIPFFT_D2Z, n, 1, s);
-    if (rc != DD_OK) return rc;
-    rc = get_plan(&pb, HIPFFT_Z2D, num, 1, s);
-    if (rc != DD_OK) return rc;
-    const int64_t nxb = n / 2 + 1, nyb = num / 2 + 1;
-    const size_t bx = (sizeof(double2) * nxb + 255) & ~(size_t)255, by = (sizeof(double2) * nyb + 255) & ~(size_t)255;
-    const size_t need = bx + by + sizeof(double) * n;
-    char* base = nullptr;
-    DDScratchLock scr;                      // held until this entry point has enqueued everything
-    rc = scr.get(need, s);
-    base = scr.ptr;
-    if (rc != DD_OK) return rc;
-    double2* X = reinterpret_cast<double2*>(base);
-    double2* Y = reinterpret_cast<double2*>(base + bx);
-    double* tmp = reinterpret_cast<double*>(base + bx + by);               // D2Z may overwrite its input: work on a copy
-    DD_HIP_CHECK(hipMemcpyAsync(tmp, in, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
-    hipfftResult r1 = hipfftExecD2Z(pf, tmp, (hipfftDoubleComplex*)X);
-    const int64_t N = num < n ? num : n;
-    hipLaunchKernelGGL(k_resample_bins, dim3(grid1(nyb)), dim3(256), 0, s, X, Y, nxb, nyb, N, num, n);
-    hipfftResult r2 = hipfftExecZ2D(pb, (hipfftDoubleComplex*)Y, out);
-    hipLaunchKernelGGL(k_scale_f64, dim3(grid1(num)), dim3(256), 0, s, out, num, 1.0 / (double)n);
-    if (r1 != HIPFFT_SUCCESS || r2 != HIPFFT_SUCCESS) {
-        dd_set_error("hipfft exec failed (%d, %d)", (int)r1, (int)r2);
-        return DD_ERR_HIP;
-    }
-    DD_LAUNCH_CHECK();
     return DD_OK;
 }
 
@@ -436,23 +384,15 @@ __global__ void __launch_bounds__(256) k_rs_bins_b(const double2* __restrict__ X
     if (k >= ny_bins) return;
     X += (int64_t)blockIdx.y * nx_bins;
     Y += (int64_t)blockIdx.y * ny_bins;
-    // scipy.signal.resample for real input (rfft route): keep the first N/2+1 bins; the Nyquist bin of the SHORTER length is
-    // halved when downsampling / doubled... same rule as k_resample_bins
-    double2 v = make_double2(0.0, 0.0);
-    const int64_t nyq = N / 2;
-    if (k < nx_bins && k <= nyq) {
-        v = X[k];
-        if (N % 2 == 0 && k == nyq) {
-            if (num < n) { v.x *= 2.0; v.y *= 2.0; }      // downsampling: the kept Nyquist bin collects both halves
-            else if (num > n) { v.x *= 0.5; v.y *= 0.5; }
-        }
-    }
-    Y[k] = v;
+    // scipy.signal.resample for real input (rfft route): keep the first N/2 + 1 bins of the SHORTER length N
+    Y[k] = (k < nx_bins && k <= N / 2) ? dd_rs_nyquist(X[k], k, N, num < n, n < num) : make_double2(0.0, 0.0);
 }
-__global__ void __launch_bounds__(256) k_rs_scatter(const double* __restrict__ src, const DDRsJob* __restrict__ jobs, int64_t num, double scale, double* __restrict__ out) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < num) out[jobs[blockIdx.y].out_off + i] = src[(int64_t)blockIdx.y * num + i] * scale;
-}
+struct DDRsJobs {                                          // the uploaded table of a group and the group's scale 1 / n
+    const DDRsJob* j;
+    double sc;
+    __device__ int64_t out_off(int b) const { return j[b].out_off; }
+    __device__ double scale(int) const { return sc; }
+};
 
 extern "C" int dd_resample_fft_chunks(const void* in, int in_is_f32, const int64_t* in_off_host, const int64_t* n_host, double* out,
                                       const int64_t* out_off_host, const int64_t* num_host, int count, void* stream) {
@@ -502,12 +442,54 @@ extern "C" int dd_resample_fft_chunks(const void* in, int in_is_f32, const int64
         const int64_t N = num < n ? num : n;
         hipLaunchKernelGGL(k_rs_bins_b, dim3(grid1(nyb), B), dim3(256), 0, s, X, Y, nxb, nyb, N, num, n);
         hipfftResult r2 = hipfftExecZ2D(pb, (hipfftDoubleComplex*)Y, res);
-        hipLaunchKernelGGL(k_rs_scatter, dim3(grid1(num), B), dim3(256), 0, s, res, dj, num, 1.0 / (double)n, out);
+        hipLaunchKernelGGL(k_rs_scatter<DDRsJobs>, dim3(grid1(num), B), dim3(256), 0, s, res, DDRsJobs{dj, 1.0 / (double)n}, num, out);
         if (r1 != HIPFFT_SUCCESS || r2 != HIPFFT_SUCCESS) {
             dd_set_error("hipfft exec failed (%d, %d)", (int)r1, (int)r2);
             return DD_ERR_HIP;
         }
         DD_LAUNCH_CHECK();
     }
+    return DD_OK;
+}
+
+// One chunk of float64: the chirp-z batch of one where the list would take it, else the list's plain route with batch-of-one plans and
+// the same arithmetic (equal arrays: tests/test_gpu_audio.py), written out without the list's job table -- its 16-byte upload took the
+// host time of a 1000 -> 333 call from 32 to 37 us (profiles/envelope_refactor.txt)
+__global__ void __launch_bounds__(256) k_scale_f64(double* __restrict__ y, int64_t n, double f) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) y[i] *= f;
+}
+extern "C" int dd_resample_fft_f64(const double* in, double* out, int64_t n, int64_t num, void* stream) {
+    DD_REQUIRE(n >= 1 && num >= 1, "n/num");
+    DD_REQUIRE(in && out, "null buffer");
+    hipStream_t s = dd_stream(stream);
+    if (czt_wanted(n, num)) {
+        const int64_t zero = 0;
+        const int rc = resample_czt_batch(in, 0, &zero, &n, out, &zero, num, std::vector<int>{0}, s);
+        if (rc != 1) return rc;
+    }
+    hipfftHandle pf, pb;
+    int rc = get_plan(&pf, HIPFFT_D2Z, n, 1, s);
+    if (rc != DD_OK) return rc;
+    rc = get_plan(&pb, HIPFFT_Z2D, num, 1, s);
+    if (rc != DD_OK) return rc;
+    const int64_t nxb = n / 2 + 1, nyb = num / 2 + 1;
+    const size_t bx = (sizeof(double2) * nxb + 255) & ~(size_t)255, by = (sizeof(double2) * nyb + 255) & ~(size_t)255;
+    DDScratchLock scr;                      // held until this entry point has enqueued everything
+    rc = scr.get(bx + by + sizeof(double) * n, s);
+    if (rc != DD_OK) return rc;
+    double2* X = reinterpret_cast<double2*>(scr.ptr);
+    double2* Y = reinterpret_cast<double2*>(scr.ptr + bx);
+    double* tmp = reinterpret_cast<double*>(scr.ptr + bx + by);            // D2Z may overwrite its input: work on a copy
+    DD_HIP_CHECK(hipMemcpyAsync(tmp, in, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
+    hipfftResult r1 = hipfftExecD2Z(pf, tmp, (hipfftDoubleComplex*)X);
+    hipLaunchKernelGGL(k_rs_bins_b, dim3(grid1(nyb), 1), dim3(256), 0, s, X, Y, nxb, nyb, num < n ? num : n, num, n);
+    hipfftResult r2 = hipfftExecZ2D(pb, (hipfftDoubleComplex*)Y, out);
+    hipLaunchKernelGGL(k_scale_f64, dim3(grid1(num)), dim3(256), 0, s, out, num, 1.0 / (double)n);
+    if (r1 != HIPFFT_SUCCESS || r2 != HIPFFT_SUCCESS) {
+        dd_set_error("hipfft exec failed (%d, %d)", (int)r1, (int)r2);
+        return DD_ERR_HIP;
+    }
+    DD_LAUNCH_CHECK();
     return DD_OK;
 }

@@ -1,5 +1,7 @@
-// getAccurateSync's windows, batched (decode_noaa.py:808-880): dd_noaa_sync_windows(_multi), and dd_noaa_prepare.  The envelope
-// stage's Hilbert-kernel spectra are those of dd_audio_envelope.h; the scan and the needle's run table those of dd_audio_xcorr.h.
+// getAccurateSync's windows, batched (decode_noaa.py:808-880): dd_noaa_sync_windows(_multi), and dd_noaa_prepare.  The
+// windows' envelope is ONE stage (sync_envelope_stage: own transform, the library's padded real transforms, the library's length-N
+// complex pair), which the production entry runs per batch and dd_debug_sync_envelope runs alone.  Its Hilbert-kernel spectra and
+// the padded convolution's body are those of dd_audio_envelope.h; the scan and the needle's run table those of dd_audio_xcorr.h.
 // One of the six parts of dd_audio.hip (one translation unit: the parts share the plan cache, the float64 transform and the scratch
 // buffers of dd_audio.hip and are included there, each using only the parts before it).  Internal; not a stand-alone header.
 // ---------------------------------------------------------------- 8f-2: accurate-sync windows, batched
@@ -197,6 +199,30 @@ __global__ void __launch_bounds__(256) k_sync_fm_pad(const float2* __restrict__ 
     XR[(int64_t)blockIdx.y * M + j] = j < L - 1 ? (double)dd_fm_angle(y[j + 1], y[j]) : 0.0;
 }
 
+// The envelope stage of a batch of b windows: X [b][L] filtered IQ -> ENV [b][L - 1] = abs(hilbert(angle(X[n+1] conj X[n]))).
+// route 0: dd_hconv_kernels.h (hc_length_ok(M); W: c128 [(b+1)/2][M], two windows per image), route 1 ("lib"): the library's padded real
+// transforms (W as f64 [b][M], SP: c128 [b][M/2 + 1], YR: f64 [b][M]), route 2 ("fft"): the library's length-(L-1) complex pair in W
+// (c128 [b][L - 1]).  HH: hilbert_spectrum(L - 1, M, false) for routes 0 and 1
+static int sync_envelope_stage(int route, const float2* X, int64_t L, int b, int64_t M, const double2* HH, double2* W, double2* SP, double* YR,
+                               double* ENV, hipStream_t s) {
+    const int64_t L2 = L - 1;
+    if (route == 0) return hc_envelope(M, X, L, b, HH + (M / 2 + 1), W, ENV, s);
+    if (route == 1) {
+        hipLaunchKernelGGL(k_sync_fm_pad, dim3(grid1(M), b), dim3(256), 0, s, X, L, (double*)W, M);
+        return envelope_padded((double*)W, SP, YR, HH, M, L2, b, ENV, s);
+    }
+    const dim3 gL2(grid1(L2), b);
+    hipfftHandle plan;
+    const int rc = get_plan(&plan, HIPFFT_Z2Z, L2, b, s);
+    if (rc != DD_OK) return rc;
+    hipLaunchKernelGGL(k_sync_fm, gL2, dim3(256), 0, s, X, L, W);
+    DD_FFT_CHECK(hipfftExecZ2Z(plan, (hipfftDoubleComplex*)W, (hipfftDoubleComplex*)W, HIPFFT_FORWARD));
+    hipLaunchKernelGGL(k_hilbert_mask_b, gL2, dim3(256), 0, s, W, L2);
+    DD_FFT_CHECK(hipfftExecZ2Z(plan, (hipfftDoubleComplex*)W, (hipfftDoubleComplex*)W, HIPFFT_BACKWARD));
+    hipLaunchKernelGGL(k_cplx_abs_b, gL2, dim3(256), 0, s, W, ENV, L2, 1.0 / (double)L2);
+    return DD_OK;
+}
+
 // What dd_noaa_crude_tail will need for `n` audio samples in blocks of `block` -- the Hilbert-kernel spectra of the block and of the ragged
 // last block (host transforms: ~20 ms) and the transform's twiddle tables -- built ahead of time.  noaa_sync calls this from a thread of
 // its own when the decoder object is created, so that it overlaps the upload of the recording and the audio chain; the result sits in the
@@ -211,20 +237,18 @@ extern "C" int dd_noaa_prepare(int64_t n, int64_t block, int64_t window, void* s
     struct Job { std::pair<int, int64_t> key; int64_t len, M; bool split; };
     std::vector<Job> jobs;
     if (n >= 1) {
-        int64_t nfull = 0;
-        while ((nfull + 1) * block < n) ++nfull;
-        const int64_t lens[2] = {nfull > 0 ? block : 0, n - nfull * block};
-        for (int i = 0; i < 2; ++i) {
-            bool split = false;
-            const int64_t M = hc_block_len(lens[i], &split);
-            if (M) jobs.push_back(Job{split ? hilbert_split_key(dev, lens[i], M) : hilbert_kernel_key(dev, lens[i], M), lens[i], M, split});
-        }
+        const DDEnvWalk w = envelope_plan(n, block);
+        for (const DDEnvGroup* g : {&w.full, &w.last})
+            if (g->route == DD_ENV_OWN_SPLIT || g->route == DD_ENV_OWN_PLAIN) {
+                const bool split = g->route == DD_ENV_OWN_SPLIT;
+                jobs.push_back(Job{hilbert_key(dev, g->N, g->M, split), g->N, g->M, split});
+            }
     }
     if (window >= 4) {                                               // dd_noaa_sync_windows: L2 = window - 1 angles, cyclic length >= 2 L2 + 2
         const int64_t L2 = window - 1;
         int64_t M = 1;
         while (M < 2 * L2 + 2) M <<= 1;
-        if (hc_length_ok(M)) jobs.push_back(Job{hilbert_kernel_key(dev, L2, M), L2, M, false});
+        if (hc_length_ok(M)) jobs.push_back(Job{hilbert_key(dev, L2, M, false), L2, M, false});
     }
     int built = 0;
     for (const Job& j : jobs) {
@@ -236,7 +260,7 @@ extern "C" int dd_noaa_prepare(int64_t n, int64_t block, int64_t window, void* s
         // closed forms and a radix-2 transform, outside every lock, no device call: in a fresh process the runtime is still busy with its
         // first copy (~100 ms, _hip.require_gpu's warm-up thread) and this thread beside it
         std::vector<double2> h;
-        if (j.split) hilbert_split_host(j.len, j.M, h); else hilbert_kernel_host(j.len, j.M, h);
+        hilbert_host(j.len, j.M, j.split, h);
         (void)hilb_host_keep(j.key, h);
         ++built;
     }
@@ -270,31 +294,12 @@ extern "C" int dd_debug_sync_envelope(const void* X_dev, int64_t L, int nwin, in
     hipStream_t s = dd_stream(stream);
     std::lock_guard<std::mutex> lk(g_sync_mu);
     const double2* HH = nullptr;
-    int rc = hilbert_kernel_spectrum(L2, M, &HH, s);
+    int rc = hilbert_spectrum(L2, M, false, &HH, s);
     if (rc != DD_OK) return rc;
-    const float2* X = (const float2*)X_dev;
-    const int pairs = (nwin + 1) / 2;
     DDDevBuf<char> buf;
-    const size_t bW = sizeof(double2) * (size_t)pairs * M, bSP = sizeof(double2) * (size_t)nwin * nb, bYR = sizeof(double) * (size_t)nwin * M;
+    const size_t bW = sizeof(double2) * (size_t)((nwin + 1) / 2) * M, bSP = sizeof(double2) * (size_t)nwin * nb, bYR = sizeof(double) * (size_t)nwin * M;
     DD_HIP_CHECK(buf.alloc(bW + (route ? bSP + bYR : 0)));
-    if (route == 0) {
-        rc = hc_envelope(M, X, L, nwin, HH + nb, (double2*)buf.get(), env_dev, s);
-    } else {
-        double* XR = (double*)buf.get();
-        double2* SP = (double2*)(buf + bW);
-        double* YR = (double*)(buf + bW + bSP);
-        hipfftHandle pf, pb;
-        rc = get_plan(&pf, HIPFFT_D2Z, M, nwin, s);
-        if (rc == DD_OK) rc = get_plan(&pb, HIPFFT_Z2D, M, nwin, s);
-        if (rc == DD_OK) {
-            hipLaunchKernelGGL(k_sync_fm_pad, dim3(grid1(M), nwin), dim3(256), 0, s, X, L, XR, M);
-            hipfftResult r1 = hipfftExecD2Z(pf, XR, (hipfftDoubleComplex*)SP);
-            hipLaunchKernelGGL(k_spec_mul, dim3(grid1(nb), nwin), dim3(256), 0, s, SP, HH, nb);
-            hipfftResult r2 = hipfftExecZ2D(pb, (hipfftDoubleComplex*)SP, YR);
-            hipLaunchKernelGGL(k_env_hypot, dim3(grid1(L2), nwin), dim3(256), 0, s, XR, YR, M, L2, env_dev);
-            if (r1 != HIPFFT_SUCCESS || r2 != HIPFFT_SUCCESS) { dd_set_error("hipfft exec failed (%d, %d)", (int)r1, (int)r2); rc = DD_ERR_HIP; }
-        }
-    }
+    rc = sync_envelope_stage(route, (const float2*)X_dev, L, nwin, M, HH, (double2*)buf.get(), (double2*)(buf + bW), (double*)(buf + bW + bSP), env_dev, s);
     hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(s);         // (before buf is freed: every return is behind it)
     if (rc != DD_OK) return rc;
     if (e1 != hipSuccess || e2 != hipSuccess) { dd_set_error("dd_debug_sync_envelope: %s", hipGetErrorString(e1 != hipSuccess ? e1 : e2)); return DD_ERR_HIP; }
@@ -405,12 +410,11 @@ extern "C" int dd_noaa_sync_windows_multi(const void* iq, int iq_kind, const int
     float2* X = (float2*)(base + o_X);
     float2* Y1 = (float2*)(base + o_Y1);
     double2* W = (double2*)(base + o_W);
-    double* XR = (double*)(base + o_W);
     double2* SP = (double2*)(base + o_SP);
     double* YR = (double*)(base + o_YR);
     const double2* HH = nullptr;
     if (!hilbert_fft) {
-        rc = hilbert_kernel_spectrum(L2, M, &HH, s);
+        rc = hilbert_spectrum(L2, M, false, &HH, s);
         if (rc != DD_OK) return rc;
     }
     double* ENV = (double*)(base + o_ENV);
@@ -441,7 +445,7 @@ extern "C" int dd_noaa_sync_windows_multi(const void* iq, int iq_kind, const int
     const double tt_up1 = now_us() - tt0;
     for (int w0 = 0; w0 < n_windows; w0 += B) {
         const int b = n_windows - w0 < B ? n_windows - w0 : B;
-        const dim3 gL(grid1(L), b), gL2(grid1(L2), b), gL4(grid1((L + 3) / 4), b);
+        const dim3 gL4(grid1((L + 3) / 4), b);
         if (front_fused) {
             // X <- filtfilt(oscillator x raw IQ): pass 1 computes the samples where it stages them
             const DDFrontSrc F = {iq, d_starts + w0, cycles_q64, tbl, iq_kind};
@@ -451,29 +455,8 @@ extern "C" int dd_noaa_sync_windows_multi(const void* iq, int iq_kind, const int
             else hipLaunchKernelGGL(k_sync_front<false>, gL4, dim3(256), 0, s, iq, d_starts + w0, L, cycles_q64, tbl, X);
             dd_filtfilt_launch<float2>(X, L, Y1, X, L, L, fir_ntaps, d_taps1, b, s);        // X <- filtfilt(X): pass 2 reads only Y1
         }
-        if (hilbert_fft) {
-            hipLaunchKernelGGL(k_sync_fm, gL2, dim3(256), 0, s, X, L, W);
-            hipfftHandle plan;
-            rc = get_plan(&plan, HIPFFT_Z2Z, L2, b, s);
-            if (rc != DD_OK) return rc;
-            DD_FFT_CHECK(hipfftExecZ2Z(plan, (hipfftDoubleComplex*)W, (hipfftDoubleComplex*)W, HIPFFT_FORWARD));
-            hipLaunchKernelGGL(k_hilbert_mask_b, gL2, dim3(256), 0, s, W, L2);
-            DD_FFT_CHECK(hipfftExecZ2Z(plan, (hipfftDoubleComplex*)W, (hipfftDoubleComplex*)W, HIPFFT_BACKWARD));
-            hipLaunchKernelGGL(k_cplx_abs_b, gL2, dim3(256), 0, s, W, ENV, L2, 1.0 / (double)L2);
-        } else if (hilbert_own) {
-            rc = hc_envelope(M, X, L, b, HH + nb, W, ENV, s);
-            if (rc != DD_OK) return rc;
-        } else {
-            hipfftHandle pf, pb;
-            rc = get_plan(&pf, HIPFFT_D2Z, M, b, s);
-            if (rc == DD_OK) rc = get_plan(&pb, HIPFFT_Z2D, M, b, s);
-            if (rc != DD_OK) return rc;
-            hipLaunchKernelGGL(k_sync_fm_pad, dim3(grid1(M), b), dim3(256), 0, s, X, L, XR, M);
-            DD_FFT_CHECK(hipfftExecD2Z(pf, XR, (hipfftDoubleComplex*)SP));
-            hipLaunchKernelGGL(k_spec_mul, dim3(grid1(nb), b), dim3(256), 0, s, SP, HH, nb);
-            DD_FFT_CHECK(hipfftExecZ2D(pb, (hipfftDoubleComplex*)SP, YR));
-            hipLaunchKernelGGL(k_env_hypot, gL2, dim3(256), 0, s, XR, YR, M, L2, ENV);
-        }
+        rc = sync_envelope_stage(hilbert_fft ? 2 : (hilbert_own ? 0 : 1), X, L, b, M, HH, W, SP, YR, ENV, s);
+        if (rc != DD_OK) return rc;
         const double* hay = ENV;
         if (pre_ntaps) {
             if (cos2) {
