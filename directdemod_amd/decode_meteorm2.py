@@ -1,7 +1,7 @@
 """
 Meteor-M2 QPSK sync detection -- the reference's decode_meteorm2 surface (decode_meteorm2.py): `useful`, `getSyncs` and the
-module helpers `lim` / `limBin`, plus `getSymbols`, the PLL-corrected soft symbols (gardnerA after pllObj.loop) a later LRPT decoder
-would read.
+module helpers `lim` / `limBin`, plus `getSymbols`, the PLL-corrected soft symbols (gardnerA after pllObj.loop), and beyond the
+reference `getFrames` / `frameInfo`: the LRPT channel frames decoded from those symbols (lrpt.py).
 
 One decode pass, cached, feeds both properties.  Per chunk of the recording (the reference's chunker, no chunker handed to the
 signal, so the mixer phase restarts at 0 in every chunk): offsetFreq in the reference's float64 arithmetic (qpsk.mix: the package's
@@ -15,10 +15,11 @@ Deviations from the reference:
   - with exactly one MAXSYNC the reference raises ValueError (np.min of an empty np.diff); here getSyncs returns [] with useful 0.
 """
 import logging
+import time
 
 import numpy as np
 
-from . import comm, filters, qpsk, symbolsync
+from . import _hip, comm, filters, lrpt, qpsk, symbolsync
 from .qpsk import lim, limBin  # noqa: F401  (module-level helpers, as in the reference)
 
 
@@ -26,7 +27,9 @@ class decode_meteorm2(symbolsync.SyncDecoder):
     """Object to decode Meteor m2: decode_meteorm2(sigsrc, offset, bw) as in the reference (bw None -> 70000).
     use_device_raw: read the recording as raw u8 pairs resident on the device when the source offers it (source.read_device_raw).
     `useful`: 1 if two MAXSYNCs lie 0.11 s +- 0.05 s apart; `getSyncs`: np.float64 positions; `getSymbols`: at 72000 Hz.
-    minsyncs: (ctr, template 0 = sync2mhz / 1 = sync2mhz2) per MINSYNC event; buffers: (intervals, maxBuffStart, template)."""
+    minsyncs: (ctr, template 0 = sync2mhz / 1 = sync2mhz2) per MINSYNC event; buffers: (intervals, maxBuffStart, template).
+    `getFrames`: uint8[n, 1020], the de-randomised LRPT frame bodies in stream order (Reed-Solomon parity still attached);
+    `frameInfo`: one lrpt.INFO record per frame.  Both come from the same cached walk, whether or not the 120-bit sync was seen."""
     WALKER = qpsk.Walker
     STAGES = ("front_end",)
     SPACING = (0.11, 0.05)
@@ -35,6 +38,46 @@ class decode_meteorm2(symbolsync.SyncDecoder):
         super().__init__(sigsrc, use_device_raw)
         self._bw = 70000 if bw is None else bw
         self._offset = offset
+        self._frames = None
+
+    @property
+    def getFrames(self):
+        """The LRPT frame bodies, uint8[n, 1020], in stream order"""
+        return self._decode_frames()[0]
+
+    @property
+    def frameInfo(self):
+        """Per frame (lrpt.INFO): symbol (of the marker's first bit), sample (the walk's A sample of that symbol), hypothesis,
+        asm_score (of 52), asm_errors (of 32 decoded marker bits), corrected (channel bits the decoder changed), vcid, counter"""
+        return self._decode_frames()[1]
+
+    def _decode_frames(self):
+        if self._frames is not None:
+            return self._frames
+        w = self.walker()
+        t0 = time.perf_counter()
+
+        def lap(name):
+            nonlocal t0
+            _hip.sync()
+            now = time.perf_counter()
+            self.timings["lrpt_" + name] = now - t0
+            t0 = now
+        soft = lrpt.soft_symbols(w.view("sym"))
+        lap("soft")
+        starts = lrpt.frame_starts(lrpt.asm_candidates(soft, w.nsym), w.nsym)
+        lap("asm")
+        bits = lrpt.viterbi(soft, w.nsym, starts[:, :2])
+        lap("viterbi")
+        bodies, fin = lrpt.finish(bits, soft, w.nsym, starts[:, :2])
+        info = np.zeros(len(starts), dtype=lrpt.INFO)
+        info["symbol"], info["hypothesis"], info["asm_score"] = starts[:, 0], starts[:, 1], starts[:, 2]
+        info["asm_errors"], info["corrected"], info["vcid"] = fin[:, 0], fin[:, 1], fin[:, 2]
+        info["sample"] = [int(w.aidx.view(int(k), 1).to_host()[0]) for k in starts[:, 0]]
+        info["counter"] = [lrpt.vcdu_header(b)["counter"] for b in bodies]
+        lap("finish")
+        self._frames = (bodies, info)
+        return self._frames
 
     def _front_end(self, src, ck, lap):
         bf = filters.butter(src.sampFreq, self._bw)

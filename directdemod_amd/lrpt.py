@@ -1,0 +1,250 @@
+"""
+Meteor-M2 LRPT channel decoding -- beyond the reference, which stops at the sync list: from the PLL-corrected soft symbols of the
+symbol walk (decode_meteorm2.getSymbols, 72 ksym/s) to de-randomised 1020-byte frame bodies (where every
+stage is defined bit for bit).  Device stages (dd_lrpt.h): the int8 soft pairs (`soft_symbols`), the attached-sync-marker scores
+under the eight phase / IQ-swap hypotheses (`asm_candidates`), the block-wise soft-decision Viterbi decode of the rate-1/2, K = 7
+code (`viterbi`) and the per-frame finish (`finish`: marker check, de-randomisation, re-encode count).  Host stages, O(frames):
+`frame_starts`, `vcdu_header`.  NumPy restatements of the same definitions, for the tests: `encode`, `pn_sequence`, `hypothesis`,
+`soft_np`, `asm_scores`, `asm_candidates_np`, `viterbi_blocks`, `finish_np`.  All arithmetic is integer.
+"""
+import numpy as np
+
+from ._hip import DevArray, check, lib
+
+FRAME_BITS = 8192
+BODY_BYTES = 1020
+ASM = np.array([0x1A, 0xCF, 0xFC, 0x1D], dtype=np.uint8)
+ASM_ENCODED = 0x035D49C24FF2686B          # encode(ASM bits) from state 0, first code bit in bit 63
+ASM_SKIP = 12                             # code bits that depend on the previous frame's tail: never scored
+MIN_SCORE = 46                            # of 52
+GUARD = 31                                # symbols around a candidate in which a better one suppresses it
+BLOCK, WARM = 512, 128                    # trellis steps decoded per block; steps of warm-up before and of tail after it
+G1, G2 = 0x79, 0x5B
+INFO = np.dtype([("symbol", np.int64), ("sample", np.int64), ("hypothesis", np.int64), ("asm_score", np.int64),
+                 ("asm_errors", np.int64), ("corrected", np.int64), ("vcid", np.int64), ("counter", np.int64)])
+
+
+# ------------------------------------------------------------------ the definitions in NumPy
+def _taps(g):
+    return [j for j in range(7) if (g >> j) & 1]
+
+
+def encode(bits, state=0):
+    """The code bits (c1, c2 per input bit, interleaved) of `bits` from encoder state `state` (the previous six input bits, newest at
+    bit 5): r = (b << 6) | s, c1 = parity(r & 0x79), c2 = parity(r & 0x5B), s' = r >> 1."""
+    bits = np.asarray(bits, dtype=np.uint8)
+    ext = np.concatenate((np.array([(state >> j) & 1 for j in range(6)], dtype=np.uint8), bits))     # r bit j of step k = ext[k + j]
+    n = len(bits)
+    out = np.zeros((n, 2), dtype=np.uint8)
+    for col, g in enumerate((G1, G2)):
+        for j in _taps(g):
+            out[:, col] ^= ext[j:j + n]
+    return out.ravel()
+
+
+def pn_sequence(nbytes=BODY_BYTES):
+    """The CCSDS pseudo-noise bytes: h(x) = x^8 + x^7 + x^5 + x^3 + 1, register all ones, output r[0], feedback
+    r[0] ^ r[3] ^ r[5] ^ r[7] shifted in at the far end; period 255 bits."""
+    r = [1] * 8
+    one = []
+    for _ in range(255):
+        one.append(r[0])
+        r = r[1:] + [r[0] ^ r[3] ^ r[5] ^ r[7]]
+    reps = -(-8 * nbytes // 255)
+    return np.packbits(np.tile(np.array(one, dtype=np.uint8), reps)[:8 * nbytes])
+
+
+def hypothesis(a, b, h):
+    """The soft pair (a, b) under hypothesis h in 0..7, in int32 (-(-128) = 128 survives): h & 3 selects (a, b), (-b, a), (-a, -b),
+    (b, -a); h & 4 then exchanges the two."""
+    a = np.asarray(a).astype(np.int32)
+    b = np.asarray(b).astype(np.int32)
+    a, b = ((a, b), (-b, a), (-a, -b), (b, -a))[h & 3]
+    return (b, a) if h & 4 else (a, b)
+
+
+def soft_np(sym):
+    """complex symbols -> int8[2 n]: lim(re / 2), lim(im / 2) (symbolsync.lim), interleaved"""
+    sym = np.asarray(sym, dtype=np.complex128)
+    v = np.stack((sym.real, sym.imag), axis=1).ravel() / 2.0
+    out = np.trunc(np.clip(v, -128.0, 127.0))
+    out = np.where((v > 0) & (v < 1), 1.0, out)
+    out = np.where((v > -1) & (v < 0), -1.0, out)
+    return out.astype(np.int8)
+
+
+def _asm_code_bits():
+    return np.array([(ASM_ENCODED >> (63 - j)) & 1 for j in range(64)], dtype=np.uint8)
+
+
+def asm_scores(soft, nsym):
+    """int64[nsym - 31, 8]: score(p, h) = how many of the code bits j in 12..63 of the encoded marker equal the hard bit 2p + j
+    under h (0..52); empty for nsym < 32"""
+    soft = np.asarray(soft, dtype=np.int8)[:2 * nsym]
+    npos = max(nsym - 31, 0)
+    out = np.zeros((npos, 8), dtype=np.int64)
+    if npos == 0:
+        return out
+    e = _asm_code_bits()[ASM_SKIP:]
+    for h in range(8):
+        a, b = hypothesis(soft[0::2], soft[1::2], h)
+        hard = np.stack((a > 0, b > 0), axis=1).ravel().astype(np.uint8)
+        win = np.lib.stride_tricks.sliding_window_view(hard, 64)[::2][:npos, ASM_SKIP:]
+        out[:, h] = np.sum(win == e, axis=1)
+    return out
+
+
+def asm_candidates_np(soft, nsym, min_score=MIN_SCORE):
+    """int64[m, 3] = every (p, h, score) with score >= min_score, sorted by (p, h)"""
+    sc = asm_scores(soft, nsym)
+    p, h = np.nonzero(sc >= min_score)
+    return np.stack((p, h, sc[p, h]), axis=1).astype(np.int64).reshape(-1, 3)
+
+
+def _trellis():
+    """per state ns and predecessor choice x: the predecessor ((ns & 31) << 1) | x and the signs (2 c1 - 1, 2 c2 - 1) of its branch"""
+    ns = np.arange(64)[:, None]
+    x = np.arange(2)[None, :]
+    pred = ((ns & 31) << 1) | x
+    r = ((ns >> 5) << 6) | pred
+    par = lambda v: np.array([[bin(int(q)).count("1") & 1 for q in row] for row in v])      # noqa: E731
+    return pred, 2 * par(r & G1) - 1, 2 * par(r & G2) - 1
+
+
+_PRED, _S1, _S2 = _trellis()
+
+
+def _decode_group(a, b, warm, nout):
+    """add-compare-select over the steps of a[g, t], b[g, t] (int32 soft pairs under the hypothesis, all 64 metrics 0 at t = 0), then
+    traceback from the best final state (lowest index among equals): the input bits of steps warm .. warm + nout - 1, uint8[g, nout]"""
+    G, T = a.shape
+    m = np.zeros((G, 64), dtype=np.int32)
+    dec = np.zeros((T, G, 64), dtype=bool)
+    for t in range(T):
+        c = m[:, _PRED] + (_S1[None] * a[:, t, None, None] + _S2[None] * b[:, t, None, None]).astype(np.int32)
+        d = c[:, :, 1] > c[:, :, 0]                       # x = 1 wins only when strictly larger
+        dec[t] = d
+        m = np.where(d, c[:, :, 1], c[:, :, 0])
+    st = np.argmax(m, axis=1)
+    out = np.zeros((G, nout), dtype=np.uint8)
+    g = np.arange(G)
+    for t in range(T - 1, warm - 1, -1):
+        if t < warm + nout:
+            out[:, t - warm] = st >> 5
+        st = ((st & 31) << 1) | dec[t, g, st]
+    return out
+
+
+def viterbi_blocks(soft, nsym, p, h, nbits, block=BLOCK, warm=WARM):
+    """The decoded bits (uint8[nbits]) of the nbits trellis steps from symbol p under hypothesis h: blocks [k, e) of `block` steps,
+    each with add-compare-select over max(0, k - warm) .. min(nsym, e + warm) and traceback to k.  block = nbits decodes the span as
+    one block."""
+    if nbits % block or nbits <= 0 or p < 0 or p + nbits > nsym or not 0 <= h < 8:
+        raise ValueError("viterbi_blocks: span")
+    soft = np.asarray(soft, dtype=np.int8)
+    a, b = hypothesis(soft[0:2 * nsym:2], soft[1:2 * nsym:2], h)
+    groups = {}
+    for i, k in enumerate(range(p, p + nbits, block)):
+        lo, hi = max(0, k - warm), min(nsym, k + block + warm)
+        groups.setdefault((k - lo, hi - lo), []).append((i, lo))
+    out = np.zeros(nbits, dtype=np.uint8)
+    for (w, T), members in groups.items():
+        idx = np.array([lo for _, lo in members])[:, None] + np.arange(T)[None, :]
+        bits = _decode_group(a[idx], b[idx], w, block)
+        for (i, _), row in zip(members, bits):
+            out[i * block:(i + 1) * block] = row
+    return out
+
+
+def finish_np(bits, soft, nsym, p, h):
+    """One frame's decoded bits (uint8[8192], from symbol p under h) -> (body uint8[1020], asm_errors, corrected): the marker bits that
+    differ, bytes 4..1023 XOR PN, and over steps 6..8191 how many of the 2 * 8186 hard input bits differ from the re-encoding of
+    the decoded bits (the encoder state taken from the decoded bits themselves)."""
+    bits = np.asarray(bits, dtype=np.uint8)
+    if len(bits) != FRAME_BITS or p < 0 or p + FRAME_BITS > nsym:
+        raise ValueError("finish_np: frame")
+    asm_errors = int(np.sum(bits[:32] != np.unpackbits(ASM)))
+    body = np.packbits(bits)[4:] ^ pn_sequence()
+    soft = np.asarray(soft, dtype=np.int8)
+    a, b = hypothesis(soft[2 * p:2 * (p + FRAME_BITS):2], soft[2 * p + 1:2 * (p + FRAME_BITS):2], h)
+    hard = np.stack((a > 0, b > 0), axis=1)[6:].ravel().astype(np.uint8)
+    code = np.zeros((FRAME_BITS - 6, 2), dtype=np.uint8)
+    for col, g in enumerate((G1, G2)):
+        for j in _taps(g):
+            code[:, col] ^= bits[j:j + FRAME_BITS - 6]
+    return body, asm_errors, int(np.sum(code.ravel() != hard))
+
+
+# ------------------------------------------------------------------ host stages
+def frame_starts(cands, nsym):
+    """candidates int64[m, 3] = (p, h, score) -> the frame starts among them, sorted by p: no candidate within +-31 symbols is better
+    (higher score; among equal scores the lower p, then the lower h), and the frame fits (p + 8192 <= nsym)"""
+    c = np.asarray(cands, dtype=np.int64).reshape(-1, 3)
+    c = c[np.lexsort((c[:, 1], c[:, 0]))]
+    keep = []
+    lo = 0
+    for i in range(len(c)):
+        p, h, sc = c[i]
+        while c[lo, 0] < p - GUARD:
+            lo += 1
+        best = True
+        j = lo
+        while j < len(c) and c[j, 0] <= p + GUARD:
+            if j != i and (c[j, 2] > sc or (c[j, 2] == sc and (c[j, 0], c[j, 1]) < (p, h))):
+                best = False
+                break
+            j += 1
+        if best and p + FRAME_BITS <= nsym:
+            keep.append(i)
+    return c[keep]
+
+
+def vcdu_header(body):
+    """version, spacecraft id, virtual channel and the 24-bit frame counter from a frame body's first six bytes"""
+    body = np.frombuffer(body, dtype=np.uint8) if isinstance(body, (bytes, bytearray)) else np.asarray(body, dtype=np.uint8)
+    b = [int(v) for v in body[:6]]
+    return dict(version=b[0] >> 6, scid=((b[0] & 0x3F) << 2) | (b[1] >> 6), vcid=b[1] & 0x3F, counter=(b[2] << 16) | (b[3] << 8) | b[4])
+
+
+# ------------------------------------------------------------------ device stages
+def _spans(spans):
+    s = np.ascontiguousarray(np.asarray(spans, dtype=np.int64).reshape(-1, 2))
+    return s, len(s)
+
+
+def soft_symbols(sym):
+    """complex128 device symbols -> device int8[2 n], (lim(re / 2), lim(im / 2)) per symbol"""
+    if sym.dtype != np.dtype(np.complex128):
+        raise TypeError("complex128 device array expected, got %s" % sym.dtype)
+    out = DevArray(max(2 * sym.n, 1), np.int8)
+    check(lib().dd_lrpt_soft(sym.ptr, sym.n, out.ptr, None), "dd_lrpt_soft")
+    return out.view(0, 2 * sym.n)
+
+
+def asm_candidates(soft, nsym, min_score=MIN_SCORE, cap=1 << 16):
+    """int64[m, 3] = every (p, h, score) with score >= min_score, sorted by (p, h); more than `cap` of them raise"""
+    cand = DevArray(3 * max(cap, 1), np.int64)
+    cnt = DevArray(1, np.uint64)
+    check(lib().dd_lrpt_asm_search(soft.ptr, nsym, min_score, cap, cand.ptr, cnt.ptr, None), "dd_lrpt_asm_search")
+    m = int(cnt.to_host()[0])
+    if m > cap:
+        raise RuntimeError("LRPT marker search: %d candidates, more than %d" % (m, cap))
+    c = cand.view(0, 3 * m).to_host().reshape(m, 3)
+    return c[np.lexsort((c[:, 1], c[:, 0]))]
+
+
+def viterbi(soft, nsym, spans, nbits=FRAME_BITS):
+    """spans [(p, h)] -> device uint8[len(spans) * nbits / 8]: each span's nbits decoded bits from symbol p under h, MSB first"""
+    s, n = _spans(spans)
+    out = DevArray(max(n * nbits // 8, 1), np.uint8)
+    check(lib().dd_lrpt_viterbi(soft.ptr, nsym, s.ctypes.data, n, nbits, out.ptr, None), "dd_lrpt_viterbi")
+    return out.view(0, n * nbits // 8)
+
+
+def finish(bits, soft, nsym, spans):
+    """The frames decoded by viterbi(soft, nsym, spans) -> (bodies uint8[n, 1020], info int32[n, 3] = asm_errors, corrected, vcid)"""
+    s, n = _spans(spans)
+    bodies = DevArray(max(n * BODY_BYTES, 1), np.uint8)
+    info = DevArray(max(3 * n, 1), np.int32)
+    check(lib().dd_lrpt_finish(bits.ptr, soft.ptr, nsym, s.ctypes.data, n, bodies.ptr, info.ptr, None), "dd_lrpt_finish")
+    return bodies.view(0, n * BODY_BYTES).to_host().reshape(n, BODY_BYTES), info.view(0, 3 * n).to_host().reshape(n, 3)

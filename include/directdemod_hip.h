@@ -461,6 +461,26 @@ int dd_meteor_minsync(const void* sym, int64_t nsym, const uint8_t* sync_bits_ho
 int dd_meteor_maxcorr(const void* lim, int64_t lim_len, const int64_t* bufs_host, int64_t nbuf, const int8_t* templates_host,
                       int64_t* out, void* stream);
 
+/* ---- Meteor-M2 LRPT channel decoding (beyond the reference; DESIGN.md section 4.14 defines every stage) ---------------------
+ * dd_lrpt_soft -- soft[2k], soft[2k+1] = lim(re(sym[k]) / 2), lim(im(sym[k]) / 2) as int8 (sym complex128, the walk's sym[]).
+ * dd_lrpt_asm_search -- for every symbol p <= nsym - 32 and hypothesis h in 0..7: score = how many of the encoded sync marker's
+ *     code bits 12..63 equal the hard bit 2p + j under h; every score >= min_score appends cand[3c .. 3c+2] = (p, h, score),
+ *     *count = the number of such (p, h) (entries past cap are dropped).  The order of the entries is not defined.
+ * dd_lrpt_viterbi -- per span i (spans_host[2i], [2i+1] = first symbol p, hypothesis h): the nbits input bits of the rate-1/2,
+ *     K = 7 code's most likely path over the steps p .. p + nbits - 1, decoded in blocks of 512 steps with 128 steps of warm-up
+ *     and tail, packed MSB first into bits_packed[i * nbits / 8 ..].  nbits a multiple of 512, h in 0..7, p + nbits <= nsym,
+ *     at most 65535 spans per call.
+ * dd_lrpt_finish -- per frame i (8192 bits of dd_lrpt_viterbi's output, the same spans): bodies[1020 i ..] = bytes 4..1023 XOR
+ *     the CCSDS pseudo-noise sequence; info[3i .. 3i+2] = (marker bits in error, hard input bits of steps 6..8191 that differ
+ *     from the re-encoded decoded bits, the virtual channel id = body[1] & 0x3F). */
+int dd_lrpt_soft(const void* sym, int64_t nsym, int8_t* soft, void* stream);
+int dd_lrpt_asm_search(const int8_t* soft, int64_t nsym, int min_score, int64_t cap, int64_t* cand, unsigned long long* count,
+                       void* stream);
+int dd_lrpt_viterbi(const int8_t* soft, int64_t nsym, const int64_t* spans_host, int64_t nspans, int64_t nbits,
+                    uint8_t* bits_packed, void* stream);
+int dd_lrpt_finish(const uint8_t* bits_packed, const int8_t* soft, int64_t nsym, const int64_t* spans_host, int64_t nspans,
+                   uint8_t* bodies, int32_t* info, void* stream);
+
 /* ---- Funcube BPSK sync detection (decode_funcube.py:148-306) ------------------------------------------------------------
  * dd_funcube_mix_ramp -- dd_meteor_mix with the frequency formed per sample: th = ((w * f[k]) * k) * inv_fs, w = -2 pi,
  *     f[k] = f0 + k * delta (np.arange's fill) clipped to target from above when target > f0, from below otherwise.

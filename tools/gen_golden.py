@@ -405,7 +405,8 @@ def _meteor_patterns():
 def _meteor_run(raw, offset):
     """The reference's decode_meteorm2.getSyncs on an in-memory recording, tapped: the sample index of every agc.adjust call (B or
     A: an A call is the one costas.loop follows), the AGC'd values, costas phase / freq after each loop, the sample of every lim call
-    (the MAXSYNC buffers), each np.correlate's buffer length, template and argmax, and the MINSYNC / MAXSYNC log records."""
+    (the MAXSYNC buffers), each np.correlate's buffer length, template and argmax, and the MINSYNC / MAXSYNC log records; with
+    each loop the corrected symbol it returns (gardnerA after pllObj.loop), which the LRPT fixture reads."""
     import logging
     import types
     from directdemod import comm
@@ -444,7 +445,7 @@ def _meteor_run(raw, offset):
     class TapCostas(dmet.costas):
         def loop(self, samp):
             out = super().loop(samp)
-            loop_rec.append((len(agc_rec) - 1, self.phase, self.freq))
+            loop_rec.append((len(agc_rec) - 1, self.phase, self.freq, out))
             return out
 
     _lim = dmet.lim
@@ -564,6 +565,29 @@ def gen_meteor():
         _meteor_store(name, raw, off, _meteor_run(raw, off), 2048 if big else 64, 1024 if big else 4096)
 
 
+def gen_lrpt():
+    """The int8 soft pairs of the reference's own symbol walk (agc / Gardner / costas, tapped by _meteor_run) over the LRPT recording
+    of tests/_lrpt.py, halved and limited as decode_meteorm2.py:238-239 does: what the frame decoder's restatement starts from.
+    gen_golden.py --lrpt [names]"""
+    install_shim()
+    sys.path.insert(0, REF)
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import _lrpt
+    from directdemod import decode_meteorm2 as dmet
+    names = [a for a in sys.argv[2:] if a in _lrpt.CASES] or sorted(_lrpt.CASES)
+    for name in names:
+        raw, _, start = _lrpt.case(name)
+        cap = _meteor_run(raw, 0)
+        sym = np.array([r[3] for r in cap["loop"]], dtype=np.complex128)
+        soft = np.array([dmet.lim(v / 2) for s in sym for v in (s.real, s.imag)], dtype=np.int8)
+        path = os.path.join(OUT, "lrpt_%s.npz" % name)
+        np.savez_compressed(path, sha256=np.array(_lrpt.sha256(raw)), n=np.int64(raw.shape[0]), nsym=np.int64(len(sym)), soft=soft,
+                            ref_cpu_s=np.float64(cap["cpu"]))
+        print("lrpt %s: n %d, start bit %d, %d symbols, syncs %s, cpu %.1f s, %d bytes" %
+              (name, raw.shape[0], start, len(sym), cap["syncs"], cap["cpu"], os.path.getsize(path)))
+
+
 def _funcube_run(raw, offset, corrfreq, center, channel):
     """The reference's decode_funcube.getSyncs on an in-memory recording, tapped like _meteor_run: the sample index of every
     agc.adjust call (B or A: an A call is the one costas.loop follows), the AGC'd values, costas phase / freq after each loop, the
@@ -614,7 +638,7 @@ def _funcube_run(raw, offset, corrfreq, center, channel):
     class TapCostas(dfc.costas):
         def loop(self, samp):
             out = super().loop(samp)
-            loop_rec.append((len(agc_rec) - 1, self.phase, self.freq))
+            loop_rec.append((len(agc_rec) - 1, self.phase, self.freq, out))
             return out
 
     _lim = dfc.lim
@@ -739,6 +763,8 @@ def main():
         return gen_funcube()
     if "--meteor" in sys.argv:
         return gen_meteor()
+    if "--lrpt" in sys.argv:
+        return gen_lrpt()
     if "--afsk-frames" in sys.argv:
         return gen_afsk_frames()
     if "--c4-60s" in sys.argv:
