@@ -394,6 +394,20 @@ def gen_afsk_frames():
     _save_afsk_frames("afsk_frames_b.npz", cap, {"fs": np.int64(fs), "offset": np.int64(offset)})
 
 
+def _walk_taps(walk, agc=None, costas=None):
+    """--symbolwalk: `walk` = dict(x = the complex128 samples the tapped loop reads in place of the front end's, amean, pmean, lock =
+    the values agc.mean, costas.mean and costas.plllock start from).  Nothing changes without it."""
+    if walk is None:
+        return
+    if agc is not None:
+        agc.mean = walk["amean"]
+    if costas is not None:
+        costas.mean = walk["pmean"]
+        if walk["lock"]:
+            costas.plllock = True
+            costas.compAlphaBeta(costas.damping, costas.bw / 2.0)
+
+
 def _meteor_patterns():
     """sync72khz, sync72khz1, sync72khz2 (decode_meteorm2.py:163-189)"""
     import _meteor
@@ -402,8 +416,8 @@ def _meteor_patterns():
     return s, np.where(alt == 0, s, 1 - s), np.where(alt == 1, s, 1 - s)
 
 
-def _meteor_run(raw, offset):
-    """The reference's decode_meteorm2.getSyncs on an in-memory recording, tapped: the sample index of every agc.adjust call (B or
+def _meteor_run(raw, offset, walk=None):
+    """The reference's decode_meteorm2.getSyncs on an in-memory recording, tapped (walk: see _walk_taps): the sample index of every agc.adjust call (B or
     A: an A call is the one costas.loop follows), the AGC'd values, costas phase / freq after each loop, the sample of every lim call
     (the MAXSYNC buffers), each np.correlate's buffer length, template and argmax, and the MINSYNC / MAXSYNC log records; with
     each loop the corrected symbol it returns (gardnerA after pllObj.loop), which the LRPT fixture reads."""
@@ -427,7 +441,7 @@ def _meteor_run(raw, offset):
             arr = comm.commSignal.signal.fget(self)
             if not self.tapped:
                 return arr
-            return self._walk(arr)
+            return self._walk(arr if walk is None else walk["x"])
 
         def _walk(self, arr):
             base = cur["base"]
@@ -437,12 +451,20 @@ def _meteor_run(raw, offset):
             cur["base"] = base + len(arr)
 
     class TapAgc(dmet.agc):
+        def __init__(self):
+            super().__init__()
+            _walk_taps(walk, agc=self)
+
         def adjust(self, inp):
             out = super().adjust(inp)
             agc_rec.append((cur["j"], out))
             return out
 
     class TapCostas(dmet.costas):
+        def __init__(self):
+            super().__init__()
+            _walk_taps(walk, costas=self)
+
         def loop(self, samp):
             out = super().loop(samp)
             loop_rec.append((len(agc_rec) - 1, self.phase, self.freq, out))
@@ -588,8 +610,8 @@ def gen_lrpt():
               (name, raw.shape[0], start, len(sym), cap["syncs"], cap["cpu"], os.path.getsize(path)))
 
 
-def _funcube_run(raw, offset, corrfreq, center, channel):
-    """The reference's decode_funcube.getSyncs on an in-memory recording, tapped like _meteor_run: the sample index of every
+def _funcube_run(raw, offset, corrfreq, center, channel, walk=None):
+    """The reference's decode_funcube.getSyncs on an in-memory recording, tapped like _meteor_run (walk: see _walk_taps): the sample index of every
     agc.adjust call (B or A: an A call is the one costas.loop follows), the AGC'd values, costas phase / freq after each loop, the
     samples of each np.correlate's buffer and its argmax, each chunk's mixer frequencies, and the log records."""
     import logging
@@ -620,7 +642,7 @@ def _funcube_run(raw, offset, corrfreq, center, channel):
             arr = comm.commSignal.signal.fget(self)
             if not self.tapped:
                 return arr
-            return self._walk(arr)
+            return self._walk(arr if walk is None else walk["x"])
 
         def _walk(self, arr):
             base = cur["base"]
@@ -630,12 +652,20 @@ def _funcube_run(raw, offset, corrfreq, center, channel):
             cur["base"] = base + len(arr)
 
     class TapAgc(dfc.agc):
+        def __init__(self):
+            super().__init__()
+            _walk_taps(walk, agc=self)
+
         def adjust(self, inp):
             out = super().adjust(inp)
             agc_rec.append((cur["j"], out))
             return out
 
     class TapCostas(dfc.costas):
+        def __init__(self):
+            super().__init__()
+            _walk_taps(walk, costas=self)
+
         def loop(self, samp):
             out = super().loop(samp)
             loop_rec.append((len(agc_rec) - 1, self.phase, self.freq, out))
@@ -758,7 +788,48 @@ def gen_funcube():
                        256 if big else 16, 1024 if big else 2048)
 
 
+def gen_symbolwalk():
+    """The reference's own agc / Gardner / costas loop (both decoders') over the seeded samples of tests/_symbolwalk.py, read in place
+    of the front end's output, from the start values each case states: every symbol's B and A sample index, agc.adjust's output,
+    the corrected symbol, and phase and freq after the loop.   gen_golden.py --symbolwalk [names]"""
+    install_shim()
+    sys.path.insert(0, REF)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import matplotlib
+    matplotlib.use("Agg")
+    import _funcube
+    import _symbolwalk as sw
+    fixtures = [k for k, c in sw.CASES.items() if c.get("fixture")]
+    for name in [a for a in sys.argv[2:] if a in fixtures] or fixtures:
+        policy, x, st = sw.case(name)
+        assert all(st[f] == 0 for f in ("timing", "b_re", "b_im", "c_re", "c_im", "dc_re", "dc_im", "phase", "ctr")) and st["freq"] == 0.001
+        walk = dict(x=x, amean=st["amean"], pmean=st["pmean"], lock=st["lock"])
+        raw = np.full((len(x), 2), 128, dtype=np.uint8)               # what the front end reads; the loop never sees it
+        if policy == "meteor":
+            cap = _meteor_run(raw, 0, walk)
+        else:
+            cap = _funcube_run(raw, 0, False, _funcube.CENTER, _funcube.CHANNEL, walk)
+        agc, loop = cap["agc"], cap["loop"]
+        a_call = np.array([r[0] for r in loop], dtype=np.int64)
+        is_a = np.zeros(len(agc), dtype=bool)
+        is_a[a_call] = True
+        j = np.array([r[0] for r in agc], dtype=np.int64)
+        last_b = np.maximum.accumulate(np.where(~is_a, np.arange(len(agc)), -1))
+        b_call = np.array([last_b[c - 1] if c > 0 else -1 for c in a_call], dtype=np.int64)
+        g = dict(sha256=np.array(sw.sha256(x)), n=np.int64(len(x)), amean=np.float64(st["amean"]), pmean=np.float64(st["pmean"]),
+                 lock=np.int64(st["lock"]), aidx=j[a_call].astype(np.int32),
+                 bidx=np.where(b_call >= 0, j[np.maximum(b_call, 0)], -1).astype(np.int32),      # -1: no B sample yet
+                 agc=np.array([agc[c][1] for c in a_call], dtype=np.complex128),
+                 sym=np.array([r[3] for r in loop], dtype=np.complex128),
+                 phase=np.array([r[1] for r in loop], dtype=np.float64), freq=np.array([r[2] for r in loop], dtype=np.float64))
+        path = os.path.join(OUT, "symbolwalk_%s.npz" % name)
+        np.savez_compressed(path, **g)
+        print("symbolwalk %s: n %d, %d symbols, %d B calls, %d bytes" % (name, len(x), len(a_call), int((~is_a).sum()), os.path.getsize(path)))
+
+
 def main():
+    if "--symbolwalk" in sys.argv:
+        return gen_symbolwalk()
     if "--funcube" in sys.argv:
         return gen_funcube()
     if "--meteor" in sys.argv:
