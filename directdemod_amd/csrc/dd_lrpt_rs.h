@@ -1,0 +1,166 @@
+// Meteor-M2 LRPT: Reed-Solomon (255,223) correction of a frame's four interleaved codewords (DESIGN.md section 4.15 defines the
+// field, the code and the decoder's result; lrpt.py restates them in NumPy), included by dd_afsk.hip after dd_lrpt.h.
+//
+//   k_lrpt_rs  -- one workgroup per frame, one wave per codeword: syndromes, the all-zero exit, Berlekamp-Massey with a lane per
+//                 locator coefficient, a search of the 255 positions with a lane per position, Forney's value in the same lane,
+//                 and the corrected word's syndromes before anything is written
+#pragma once
+
+#define DD_RS_N 255
+#define DD_RS_T 16
+#define DD_RS_BETA 11                 // beta = alpha^11
+#define DD_RS_ROOT0 112               // c(beta^j) = 0 for j = 112 .. 143
+
+// GF(256) = GF(2)[x] / 0x187, alpha = 2: ex[i] = alpha^(i mod 255), so that ex[lg[a] + lg[b]] is a * b and
+// ex[lg[a] + 255 - lg[b]] is a / b for non-zero a, b with no reduction of the sum
+struct DDRsTables {
+    uint8_t ex[512];
+    uint8_t lg[256];
+};
+
+static constexpr DDRsTables dd_rs_make_tables() {
+    DDRsTables t{};
+    int v = 1;
+    for (int i = 0; i < 255; ++i) {
+        t.ex[i] = (uint8_t)v;
+        t.lg[v] = (uint8_t)i;
+        v <<= 1;
+        if (v & 0x100) v ^= 0x187;
+    }
+    for (int i = 255; i < 512; ++i) t.ex[i] = t.ex[i - 255];
+    return t;
+}
+
+__constant__ DDRsTables dd_rs_tables = dd_rs_make_tables();
+
+__device__ __forceinline__ int dd_gf_mul(const uint8_t* ex, const uint8_t* lg, int a, int b) {
+    const int t = ex[lg[a] + lg[b]];              // lg[0] = 0: the load is in range whatever a and b are
+    return (a != 0 && b != 0) ? t : 0;
+}
+
+// a * alpha^lb, lb in 0..254
+__device__ __forceinline__ int dd_gf_mul_log(const uint8_t* ex, const uint8_t* lg, int a, int lb) {
+    const int t = ex[lg[a] + lb];
+    return a != 0 ? t : 0;
+}
+
+// S_j = c(beta^(112 + j)) in lane j < 32, 0 in the others.  row[0] = 0 and row[1 + i] = byte i, the coefficient of x^(254 - i):
+// lane j runs Horner over row[0..127], lane 32 + j over row[128..255], and the first half is worth x^128 more.
+__device__ __forceinline__ int dd_rs_syndrome(const uint8_t* ex, const uint8_t* lg, const uint8_t* row, int lane) {
+    const int j = lane & 31;
+    const int lr = (DD_RS_BETA * (DD_RS_ROOT0 + j)) % 255;
+    const uint8_t* src = row + ((lane >> 5) << 7);
+    int acc = 0;
+    for (int s = 0; s < 128; ++s) acc = dd_gf_mul_log(ex, lg, acc, lr) ^ src[s];
+    const int hi = __shfl(acc, j, 64), lo = __shfl(acc, j + 32, 64);
+    return lane < 32 ? (dd_gf_mul_log(ex, lg, hi, (lr * 128) % 255) ^ lo) : 0;
+}
+
+// Frame blockIdx.x.  After the staging barrier the four waves share nothing but the read-only tables: a clean codeword leaves at
+// the all-zero test while a damaged one runs on, so there is NO workgroup barrier below the first -- only wave-level operations.
+__global__ void __launch_bounds__(256) k_lrpt_rs(const uint8_t* __restrict__ bodies, uint8_t* __restrict__ fixed, int* __restrict__ errors) {
+    __shared__ uint8_t ex[512];
+    __shared__ uint8_t lg[256];
+    __shared__ uint8_t cw[4][256];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int64_t f = blockIdx.x;
+    ex[tid] = dd_rs_tables.ex[tid];
+    ex[tid + 256] = dd_rs_tables.ex[tid + 256];
+    lg[tid] = dd_rs_tables.lg[tid];
+    for (int i = tid; i < DD_LRPT_BODY; i += 256) cw[i & 3][1 + (i >> 2)] = bodies[f * DD_LRPT_BODY + i];
+    if (tid < 4) cw[tid][0] = 0;
+    __syncthreads();
+
+    uint8_t* row = cw[w];
+    int pos[4], got[4], out[4];                         // lane's positions lane + 64 q, the received bytes, what leaves
+    for (int q = 0; q < 4; ++q) {
+        pos[q] = lane + 64 * q;
+        got[q] = pos[q] < DD_RS_N ? row[1 + pos[q]] : 0;
+        out[q] = got[q];
+    }
+    const int S = dd_rs_syndrome(ex, lg, row, lane);
+    int nerr = 0;
+    if (__ballot(S != 0) != 0) {
+        nerr = -1;
+        // Berlekamp-Massey: lane i holds the coefficients C_i, B_i; the discrepancy and all that follows from it are wave-uniform
+        int C = lane == 0, B = C, L = 0, m = 1, b = 1;
+        for (int n = 0; n < 2 * DD_RS_T; ++n) {
+            const int sv = __shfl(S, (n - lane) & 63, 64);                  // S_(n-i)
+            int d = (lane <= L && lane <= n) ? dd_gf_mul(ex, lg, C, sv) : 0;
+            for (int off = 32; off >= 1; off >>= 1) d ^= __shfl_xor(d, off, 64);
+            d = __builtin_amdgcn_readfirstlane(d);
+            const int Bs = __shfl(B, (lane - m) & 63, 64);                  // B_(i-m)
+            if (d == 0) {
+                ++m;
+                continue;
+            }
+            const int coef = ex[lg[d] + 255 - lg[b]];
+            const int T = C;
+            C ^= (lane >= m && lane <= 2 * DD_RS_T) ? dd_gf_mul(ex, lg, coef, Bs) : 0;
+            if (2 * L <= n) {
+                L = n + 1 - L;
+                B = T;
+                b = d;
+                m = 1;
+            } else {
+                ++m;
+            }
+        }
+        const unsigned long long nz = __ballot(C != 0 && lane <= 2 * DD_RS_T);        // bit 0 is set: C_0 = 1
+        if (L <= DD_RS_T && 63 - __clzll((long long)nz) == L) {
+            int lam[DD_RS_T + 1], om[DD_RS_T];
+            for (int k = 0; k <= DD_RS_T; ++k) lam[k] = __builtin_amdgcn_readlane(C, k);
+            // Omega = S Lambda mod x^32, of degree < L <= 16: lane k < 16 forms Omega_k
+            int mine = 0;
+            for (int i = 0; i <= DD_RS_T; ++i) {
+                const int sv = __shfl(S, (lane - i) & 63, 64);
+                mine ^= (i <= lane && lane < DD_RS_T) ? dd_gf_mul(ex, lg, lam[i], sv) : 0;
+            }
+            for (int k = 0; k < DD_RS_T; ++k) om[k] = __builtin_amdgcn_readlane(mine, k);
+            int roots = 0;
+            bool zero = false;
+            for (int q = 0; q < 4; ++q) {
+                const bool in = pos[q] < DD_RS_N;
+                const int lX = in ? (DD_RS_BETA * (254 - pos[q])) % 255 : 0;             // position i has locator X = beta^(254 - i)
+                const int lx = (255 - lX) % 255, lx2 = (2 * lx) % 255;                   // X^-1 and its square
+                int v = lam[DD_RS_T];
+                for (int k = DD_RS_T - 1; k >= 0; --k) v = dd_gf_mul_log(ex, lg, v, lx) ^ lam[k];
+                const bool root = in && v == 0;
+                int num = om[DD_RS_T - 1];
+                for (int k = DD_RS_T - 2; k >= 0; --k) num = dd_gf_mul_log(ex, lg, num, lx) ^ om[k];
+                int den = lam[DD_RS_T - 1];                                              // Lambda'(x): the odd terms, one degree down
+                for (int k = DD_RS_T - 3; k >= 1; k -= 2) den = dd_gf_mul_log(ex, lg, den, lx2) ^ lam[k];
+                // the value X^(1 - 112) Omega(X^-1) / Lambda'(X^-1); -111 = 144 modulo 255
+                const int e = (num != 0 && den != 0) ? ex[(lg[num] + 255 - lg[den] + (lX * 144) % 255) % 255] : 0;
+                roots += __popcll(__ballot(root));
+                zero = zero || __ballot(root && e == 0) != 0;
+                if (root) out[q] = got[q] ^ e;
+            }
+            bool good = roots == L && !zero;
+            if (good) {
+                // the corrected word's syndromes, from the wave's own row: the stores are ordered before the loads within the wave
+                for (int q = 0; q < 4; ++q)
+                    if (pos[q] < DD_RS_N) row[1 + pos[q]] = (uint8_t)out[q];
+                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+                good = __ballot(dd_rs_syndrome(ex, lg, row, lane) != 0) == 0;
+            }
+            if (good) nerr = L;
+        }
+        if (nerr < 0)
+            for (int q = 0; q < 4; ++q) out[q] = got[q];
+    }
+    uint8_t* dst = fixed + f * DD_LRPT_BODY + w;
+    for (int q = 0; q < 4; ++q)
+        if (pos[q] < DD_RS_N) dst[4 * pos[q]] = (uint8_t)out[q];
+    if (lane == 0) errors[4 * f + w] = nerr;
+}
+
+extern "C" int dd_lrpt_rs(const uint8_t* bodies, int64_t nframes, uint8_t* fixed, int32_t* errors, void* stream) {
+    DD_REQUIRE(nframes >= 0 && nframes <= 0x7fffffff, "dd_lrpt_rs: sizes");
+    if (nframes == 0) return DD_OK;
+    DD_REQUIRE(bodies != nullptr && fixed != nullptr && errors != nullptr, "dd_lrpt_rs: null buffer");
+    hipLaunchKernelGGL(k_lrpt_rs, dim3((unsigned)nframes), dim3(256), 0, dd_stream(stream), bodies, fixed, errors);
+    DD_LAUNCH_CHECK();
+    return DD_OK;
+}

@@ -1,7 +1,9 @@
 """
 Meteor-M2 QPSK sync detection -- the reference's decode_meteorm2 surface (decode_meteorm2.py): `useful`, `getSyncs` and the
 module helpers `lim` / `limBin`, plus `getSymbols`, the PLL-corrected soft symbols (gardnerA after pllObj.loop), and beyond the
-reference `getFrames` / `frameInfo`: the LRPT channel frames decoded from those symbols (lrpt.py).
+reference `getFrames` / `frameInfo`: the LRPT channel frames decoded from those symbols (lrpt.py), and
+`getVCDUs` / `rsInfo` / `getPackets` / `packetInfo`: the frames after Reed-Solomon correction and the CCSDS source packets
+reassembled from them.
 
 One decode pass, cached, feeds both properties.  Per chunk of the recording (the reference's chunker, no chunker handed to the
 signal, so the mixer phase restarts at 0 in every chunk): offsetFreq in the reference's float64 arithmetic (qpsk.mix: the package's
@@ -29,7 +31,10 @@ class decode_meteorm2(symbolsync.SyncDecoder):
     `useful`: 1 if two MAXSYNCs lie 0.11 s +- 0.05 s apart; `getSyncs`: np.float64 positions; `getSymbols`: at 72000 Hz.
     minsyncs: (ctr, template 0 = sync2mhz / 1 = sync2mhz2) per MINSYNC event; buffers: (intervals, maxBuffStart, template).
     `getFrames`: uint8[n, 1020], the de-randomised LRPT frame bodies in stream order (Reed-Solomon parity still attached);
-    `frameInfo`: one lrpt.INFO record per frame.  Both come from the same cached walk, whether or not the 120-bit sync was seen."""
+    `frameInfo`: one lrpt.INFO record per frame.  Both come from the same cached walk, whether or not the 120-bit sync was seen.
+    `getVCDUs`: uint8[n, 892], the frames' data bytes after Reed-Solomon correction, row-aligned with getFrames; `rsInfo`: one
+    lrpt.RS_INFO record per frame; `getPackets`: the source packets as bytes, in order of completion; `packetInfo`: one
+    lrpt.PACKET_INFO record per packet."""
     WALKER = qpsk.Walker
     STAGES = ("front_end",)
     SPACING = (0.11, 0.05)
@@ -39,6 +44,7 @@ class decode_meteorm2(symbolsync.SyncDecoder):
         self._bw = 70000 if bw is None else bw
         self._offset = offset
         self._frames = None
+        self._rs = None
 
     @property
     def getFrames(self):
@@ -50,6 +56,47 @@ class decode_meteorm2(symbolsync.SyncDecoder):
         """Per frame (lrpt.INFO): symbol (of the marker's first bit), sample (the walk's A sample of that symbol), hypothesis,
         asm_score (of 52), asm_errors (of 32 decoded marker bits), corrected (channel bits the decoder changed), vcid, counter"""
         return self._decode_frames()[1]
+
+    @property
+    def getVCDUs(self):
+        """The frames' 892 data bytes, uint8[n, 892], row-aligned with getFrames: corrected where the codeword was decodable, as
+        received where it was not"""
+        return self._decode_rs()[0]
+
+    @property
+    def rsInfo(self):
+        """Per frame (lrpt.RS_INFO): errors (bytes changed in each of the four codewords, -1: not decodable), ok (all four decoded),
+        and vcid, counter from the corrected header (meaningful when ok)"""
+        return self._decode_rs()[1]
+
+    @property
+    def getPackets(self):
+        """The CCSDS source packets (bytes, header included) reassembled from the ok frames, in order of completion"""
+        return self._decode_rs()[2]
+
+    @property
+    def packetInfo(self):
+        """Per packet (lrpt.PACKET_INFO): apid, flags, count, vcid, frame (the row of getFrames in which its first byte lies), length"""
+        return self._decode_rs()[3]
+
+    def _decode_rs(self):
+        if self._rs is not None:
+            return self._rs
+        bodies = self._decode_frames()[0]
+        t0 = time.perf_counter()
+        fixed, errors = lrpt.reed_solomon(bodies)
+        info = np.zeros(len(bodies), dtype=lrpt.RS_INFO)
+        info["errors"] = errors
+        info["ok"] = np.all(errors >= 0, axis=1)
+        info["vcid"] = fixed[:, 1] & 0x3F
+        info["counter"] = (fixed[:, 2].astype(np.int64) << 16) | (fixed[:, 3].astype(np.int64) << 8) | fixed[:, 4]
+        vcdus = np.ascontiguousarray(fixed[:, :lrpt.VCDU_BYTES])
+        t1 = time.perf_counter()
+        pkts, pinfo = lrpt.packets(vcdus, info["ok"], info["vcid"], info["counter"])
+        self.timings["lrpt_rs"] = t1 - t0
+        self.timings["lrpt_packets"] = time.perf_counter() - t1
+        self._rs = (vcdus, info, pkts, pinfo)
+        return self._rs
 
     def _decode_frames(self):
         if self._frames is not None:

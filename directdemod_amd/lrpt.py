@@ -6,7 +6,14 @@ under the eight phase / IQ-swap hypotheses (`asm_candidates`), the block-wise so
 code (`viterbi`) and the per-frame finish (`finish`: marker check, de-randomisation, re-encode count).  Host stages, O(frames):
 `frame_starts`, `vcdu_header`.  NumPy restatements of the same definitions, for the tests: `encode`, `pn_sequence`, `hypothesis`,
 `soft_np`, `asm_scores`, `asm_candidates_np`, `viterbi_blocks`, `finish_np`.  All arithmetic is integer.
+
+Section 4.15 finishes the channel decoder: Reed-Solomon (255,223) correction of a frame's four interleaved codewords on the device
+(`reed_solomon`, dd_lrpt_rs.h) and, on the host, the VCDU / M_PDU layer and the reassembly of CCSDS source packets (`mpdu_header`,
+`packet_header`, `packets`).  Restatements: `gf_tables`, `rs_generator`, `rs_encode`, `rs_syndromes`, `rs_decode_np`, `interleave`,
+`deinterleave`, `rs_frames_np`.
 """
+import functools
+
 import numpy as np
 
 from ._hip import DevArray, check, lib
@@ -22,6 +29,13 @@ BLOCK, WARM = 512, 128                    # trellis steps decoded per block; ste
 G1, G2 = 0x79, 0x5B
 INFO = np.dtype([("symbol", np.int64), ("sample", np.int64), ("hypothesis", np.int64), ("asm_score", np.int64),
                  ("asm_errors", np.int64), ("corrected", np.int64), ("vcid", np.int64), ("counter", np.int64)])
+GF_POLY, RS_BETA_LOG, RS_FIRST_ROOT = 0x187, 11, 112     # GF(256) = GF(2)[x] / 0x187, alpha = 2; beta = alpha^11; c(beta^j) = 0, j = 112..143
+RS_N, RS_K, RS_T, RS_DEPTH = 255, 223, 16, 4
+VCDU_BYTES, ZONE_BYTES = 892, 882                         # a frame's data bytes; the M_PDU packet zone, VCDU bytes 10..891
+FILL_VCID, NO_HEADER = 63, 0x7FF
+RS_INFO = np.dtype([("errors", np.int64, (RS_DEPTH,)), ("ok", np.bool_), ("vcid", np.int64), ("counter", np.int64)])
+PACKET_INFO = np.dtype([("apid", np.int64), ("flags", np.int64), ("count", np.int64), ("vcid", np.int64), ("frame", np.int64),
+                        ("length", np.int64)])
 
 
 # ------------------------------------------------------------------ the definitions in NumPy
@@ -175,6 +189,179 @@ def finish_np(bits, soft, nsym, p, h):
     return body, asm_errors, int(np.sum(code.ravel() != hard))
 
 
+# ------------------------------------------------------------------ section 4.15 in NumPy: GF(256), RS(255,223), interleave
+@functools.lru_cache(maxsize=None)
+def gf_tables():
+    """(exp uint8[512], log int16[256]): exp[i] = alpha^(i mod 255), so that exp[log[a] + log[b]] is a * b for non-zero a, b with no
+    reduction of the sum; log[0] is 0 and never meant"""
+    ex = np.zeros(512, dtype=np.uint8)
+    lg = np.zeros(256, dtype=np.int16)
+    v = 1
+    for i in range(255):
+        ex[i] = v
+        lg[v] = i
+        v <<= 1
+        if v & 0x100:
+            v ^= GF_POLY
+    ex[255:510] = ex[:255]
+    ex[510:] = ex[:2]
+    ex.setflags(write=False)
+    lg.setflags(write=False)
+    return ex, lg
+
+
+def gf_mul(a, b):
+    """a * b in GF(256), element-wise over uint8 arrays"""
+    ex, lg = gf_tables()
+    a, b = np.asarray(a, dtype=np.uint8), np.asarray(b, dtype=np.uint8)
+    return np.where((a == 0) | (b == 0), 0, ex[lg[a] + lg[b]]).astype(np.uint8)
+
+
+@functools.lru_cache(maxsize=None)
+def rs_generator():
+    """g(x) = prod over j = 112..143 of (x - beta^j), uint8[33], low to high coefficient"""
+    ex, _ = gf_tables()
+    g = np.array([1], dtype=np.uint8)
+    for j in range(RS_FIRST_ROOT, RS_FIRST_ROOT + 2 * RS_T):
+        root = ex[RS_BETA_LOG * j % 255]
+        g = np.concatenate(([0], g)).astype(np.uint8) ^ np.concatenate((gf_mul(g, root), [0])).astype(np.uint8)
+    g.setflags(write=False)
+    return g
+
+
+def rs_encode(data):
+    """data uint8[..., 223] -> codewords uint8[..., 255]: the data, then the remainder of data(x) x^32 modulo g(x), high coefficient
+    first"""
+    data = np.asarray(data, dtype=np.uint8)
+    if data.shape[-1] != RS_K:
+        raise ValueError("rs_encode: 223 data bytes per word")
+    taps = rs_generator()[2 * RS_T - 1::-1]                         # g31 .. g0: register cell k holds the coefficient of x^(31 - k)
+    reg = np.zeros(data.shape[:-1] + (2 * RS_T,), dtype=np.uint8)
+    for i in range(RS_K):
+        fb = data[..., i] ^ reg[..., 0]
+        reg = np.concatenate((reg[..., 1:], np.zeros_like(reg[..., :1])), axis=-1) ^ gf_mul(fb[..., None], taps)
+    return np.concatenate((data, reg), axis=-1)
+
+
+def rs_syndromes(words):
+    """words uint8[..., 255] -> uint8[..., 32]: S_j = c(beta^(112 + j)) with byte i the coefficient of x^(254 - i)"""
+    ex, lg = gf_tables()
+    words = np.asarray(words, dtype=np.uint8)
+    if words.shape[-1] != RS_N:
+        raise ValueError("rs_syndromes: 255 bytes per word")
+    lr = (RS_BETA_LOG * (RS_FIRST_ROOT + np.arange(2 * RS_T)) % 255).astype(np.int16)
+    acc = np.zeros(words.shape[:-1] + (2 * RS_T,), dtype=np.uint8)
+    for i in range(RS_N):
+        acc = np.where(acc == 0, 0, ex[lg[acc] + lr]).astype(np.uint8) ^ words[..., i, None]
+    return acc
+
+
+def _poly_at(coef, lx):
+    """sum of coef[k] * alpha^(k lx[p]) over k, for every p: uint8[len(lx)]"""
+    ex, lg = gf_tables()
+    coef = np.asarray(coef, dtype=np.uint8)
+    k = np.arange(len(coef), dtype=np.int64)[:, None]
+    terms = np.where(coef[:, None] == 0, 0, ex[(lg[coef].astype(np.int64)[:, None] + k * lx[None, :]) % 255])
+    return np.bitwise_xor.reduce(terms.astype(np.uint8), axis=0)
+
+
+def _rs_correction(S):
+    """syndromes uint8[32], not all zero -> (positions, values) of the error pattern Berlekamp-Massey, a search of the 255 positions
+    and Forney's formula propose, or None when they propose none: a locator of degree > 16, fewer roots than its degree, a zero
+    value.  The caller checks the corrected word's syndromes."""
+    ex, lg = (t.tolist() for t in gf_tables())
+    S = [int(v) for v in S]
+
+    def mul(a, b):
+        return ex[lg[a] + lg[b]] if a and b else 0
+    C, B, L, m, b = [1] + [0] * 32, [1] + [0] * 32, 0, 1, 1
+    for n in range(2 * RS_T):
+        d = S[n]
+        for i in range(1, L + 1):
+            d ^= mul(C[i], S[n - i])
+        if d == 0:
+            m += 1
+            continue
+        coef = ex[lg[d] + 255 - lg[b]]
+        T = C[:]
+        for i in range(m, 33):
+            C[i] ^= mul(coef, B[i - m])
+        if 2 * L <= n:
+            L, B, b, m = n + 1 - L, T, d, 1
+        else:
+            m += 1
+    if L > RS_T or max(i for i in range(33) if C[i]) != L:
+        return None
+    lam = C[:RS_T + 1]
+    lX = RS_BETA_LOG * (254 - np.arange(RS_N, dtype=np.int64)) % 255       # position i has locator X = beta^(254 - i)
+    lx = (255 - lX) % 255                                                      # X^-1
+    pos = np.nonzero(_poly_at(lam, lx) == 0)[0]
+    if len(pos) != L:
+        return None
+    omega = [0] * RS_T                                                         # S Lambda mod x^32 has degree < L <= 16
+    for k in range(RS_T):
+        for i in range(min(k, RS_T) + 1):
+            omega[k] ^= mul(lam[i], S[k - i])
+    deriv = [lam[i + 1] if i % 2 == 0 else 0 for i in range(RS_T)]              # Lambda'(x): the odd terms, one degree down
+    num, den = _poly_at(omega, lx[pos]), _poly_at(deriv, lx[pos])
+    if np.any(num == 0) or np.any(den == 0):
+        return None
+    glog = gf_tables()[1]
+    val = gf_tables()[0][(glog[num].astype(np.int64) - glog[den] + (1 - RS_FIRST_ROOT) * lX[pos]) % 255]
+    return pos, val
+
+
+def rs_decode_np(words):
+    """words uint8[..., 255] -> (fixed uint8[..., 255], errors int32[...]): the codeword within Hamming distance 16 of each word and
+    how many bytes it changes, or the word itself and -1 where there is none.  Table-driven; the syndromes before and after are
+    computed for all words together, the locator word by word for the damaged ones."""
+    words = np.asarray(words, dtype=np.uint8)
+    if words.shape[-1] != RS_N:
+        raise ValueError("rs_decode_np: 255 bytes per word")
+    flat = words.reshape(-1, RS_N)
+    fixed = flat.copy()
+    errors = np.zeros(len(flat), dtype=np.int32)
+    syn = rs_syndromes(flat)
+    tried = []
+    for w in np.nonzero(syn.any(axis=1))[0]:
+        fix = _rs_correction(syn[w])
+        if fix is None:
+            errors[w] = -1
+        else:
+            fixed[w, fix[0]] ^= fix[1]
+            errors[w] = len(fix[0])
+            tried.append(w)
+    if tried:
+        tried = np.array(tried)
+        bad = tried[rs_syndromes(fixed[tried]).any(axis=1)]
+        fixed[bad] = flat[bad]
+        errors[bad] = -1
+    return fixed.reshape(words.shape), errors.reshape(words.shape[:-1])
+
+
+def interleave(words):
+    """codewords uint8[..., 4, 255] -> bodies uint8[..., 1020]: body byte k is byte k // 4 of codeword k % 4"""
+    words = np.asarray(words, dtype=np.uint8)
+    if words.shape[-2:] != (RS_DEPTH, RS_N):
+        raise ValueError("interleave: four words of 255 bytes")
+    return np.ascontiguousarray(np.swapaxes(words, -1, -2)).reshape(words.shape[:-2] + (BODY_BYTES,))
+
+
+def deinterleave(bodies):
+    """bodies uint8[..., 1020] -> codewords uint8[..., 4, 255]"""
+    bodies = np.asarray(bodies, dtype=np.uint8)
+    if bodies.shape[-1] != BODY_BYTES:
+        raise ValueError("deinterleave: 1020 bytes per body")
+    return np.ascontiguousarray(np.swapaxes(bodies.reshape(bodies.shape[:-1] + (RS_N, RS_DEPTH)), -1, -2))
+
+
+def rs_frames_np(bodies):
+    """bodies uint8[n, 1020] -> (fixed uint8[n, 1020], errors int32[n, 4]): every decodable codeword corrected, parity included"""
+    bodies = np.asarray(bodies, dtype=np.uint8).reshape(-1, BODY_BYTES)
+    fixed, errors = rs_decode_np(deinterleave(bodies))
+    return interleave(fixed), errors
+
+
 # ------------------------------------------------------------------ host stages
 def frame_starts(cands, nsym):
     """candidates int64[m, 3] = (p, h, score) -> the frame starts among them, sorted by p: no candidate within +-31 symbols is better
@@ -204,6 +391,66 @@ def vcdu_header(body):
     body = np.frombuffer(body, dtype=np.uint8) if isinstance(body, (bytes, bytearray)) else np.asarray(body, dtype=np.uint8)
     b = [int(v) for v in body[:6]]
     return dict(version=b[0] >> 6, scid=((b[0] & 0x3F) << 2) | (b[1] >> 6), vcid=b[1] & 0x3F, counter=(b[2] << 16) | (b[3] << 8) | b[4])
+
+
+def mpdu_header(vcdu):
+    """spare bits and the first-header pointer from a VCDU's bytes 8..9: fhp = ((b8 & 7) << 8) | b9"""
+    v = np.frombuffer(vcdu, dtype=np.uint8) if isinstance(vcdu, (bytes, bytearray)) else np.asarray(vcdu, dtype=np.uint8)
+    return dict(spare=int(v[8]) >> 3, fhp=((int(v[8]) & 7) << 8) | int(v[9]))
+
+
+def packet_header(pkt):
+    """version, type, secondary-header flag, APID, sequence flags, sequence count and the total length 7 + (b4 << 8 | b5) from a
+    source packet's first six bytes"""
+    b = [int(v) for v in bytes(pkt[:6])]
+    return dict(version=b[0] >> 5, type=(b[0] >> 4) & 1, secondary=(b[0] >> 3) & 1, apid=((b[0] & 7) << 8) | b[1], flags=b[2] >> 6,
+                count=((b[2] & 0x3F) << 8) | b[3], length=7 + ((b[4] << 8) | b[5]))
+
+
+def packets(vcdus, ok, vcids, counters):
+    """The source packets of the frames in stream order (section 4.15, reassembly) -> (list of bytes, info PACKET_INFO[m]).
+    vcdus uint8[n, 892]; ok, vcids, counters per frame (rsInfo's fields)."""
+    vcdus = np.asarray(vcdus, dtype=np.uint8).reshape(-1, VCDU_BYTES)
+    part, last, out, rows = {}, {}, [], []                  # per channel: (bytes so far, frame of the first byte); the last counter
+
+    def emit(pkt, vcid, frame):
+        h = packet_header(pkt)
+        out.append(bytes(pkt))
+        rows.append((h["apid"], h["flags"], h["count"], vcid, frame, len(pkt)))
+
+    def complete(pkt):
+        return len(pkt) >= 6 and len(pkt) == packet_header(pkt)["length"]
+    for f, (v, good, vcid, ctr) in enumerate(zip(vcdus, ok, vcids, counters)):
+        if not good:
+            part.clear()                                    # whose frame it was is not known
+            continue
+        vcid, ctr = int(vcid), int(ctr)
+        if vcid == FILL_VCID:
+            continue
+        if vcid in last and ctr != (last[vcid] + 1) & 0xFFFFFF:
+            part.pop(vcid, None)
+        last[vcid] = ctr
+        fhp = mpdu_header(v)["fhp"]
+        zone = v[10:].tobytes()
+        held = part.pop(vcid, None)
+        if fhp == NO_HEADER:
+            if held is not None:
+                part[vcid] = (held[0] + zone, held[1])
+            continue
+        if fhp >= ZONE_BYTES:
+            continue
+        if held is not None and complete(held[0] + zone[:fhp]):
+            emit(held[0] + zone[:fhp], vcid, held[1])
+        pos = fhp
+        while pos < ZONE_BYTES:
+            rest = zone[pos:]
+            if len(rest) < 6 or len(rest) < packet_header(rest)["length"]:
+                part[vcid] = (rest, f)
+                break
+            n = packet_header(rest)["length"]
+            emit(rest[:n], vcid, f)
+            pos += n
+    return out, np.array(rows, dtype=PACKET_INFO).reshape(-1)
 
 
 # ------------------------------------------------------------------ device stages
@@ -248,3 +495,24 @@ def finish(bits, soft, nsym, spans):
     info = DevArray(max(3 * n, 1), np.int32)
     check(lib().dd_lrpt_finish(bits.ptr, soft.ptr, nsym, s.ctypes.data, n, bodies.ptr, info.ptr, None), "dd_lrpt_finish")
     return bodies.view(0, n * BODY_BYTES).to_host().reshape(n, BODY_BYTES), info.view(0, 3 * n).to_host().reshape(n, 3)
+
+
+def reed_solomon(bodies):
+    """bodies (host uint8[n, 1020] or a device uint8 array of n * 1020 bytes) -> (fixed uint8[n, 1020], errors int32[n, 4]), both on
+    the host: every codeword within 16 byte errors of a codeword corrected (parity included) with the count, the others unchanged
+    with -1"""
+    if isinstance(bodies, DevArray):
+        if bodies.dtype != np.dtype(np.uint8) or bodies.n % BODY_BYTES:
+            raise ValueError("reed_solomon: a device uint8 array of n * 1020 bytes expected")
+        dev = bodies
+    else:
+        host = np.ascontiguousarray(bodies, dtype=np.uint8)
+        if host.ndim != 2 or host.shape[1] != BODY_BYTES:
+            raise ValueError("reed_solomon: uint8[n, 1020] expected")
+        dev = DevArray.from_host(host)
+    n = dev.n // BODY_BYTES
+    fixed = DevArray(max(n * BODY_BYTES, 1), np.uint8)
+    errors = DevArray(max(RS_DEPTH * n, 1), np.int32)
+    check(lib().dd_lrpt_rs(dev.ptr, n, fixed.ptr, errors.ptr, None), "dd_lrpt_rs")
+    return (fixed.view(0, n * BODY_BYTES).to_host().reshape(n, BODY_BYTES),
+            errors.view(0, RS_DEPTH * n).to_host().reshape(n, RS_DEPTH))

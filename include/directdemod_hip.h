@@ -472,7 +472,11 @@ int dd_meteor_maxcorr(const void* lim, int64_t lim_len, const int64_t* bufs_host
  *     at most 65535 spans per call.
  * dd_lrpt_finish -- per frame i (8192 bits of dd_lrpt_viterbi's output, the same spans): bodies[1020 i ..] = bytes 4..1023 XOR
  *     the CCSDS pseudo-noise sequence; info[3i .. 3i+2] = (marker bits in error, hard input bits of steps 6..8191 that differ
- *     from the re-encoded decoded bits, the virtual channel id = body[1] & 0x3F). */
+ *     from the re-encoded decoded bits, the virtual channel id = body[1] & 0x3F).
+ * dd_lrpt_rs -- Reed-Solomon (255,223) correction (GF(256) modulo 0x187, roots (alpha^11)^j for
+ *     j = 112..143, conventional basis, interleave depth 4) of the four codewords of each of nframes 1020-byte bodies:
+ *     fixed[1020 i ..] = the body with every codeword that lies within 16 byte errors of a codeword replaced by it (parity
+ *     included), the others as received; errors[4 i + w] = the bytes changed in codeword w (0..16), or -1 where it was left. */
 int dd_lrpt_soft(const void* sym, int64_t nsym, int8_t* soft, void* stream);
 int dd_lrpt_asm_search(const int8_t* soft, int64_t nsym, int min_score, int64_t cap, int64_t* cand, unsigned long long* count,
                        void* stream);
@@ -480,6 +484,7 @@ int dd_lrpt_viterbi(const int8_t* soft, int64_t nsym, const int64_t* spans_host,
                     uint8_t* bits_packed, void* stream);
 int dd_lrpt_finish(const uint8_t* bits_packed, const int8_t* soft, int64_t nsym, const int64_t* spans_host, int64_t nspans,
                    uint8_t* bodies, int32_t* info, void* stream);
+int dd_lrpt_rs(const uint8_t* bodies, int64_t nframes, uint8_t* fixed, int32_t* errors, void* stream);
 
 /* ---- Funcube BPSK sync detection (decode_funcube.py:148-306) ------------------------------------------------------------
  * dd_funcube_mix_ramp -- dd_meteor_mix with the frequency formed per sample: th = ((w * f[k]) * k) * inv_fs, w = -2 pi,

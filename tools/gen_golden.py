@@ -610,6 +610,27 @@ def gen_lrpt():
               (name, raw.shape[0], start, len(sym), cap["syncs"], cap["cpu"], os.path.getsize(path)))
 
 
+def gen_lrpt_rs():
+    """gen_lrpt for the recording of tests/_rs.py that carries RS-encoded frames and two fades (case b): tests/golden/lrpt_rs_b.npz.
+    gen_golden.py --lrpt-rs"""
+    install_shim()
+    sys.path.insert(0, REF)
+    sys.path.insert(0, ROOT)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import _rs
+    from directdemod import decode_meteorm2 as dmet
+    for name in sorted(_rs.CASES):
+        raw, _, start = _rs.case(name)
+        cap = _meteor_run(raw, 0)
+        sym = np.array([r[3] for r in cap["loop"]], dtype=np.complex128)
+        soft = np.array([dmet.lim(v / 2) for s in sym for v in (s.real, s.imag)], dtype=np.int8)
+        path = os.path.join(OUT, "lrpt_rs_%s.npz" % name)
+        np.savez_compressed(path, sha256=np.array(_rs.sha256(raw)), n=np.int64(raw.shape[0]), nsym=np.int64(len(sym)), soft=soft,
+                            ref_cpu_s=np.float64(cap["cpu"]))
+        print("lrpt_rs %s: n %d, start bit %d, %d symbols, syncs %s, cpu %.1f s, %d bytes" %
+              (name, raw.shape[0], start, len(sym), cap["syncs"], cap["cpu"], os.path.getsize(path)))
+
+
 def _funcube_run(raw, offset, corrfreq, center, channel, walk=None):
     """The reference's decode_funcube.getSyncs on an in-memory recording, tapped like _meteor_run (walk: see _walk_taps): the sample index of every
     agc.adjust call (B or A: an A call is the one costas.loop follows), the AGC'd values, costas phase / freq after each loop, the
@@ -834,6 +855,8 @@ def main():
         return gen_funcube()
     if "--meteor" in sys.argv:
         return gen_meteor()
+    if "--lrpt-rs" in sys.argv:
+        return gen_lrpt_rs()
     if "--lrpt" in sys.argv:
         return gen_lrpt()
     if "--afsk-frames" in sys.argv:
