@@ -86,6 +86,9 @@ SIGNATURES = {
     "dd_debug_chain_select": (_int, [C.POINTER(C.c_double), _int, _int, _int, _int, C.c_char_p, C.POINTER(_int)]),
     "dd_debug_cos_fit": (_int, [C.POINTER(C.c_double), _int, C.POINTER(C.c_double), C.POINTER(_int)]),
     "dd_debug_sync_envelope": (_int, [_p, _i64, _int, _int, _p, _p]),
+    "dd_debug_sync_prefilter": (_int, [_p, _i64, _int, C.POINTER(C.c_double), _int, _int, _p, _p]),
+    "dd_debug_sync_tail": (_int, [_p, _p, _i64, _int, C.POINTER(C.c_double), _int, _int, C.POINTER(_int), _pi64,
+                                  C.POINTER(C.c_double), C.POINTER(C.c_double), _p]),
     "dd_memcpy_h2d": (_int, [_p, _p, _sz, _p]),
     "dd_memcpy_d2h": (_int, [_p, _p, _sz, _p]),
     "dd_memcpy_d2d": (_int, [_p, _p, _sz, _p]),

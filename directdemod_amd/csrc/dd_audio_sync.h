@@ -1,6 +1,7 @@
 // getAccurateSync's windows, batched (decode_noaa.py:808-880): dd_noaa_sync_windows(_multi), and dd_noaa_prepare.  The
 // windows' envelope is ONE stage (sync_envelope_stage: own transform, the library's padded real transforms, the library's length-N
-// complex pair), which the production entry runs per batch and dd_debug_sync_envelope runs alone.  Its Hilbert-kernel spectra and
+// complex pair), which the production entry runs per batch and dd_debug_sync_envelope runs alone; likewise the envelope's pre-filter
+// (sync_prefilter_stage, dd_debug_sync_prefilter) and the scan / correlation / peak tail (sync_tail_stage, dd_debug_sync_tail).  Its Hilbert-kernel spectra and
 // the padded convolution's body are those of dd_audio_envelope.h; the scan and the needle's run table those of dd_audio_xcorr.h.
 // One of the six parts of dd_audio.hip (one translation unit: the parts share the plan cache, the float64 transform and the scratch
 // buffers of dd_audio.hip and are included there, each using only the parts before it).  Internal; not a stand-alone header.
@@ -59,6 +60,9 @@ __global__ void __launch_bounds__(256) k_sync_fm(const float2* __restrict__ Y, i
 // the maximum provided it exceeds the threshold.  Also the two "extras": peak height and the mean of the
 // next needle-length of the envelope.  The correlation values are reduced where they are produced (first
 // maximum, two largest, two smallest per tile of 1024 outputs); the correlation array itself is never stored.
+// A window whose maximum does not exceed the threshold (every correlation the same value), or whose correlation holds a NaN (a NaN
+// sample; a stretch without energy as long as the needle, 0 / 0) -- where the reference would append None or sort NaNs -- comes back
+// as (INT64_MIN, NaN, NaN); a peak with i + 2 m >= n has its height and a NaN mean (:755).
 struct DDPk {
     double m1, m2, l1, l2;
     int64_t i1;
@@ -223,6 +227,36 @@ static int sync_envelope_stage(int route, const float2* X, int64_t L, int b, int
     return DD_OK;
 }
 
+// The envelope pre-filter of a batch of b windows: ENV [b][n] -> H [b][n] = filtfilt(taps, [1], ENV) (decode_noaa.py:677).  fit != NULL:
+// the prefix-sum form of a cosine series (dd_filtfilt_kernels.h; tab: dd_cos_table(K, fit->Q) on the device), else the tiled direct form
+// over `taps` (device, float64).  F1: f64 [b][n + 6 K], the first pass.
+static int sync_prefilter_stage(const double* ENV, int64_t n, int b, int K, const DDCosFit* fit, const double2* tab, const double* taps,
+                                double* F1, double* H, hipStream_t s) {
+    if (fit) return dd_filtfilt_cos_launch(ENV, n, F1, H, n, n, K, *fit, tab, b, s);
+    dd_filtfilt_launch<double>(ENV, n, F1, H, n, n, K, taps, b, s);
+    return DD_OK;
+}
+
+// The correlation/peak tail of a batch of b windows: hay [b][n] (the pre-filtered envelope) is searched for its window's needle (group:
+// device, one needle index per window, or NULL), ENV [b][n] gives the post-sync mean -> peak / height / tsync [b] on the device.
+// PQ: f64 [2][b][n + 1], the prefix sums of hay and hay^2; work: sync_tail_work_bytes(n, b), the scan's tile sums and the per-tile peak records.
+static size_t sync_tail_work_bytes(int64_t n, int b) {
+    const size_t stiles = (size_t)((n + DD_SCAN_TILE - 1) / DD_SCAN_TILE), xtiles = (size_t)((n + DD_XC_TILE - 1) / DD_XC_TILE);
+    return sizeof(double2) * b * stiles + sizeof(DDPk) * b * xtiles;
+}
+static void sync_tail_stage(const double* hay, const double* ENV, int64_t n, int b, int m, const DDRuns2& R2, const int* group,
+                            double* PQ, void* work, int64_t* peak, double* height, double* tsync, hipStream_t s) {
+    double* P = PQ;
+    double* Q = P + (size_t)b * (n + 1);
+    const int stiles = (int)((n + DD_SCAN_TILE - 1) / DD_SCAN_TILE), xtiles = (int)((n + DD_XC_TILE - 1) / DD_XC_TILE);
+    double2* spart = (double2*)work;
+    DDPk* ppart = (DDPk*)(spart + (size_t)b * stiles);
+    hipLaunchKernelGGL(k_scan_part, dim3(stiles, b), dim3(256), 0, s, hay, n, stiles, spart);
+    hipLaunchKernelGGL(k_scan_final, dim3(stiles, b), dim3(256), 0, s, hay, n, stiles, spart, P, Q);
+    hipLaunchKernelGGL(k_xcorr_runs_pk, dim3(8 * ((b + 7) / 8) * xtiles), dim3(256), 0, s, P, Q, n, m, R2, group, xtiles, b, ppart);
+    hipLaunchKernelGGL(k_sync_peak, dim3(b), dim3(256), 0, s, ppart, xtiles, ENV, n, m, peak, height, tsync);
+}
+
 // What dd_noaa_crude_tail will need for `n` audio samples in blocks of `block` -- the Hilbert-kernel spectra of the block and of the ragged
 // last block (host transforms: ~20 ms) and the transform's twiddle tables -- built ahead of time.  noaa_sync calls this from a thread of
 // its own when the decoder object is created, so that it overlaps the upload of the recording and the audio chain; the result sits in the
@@ -303,6 +337,99 @@ extern "C" int dd_debug_sync_envelope(const void* X_dev, int64_t L, int nwin, in
     hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(s);         // (before buf is freed: every return is behind it)
     if (rc != DD_OK) return rc;
     if (e1 != hipSuccess || e2 != hipSuccess) { dd_set_error("dd_debug_sync_envelope: %s", hipGetErrorString(e1 != hipSuccess ? e1 : e2)); return DD_ERR_HIP; }
+    return DD_OK;
+}
+
+// diagnostic: the envelope pre-filter of dd_noaa_sync_windows alone (sync_prefilter_stage).  x: device f64 [nwin][n] -> out: device f64
+// [nwin][n] = filtfilt(taps, [1], x).  route 0: the prefix-sum form of a cosine series (DD_ERR_UNSUPPORTED when the taps are none, or
+// too long for it), route 1: the tiled direct form on the same taps.  n <= 3 K is the batch's own error.  Synchronises.
+extern "C" int dd_debug_sync_prefilter(const double* x_dev, int64_t n, int nwin, const double* taps_host, int K, int route,
+                                       double* out_dev, void* stream) {
+    DD_REQUIRE(x_dev && out_dev && taps_host && nwin >= 1 && K >= 1 && n >= 1 && n < ((int64_t)1 << 30) && (route == 0 || route == 1), "arguments");
+    if (n <= 3 * (int64_t)K) {
+        dd_set_error("The length of the input vector x must be greater than padlen, which is %d.", 3 * K);
+        return DD_ERR_INVALID;
+    }
+    DDCosFit fit;
+    std::vector<double2> tabh(1);
+    if (route == 0) {
+        if (!dd_cos_fit(taps_host, K, &fit) || !dd_fc_ok(K, fit.Q)) {
+            dd_set_error("dd_debug_sync_prefilter: the prefix-sum form does not take these %d taps", K);
+            return DD_ERR_UNSUPPORTED;
+        }
+        dd_cos_table(K, fit.Q, tabh);
+    } else if (!dd_ff_tiled_ok(K, 8)) {
+        dd_set_error("dd_noaa_sync_windows: filter too long for the tiled zero-phase kernel");
+        return DD_ERR_INVALID;
+    }
+    hipStream_t s = dd_stream(stream);
+    std::lock_guard<std::mutex> lk(g_sync_mu);
+    DDDevBuf<double> taps, F1;
+    DDDevBuf<double2> tab;
+    DD_HIP_CHECK(taps.alloc((size_t)K));
+    DD_HIP_CHECK(tab.alloc(tabh.size()));
+    DD_HIP_CHECK(F1.alloc((size_t)nwin * (size_t)(n + 6 * (int64_t)K)));
+    hipError_t e0 = hipMemcpyAsync(taps.get(), taps_host, sizeof(double) * (size_t)K, hipMemcpyHostToDevice, s);
+    if (e0 == hipSuccess) e0 = hipMemcpyAsync(tab.get(), tabh.data(), sizeof(double2) * tabh.size(), hipMemcpyHostToDevice, s);
+    int rc = DD_OK;
+    if (e0 == hipSuccess) rc = sync_prefilter_stage(x_dev, n, nwin, K, route == 0 ? &fit : nullptr, tab.get(), taps.get(), F1.get(), out_dev, s);
+    hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(s);         // (before the buffers are freed: every return is behind it)
+    if (rc != DD_OK) return rc;
+    if (e0 != hipSuccess || e1 != hipSuccess || e2 != hipSuccess) {
+        dd_set_error("dd_debug_sync_prefilter: %s", hipGetErrorString(e0 != hipSuccess ? e0 : (e1 != hipSuccess ? e1 : e2)));
+        return DD_ERR_HIP;
+    }
+    return DD_OK;
+}
+
+// diagnostic: the correlation/peak tail of dd_noaa_sync_windows alone (sync_tail_stage).  hay: device f64 [nwin][n], the signal that is
+// searched; env: device f64 [nwin][n], the signal the post-sync mean is taken of; needle_host [n_needles][needle_len], piecewise constant;
+// needle_of_window_host [nwin] or NULL (needle 0).  Per window: peak = first index of the largest normalised correlation minus
+// needle_len / 2, height = that correlation, tsync = mean(env[peak + m .. peak + 2 m)) when peak + 2 m < n.  A window whose largest value does
+// not exceed the threshold of its two largest and two smallest, or whose correlation holds a NaN (a NaN sample, or a stretch of silence as
+// long as the needle: 0 / 0), comes back as (INT64_MIN, NaN, NaN); a found peak too close to the end has tsync = NaN alone.  Synchronises.
+extern "C" int dd_debug_sync_tail(const double* hay_dev, const double* env_dev, int64_t n, int nwin, const double* needle_host, int needle_len,
+                                  int n_needles, const int* needle_of_window_host, int64_t* peak_host, double* height_host, double* tsync_host,
+                                  void* stream) {
+    DD_REQUIRE(hay_dev && env_dev && needle_host && peak_host && height_host && tsync_host, "null buffer");
+    DD_REQUIRE(nwin >= 1 && needle_len >= 1 && needle_len <= n && n < ((int64_t)1 << 30), "nwin / needle_len / n");
+    DD_REQUIRE(n_needles >= 1 && n_needles <= DD_CS_MAXNEEDLES, "n_needles (1 or 2)");
+    if (needle_of_window_host)
+        for (int w = 0; w < nwin; ++w) DD_REQUIRE(needle_of_window_host[w] >= 0 && needle_of_window_host[w] < n_needles, "needle_of_window");
+    DDRuns2 R2;
+    if (!dd_runs_build(needle_host, needle_len, n_needles, &R2)) {
+        dd_set_error("dd_noaa_sync_windows: the needle has more than %d constant runs", DD_XCORR_MAX_RUNS);
+        return DD_ERR_INVALID;
+    }
+    hipStream_t s = dd_stream(stream);
+    std::lock_guard<std::mutex> lk(g_sync_mu);
+    DDDevBuf<double> PQ;
+    DDDevBuf<char> work, res;
+    DDDevBuf<int> group;
+    DD_HIP_CHECK(PQ.alloc(2 * (size_t)nwin * (size_t)(n + 1)));
+    DD_HIP_CHECK(work.alloc(sync_tail_work_bytes(n, nwin)));
+    DD_HIP_CHECK(res.alloc(24 * (size_t)nwin));
+    DD_HIP_CHECK(group.alloc((size_t)nwin));
+    int64_t* d_peak = (int64_t*)res.get();
+    double* d_height = (double*)(res.get() + 8 * (size_t)nwin);
+    double* d_tsync = (double*)(res.get() + 16 * (size_t)nwin);
+    std::vector<char> down(24 * (size_t)nwin);
+    hipError_t e0 = hipSuccess;
+    if (needle_of_window_host) e0 = hipMemcpyAsync(group.get(), needle_of_window_host, sizeof(int) * (size_t)nwin, hipMemcpyHostToDevice, s);
+    if (e0 == hipSuccess) {
+        sync_tail_stage(hay_dev, env_dev, n, nwin, needle_len, R2, needle_of_window_host ? group.get() : nullptr, PQ.get(), work.get(),
+                        d_peak, d_height, d_tsync, s);
+        e0 = hipGetLastError();
+    }
+    if (e0 == hipSuccess) e0 = hipMemcpyAsync(down.data(), res.get(), down.size(), hipMemcpyDeviceToHost, s);
+    const hipError_t e2 = hipStreamSynchronize(s);                            // (before the buffers are freed: every return is behind it)
+    if (e0 != hipSuccess || e2 != hipSuccess) {
+        dd_set_error("dd_debug_sync_tail: %s", hipGetErrorString(e0 != hipSuccess ? e0 : e2));
+        return DD_ERR_HIP;
+    }
+    memcpy(peak_host, down.data(), 8 * (size_t)nwin);
+    memcpy(height_host, down.data() + 8 * (size_t)nwin, 8 * (size_t)nwin);
+    memcpy(tsync_host, down.data() + 16 * (size_t)nwin, 8 * (size_t)nwin);
     return DD_OK;
 }
 
@@ -459,23 +586,12 @@ extern "C" int dd_noaa_sync_windows_multi(const void* iq, int iq_kind, const int
         if (rc != DD_OK) return rc;
         const double* hay = ENV;
         if (pre_ntaps) {
-            if (cos2) {
-                rc = dd_filtfilt_cos_launch(ENV, L2, F1, H, L2, L2, pre_ntaps, fit2, d_tab, b, s);
-                if (rc != DD_OK) return rc;
-            } else {
-                dd_filtfilt_launch<double>(ENV, L2, F1, H, L2, L2, pre_ntaps, d_taps2, b, s);
-            }
+            rc = sync_prefilter_stage(ENV, L2, b, pre_ntaps, cos2 ? &fit2 : nullptr, d_tab, d_taps2, F1, H, s);
+            if (rc != DD_OK) return rc;
             hay = H;
         }
-        double* P = (double*)W;                                            // prefix sums into the (now free) FFT buffer
-        double* Q = P + (size_t)b * (L2 + 1);
-        const int stiles = (int)((L2 + DD_SCAN_TILE - 1) / DD_SCAN_TILE), xtiles = (int)((L2 + DD_XC_TILE - 1) / DD_XC_TILE);
-        double2* spart = (double2*)F1;                                     // tile sums, then the per-tile peak records:
-        DDPk* ppart = (DDPk*)(F1 + 2 * (size_t)b * stiles);                // both in the pre-filter's (now free) work buffer
-        hipLaunchKernelGGL(k_scan_part, dim3(stiles, b), dim3(256), 0, s, hay, L2, stiles, spart);
-        hipLaunchKernelGGL(k_scan_final, dim3(stiles, b), dim3(256), 0, s, hay, L2, stiles, spart, P, Q);
-        hipLaunchKernelGGL(k_xcorr_runs_pk, dim3(8 * ((b + 7) / 8) * xtiles), dim3(256), 0, s, P, Q, L2, needle_len, R2, d_group ? d_group + w0 : nullptr, xtiles, b, ppart);
-        hipLaunchKernelGGL(k_sync_peak, dim3(b), dim3(256), 0, s, ppart, xtiles, ENV, L2, needle_len, d_peak + w0, d_height + w0, d_tsync + w0);
+        // prefix sums into the (now free) FFT buffer; tile sums and per-tile peak records into the pre-filter's (now free) work buffer
+        sync_tail_stage(hay, ENV, L2, b, needle_len, R2, d_group ? d_group + w0 : nullptr, (double*)W, F1, d_peak + w0, d_height + w0, d_tsync + w0, s);
         DD_LAUNCH_CHECK();
     }
     char* down = nullptr;                                                                        // the three result arrays, one copy (pinned)

@@ -4,6 +4,8 @@
 //   ext = odd_ext(x, edge = 3K); pass 1: y1[i] = sum_k b[k] ext[max(i-k, 0)], i in [0, N = n + 2 edge)
 //   (forward lfilter whose history is the pass's first sample, zi * x0); pass 2 is the same filter run
 //   over y1 backwards and cropped: out[m] = sum_k b[k] y1[min(m + edge + k, N-1)], m in [0, n).
+//   (With edge = 3K neither clamp reaches an output that is kept: out[m] reads y1[3K .. n + 4K - 2], and those read ext[2K + 1 ..].
+//   The kernels' clamps keep the staging of a tile inside the arrays; the values they substitute are never used.)
 //
 // Tiled form: a workgroup of 256 lanes produces 2048 consecutive outputs from an LDS image of the
 // 2048+K-1 inputs they touch.  A lane owns 8 consecutive outputs and walks the taps 8 at a time, so a
@@ -228,8 +230,10 @@ static inline void dd_filtfilt_front_launch(const DDFrontSrc& F, float2* y1, flo
 //     sum_k b[k] s[t + k] = sum_q a_q ( cos(w_q t) A_q[t] + sin(w_q t) B_q[t] ),     w_q = 2 pi q / (K-1),
 //     A_q[t] = sum_{j=t}^{t+K-1} s[j] cos(w_q j),   B_q[t] = the same with sin
 // (b is symmetric, so the forward pass -- taps running backwards over the window -- is the same expression).  The prefix
-// sums are LOCAL to a workgroup's window of 2048 + K - 1 staged samples (origin at the window start: magnitudes stay below
-// ~2500 x the signal, the differences carry ~1e-15 relative error), phases are table look-ups at j mod (K-1) (exact period),
+// sums are LOCAL to a workgroup's window of W = TILE + K - 1 <= 3072 staged samples (origin at the window start: magnitudes stay below
+// W x the signal -- ~2500 x for hamming(492) -- and a difference of K samples carries ~W / K roundings of its own size: against the
+// definition in long double 2.1e-15 of max|x| (sum|b|)^2 at K = 492 and 1.5e-14 at K = 64, the worst measured; DESIGN.md has the
+// table), phases are table look-ups at j mod (K-1) (exact period),
 // and both passes stage their samples exactly like k_filtfilt_tile.  Hamming(492) over 60 windows of 118 151 samples:
 // 2 x 150 us (7.1e9 multiply-adds, 60 % of the f64 vector peak) -> the passes become memory-bound.
 #include "dd_cosfit.h"

@@ -72,6 +72,20 @@ int  dd_debug_decimb_lds_check(int K, int M, int phi, int64_t* out);
 int  dd_debug_chain_select(const double* taps_host, int ntaps, int decim, int flags, int in_align_bytes, const char* selector_name, int* family);
 int  dd_debug_cos_fit(const double* taps_host, int K, double* a_out, int* Q_out);
 int  dd_debug_sync_envelope(const void* X_dev, int64_t L, int nwin, int route, double* env_dev, void* stream);
+/* dd_debug_sync_prefilter -- the envelope pre-filter stage of dd_noaa_sync_windows alone: x_dev f64 [nwin][n] (device) -> out_dev f64
+ *   [nwin][n] = filtfilt(taps, [1], x) per window (decode_noaa.py:677 -> filters.py:72-73).  route 0: the prefix-sum form for taps that are
+ *   a cosine series (DD_ERR_UNSUPPORTED when dd_debug_cos_fit refuses them), route 1: the tiled direct form on the same taps.
+ *   n <= 3 K: DD_ERR_INVALID with SciPy's padlen message, as the batch reports it.
+ * dd_debug_sync_tail -- the correlation / peak stage alone: hay_dev f64 [nwin][n] (device) is searched for needle
+ *   needle_of_window_host[w] (NULL: needle 0) of needle_host [n_needles][needle_len] (piecewise constant, at most 64 runs), env_dev
+ *   f64 [nwin][n] gives the post-sync mean (decode_noaa.py:671-673, :713-762 with two expected peaks).  peak = first index of the
+ *   largest correlation - needle_len / 2, height = that correlation, tsync = mean(env[peak + m .. peak + 2 m)) when peak + 2 m < n, else NaN.
+ *   A window whose maximum does not exceed the threshold, or whose correlation holds a NaN (a NaN sample; a silent stretch as long as
+ *   the needle, 0 / 0), is (INT64_MIN, NaN, NaN). */
+int  dd_debug_sync_prefilter(const double* x_dev, int64_t n, int nwin, const double* taps_host, int K, int route, double* out_dev, void* stream);
+int  dd_debug_sync_tail(const double* hay_dev, const double* env_dev, int64_t n, int nwin, const double* needle_host, int needle_len,
+                        int n_needles, const int* needle_of_window_host, int64_t* peak_host, double* height_host, double* tsync_host,
+                        void* stream);
 
 #ifdef __cplusplus
 }
