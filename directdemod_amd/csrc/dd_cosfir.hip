@@ -33,8 +33,11 @@
 // Edges and runs.  The row grid is laid by the alignment of `out` (row q covers samples [base + 1024 q, +1024), base in [s - 15, s], so
 // that every lane's 16 angles are one 64-byte line).  Rows come in runs of 8 dealt to the waves in turn (one moving window over the
 // stream; short chunks: one run per wave); a run starts from the last 256 samples of the row before it (c1_prime_light).  Rows that
-// touch the stream start, the chunk end or the carried state (history after the NCO, last FIR output: DDChainParams) load sample by
-// sample with exact phases and predicate their stores.  One launch per chunk.
+// touch the stream start, the chunk end or the carried state (history after the NCO, last FIR output: DDChainParams) take every sample
+// with its exact phase and predicate their stores; all their loads -- sample, history entry and phasor-table entry of each position, on
+// clamped indices -- go out before the first is waited for and are selected by position afterwards (c1_edge_samples: one memory round
+// trip per edge row instead of one per sample).  The next chunk's history is written the same way by the wave that owns the chunk's last
+// run, before its rows.  One launch per chunk.
 #include "dd_chain_kernels.h"
 #include "dd_cosfir.h"
 #include "dd_cosfit.h"
@@ -227,7 +230,58 @@ __device__ __forceinline__ v2f c1_row_phasor(const DDCos1kArgs& A, int64_t S, v2
     return c1_cmul(pr, ql);
 }
 
-// One row.  EDGE: sample-by-sample loads (history, chunk end), predicated stores, the carried FIR output.  emit: store the row's outputs.
+// dd_phasor with its table entry T = tbl[phase64 >> (64 - DD_NCO_TBITS)] loaded by the caller: the same arithmetic, bit for bit
+__device__ __forceinline__ float2 c1_phasor_with(uint64_t phase64, float2 T) {
+    const uint32_t lo = (uint32_t)(phase64 >> (64 - DD_NCO_TBITS - 32));
+    const float theta = (float)lo * (6.283185307179586f * 5.684341886080802e-14f);   // 2^-44
+    const float t2 = theta * theta;
+    const float c = fmaf(-0.5f, t2, 1.0f);
+    const float s = theta * fmaf(-0.16666667f, t2, 1.0f);
+    return make_float2(fmaf(T.x, c, T.y * s), fmaf(T.y, c, -T.x * s));
+}
+
+// Sample n = S + r of the chunk after the NCO as an edge sees it, for the COUNT positions r = r0 + STRIDE i (0 <= r < 1024) behind the
+// wave-uniform S: the carried history for -(K-1) <= n < 0, the sample itself for 0 <= n < L, zero elsewhere.  EVERY load is issued before
+// the first is waited for -- the sample on an index clamped into [0, L), the history on one clamped into [0, K-1), dd_phasor's table
+// entry (any phase indexes the table) -- and the value is selected afterwards: one memory round trip for the lot.  (Loaded under
+// `if (n < 0) .. else if (n < L)`, each value was a round trip of its own that the next one waited for.)  Where the chunk's ends lie
+// is wave-uniform, so a lane compares and clamps its 32-bit r against scalars.  The arithmetic per sample is what it was: the same
+// phase (mod 2^64), the same product.
+template <bool U8, bool NCO, int COUNT, int STRIDE>
+__device__ __forceinline__ void c1_edge_samples(const DDCos1kArgs& A, const int64_t S, const int r0, v2f (&xt)[COUNT]) {
+    auto lim = [](int64_t v, int lo, int hi) { return (int)(v < lo ? lo : (v > hi ? hi : v)); };
+    const int zs = lim(-S, 0, 1024);                                // n < 0          <=>  r < zs
+    const int hs = lim(-S - (C1_K - 1), 0, 1024);                   // n + K - 1 >= 0  <=>  r >= hs
+    const int ls = lim(A.L - S, 0, 1024);                           // n < L          <=>  r < ls
+    const int64_t c0 = S < 0 ? 0 : (S < A.L ? S : A.L - 1);         // sample index = c0 + min(max(r - a, 0), m) = n clamped into [0, L)
+    const int a = lim(c0 - S, -1024, 1024), m = lim(A.L - 1 - c0, 0, 1023);
+    const int t0 = lim(S + (C1_K - 1), -2048, 2048);                // history index = t0 + r clamped into [0, K - 1)
+    const int64_t abs_S = A.abs0 + S;
+    float2 x[COUNT], h[COUNT], w[COUNT];
+#pragma unroll
+    for (int i = 0; i < COUNT; ++i) {
+        const int r = r0 + STRIDE * i;
+        const unsigned d = (unsigned)min(max(r - a, 0), m), tc = (unsigned)min(max(t0 + r, 0), C1_K - 2);
+        if (U8) {
+            const uchar2 u = (reinterpret_cast<const uchar2*>(A.in) + c0)[d];
+            x[i] = make_float2((float)u.x - 127.5f, (float)u.y - 127.5f);
+        } else {
+            x[i] = (reinterpret_cast<const float2*>(A.in) + c0)[d];
+        }
+        h[i] = A.tail_in[tc];                                                    // (after the NCO already)
+        if (NCO) w[i] = A.nco_tbl[(uint32_t)(((uint64_t)(abs_S + r) * A.cyc) >> (64 - DD_NCO_TBITS))];
+    }
+    __builtin_amdgcn_sched_barrier(0);                               // (no use of a loaded value is scheduled among the loads)
+#pragma unroll
+    for (int i = 0; i < COUNT; ++i) {
+        const int r = r0 + STRIDE * i;
+        const float2 xn = NCO ? dd_cmul(x[i], c1_phasor_with((uint64_t)(abs_S + r) * A.cyc, w[i])) : x[i];
+        const bool hist = r >= hs && r < zs, smp = r >= zs && r < ls;
+        xt[i] = (v2f){hist ? h[i].x : (smp ? xn.x : 0.f), hist ? h[i].y : (smp ? xn.y : 0.f)};
+    }
+}
+
+// One row.  EDGE: clamped loads selected by position (history, chunk end), predicated stores, the carried FIR output.  emit: store the row's outputs.
 // CX: the output is the FIR output itself (commSignal.filter alone, comm.py:80-92) instead of the discriminator's angles.
 template <bool U8, bool NCO, bool EDGE, bool CX>
 __device__ __forceinline__ void c1_row(const DDCos1kArgs& A, const DDCos1kLane& lt, const int lane, char* const lds,
@@ -244,27 +298,12 @@ __device__ __forceinline__ void c1_row(const DDCos1kArgs& A, const DDCos1kLane& 
     // lane - 16's group: this row's for lanes 16.., the previous row's lanes 48.. for lanes 0..15
     const char* const old = lane < 16 ? lds + (C1_BUF_BYTES - cr.cur) + (48 + lane) * C1_GROUP_BYTES : cur + (lane - 16) * C1_GROUP_BYTES;
     v2f xt[16];
+    // (an edge row forms what it derives from the lane number row by row: as loop invariants, hoisted out of the run loop, those values
+    //  would hold registers all through the interior rows)
+    int el = lane;
+    if (EDGE) asm volatile("" : "+v"(el));
     if (EDGE) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-            const int64_t n = S + 16 * lane + i;
-            v2f v = (v2f){0.f, 0.f};
-            if (n < 0) {
-                const int64_t ti = n + (C1_K - 1);
-                if (ti >= 0) v = c1_v2(A.tail_in[ti]);                           // (after the NCO already)
-            } else if (n < A.L) {
-                float2 x;
-                if (U8) {
-                    const uchar2 u = reinterpret_cast<const uchar2*>(A.in)[n];
-                    x = make_float2((float)u.x - 127.5f, (float)u.y - 127.5f);
-                } else {
-                    x = reinterpret_cast<const float2*>(A.in)[n];
-                }
-                if (NCO) x = dd_cmul(x, dd_phasor((uint64_t)(A.abs0 + n) * A.cyc, A.nco_tbl));
-                v = c1_v2(x);
-            }
-            xt[i] = v;
-        }
+        c1_edge_samples<U8, NCO, 16, 1>(A, S, 16 * el, xt);
 #pragma unroll
         for (int t = 0; t < 8; ++t) *reinterpret_cast<v4f*>(own + 16 * t) = (v4f){xt[2 * t].x, xt[2 * t].y, xt[2 * t + 1].x, xt[2 * t + 1].y};
     } else {
@@ -433,7 +472,7 @@ __device__ __forceinline__ void c1_row(const DDCos1kArgs& A, const DDCos1kLane& 
         // the FIR output before the chunk's first sample is carried state (demod_fm.py:47-49); the chunk's last one becomes it
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            const int64_t n = S + 16 * lane + i;
+            const int64_t n = S + 16 * el + i;
             if (!CX && A.s == 0 && n == -1) y[i] = c1_v2(*A.lasty_in);
             if (n == A.L - 1 && A.lasty_out) *A.lasty_out = make_float2(A.a0 * y[i].x, A.a0 * y[i].y);
         }
@@ -445,7 +484,7 @@ __device__ __forceinline__ void c1_row(const DDCos1kArgs& A, const DDCos1kLane& 
             float2* const o = reinterpret_cast<float2*>(A.out);
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
-                const int64_t n = S + 16 * lane + i;
+                const int64_t n = S + 16 * el + i;
                 if (n >= 0 && n < A.L) o[n] = make_float2(a0 * y[i].x, a0 * y[i].y);
             }
             return;
@@ -517,10 +556,10 @@ __device__ __forceinline__ void c1_row(const DDCos1kArgs& A, const DDCos1kLane& 
         }
     }
     if (EDGE) {
-        float* const o = reinterpret_cast<float*>(A.out) + (S - A.s) + 16 * lane;
+        float* const o = reinterpret_cast<float*>(A.out) + (S - A.s) + 16 * el;
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            const int64_t n = S + 16 * lane + i;
+            const int64_t n = S + 16 * el + i;
             if (n >= A.s && n < A.L) o[i] = ang[i];
         }
         return;
@@ -671,6 +710,18 @@ __global__ void __launch_bounds__(64 * C1_WAVES, 2) k_chain_cos1k(const DDCos1kA
     if (NCO) ql = c1_v2(dd_phasor((uint64_t)(U8 ? 16 * lane : 2 * lane) * A.cyc, A.nco_tbl));
     const int R = A.run_rows;
     const int nruns = R > 0 ? (nrows + R - 1) / R : nwaves;
+    if (A.tail_out && gw == (nruns - 1) % nwaves) {
+        // The new carried history: the chunk's last K-1 samples after the NCO (older ones from the old history), written by the wave that
+        // owns the chunk's last run BEFORE its runs, four values per lane in one round trip -- at the end of that wave it was the last
+        // thing the launch did, with every other wave gone.  It reads `in` and `tail_in` and writes `tail_out` only, which nothing in this
+        // launch reads: dd_chain.hip hands out the OTHER buffer of the filter's pair (tail[parity ^ 1]; tail_in is tail[parity] or a
+        // constant history) and flips the parity after the launch.
+        v2f hv[4];
+        c1_edge_samples<U8, NCO, 4, 64>(A, A.L - (C1_K - 1), lane, hv);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (lane + 64 * j < C1_K - 1) A.tail_out[lane + 64 * j] = make_float2(hv[j].x, hv[j].y);
+    }
     for (int run = gw; run < nruns; run += nwaves) {
     const int q0 = R > 0 ? run * R : (int)(((int64_t)nrows * gw) / nwaves);
     const int q1 = R > 0 ? (q0 + R < nrows ? q0 + R : nrows) : (int)(((int64_t)nrows * (gw + 1)) / nwaves);
@@ -729,26 +780,6 @@ __global__ void __launch_bounds__(64 * C1_WAVES, 2) k_chain_cos1k(const DDCos1kA
     }
     for (int q = f1; q < q1; ++q)
         c1_row<U8, NCO, true, CX>(A, lt, lane, lds, (int64_t)A.base + (int64_t)C1_ROW * q, q >= q0, false, xa, xb, ql, cr);
-    if (q1 == nrows && A.tail_out) {
-        // the new carried history: the chunk's last K-1 samples after the NCO (older ones from the old history)
-        for (int i = lane; i < C1_K - 1; i += 64) {
-            const int64_t n = A.L - (C1_K - 1) + i;
-            float2 v;
-            if (n < 0) {
-                v = A.tail_in[n + (C1_K - 1)];
-            } else {
-                float2 x;
-                if (U8) {
-                    const uchar2 u = reinterpret_cast<const uchar2*>(A.in)[n];
-                    x = make_float2((float)u.x - 127.5f, (float)u.y - 127.5f);
-                } else {
-                    x = reinterpret_cast<const float2*>(A.in)[n];
-                }
-                v = NCO ? dd_cmul(x, dd_phasor((uint64_t)(A.abs0 + n) * A.cyc, A.nco_tbl)) : x;
-            }
-            A.tail_out[i] = v;
-        }
-    }
     }   // runs
 }
 
