@@ -182,6 +182,7 @@ SIGNATURES = {
     "dd_lrpt_viterbi": (_int, [_p, _i64, _p, _i64, _i64, _p, _p]),
     "dd_lrpt_finish": (_int, [_p, _i64, _p, _i64, _p, _p, _p]),
     "dd_lrpt_rs": (_int, [_p, _i64, _p, _p, _p]),
+    "dd_lrpt_jpeg": (_int, [_p, _p, _p, _p, _i64, _i64, _p, _p, _p]),
     "dd_funcube_mix_ramp": (_int, [_p, _p, _i64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _p, _p]),
     "dd_funcube_lowpass": (_int, [_p, _p, _i64, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, _p, _p]),
     "dd_funcube_walk": (_int, [_p, _i64, _i64, _p, C.POINTER(C.c_double), _i64, _p, _p, _p, _p, _p, _p, _p]),

@@ -91,6 +91,9 @@ extern "C" int dd_afsk_edges_f64(const double* binary_filter, int64_t n, int spb
 // Reed-Solomon (255,223) correction of the frame bodies
 #include "dd_lrpt_rs.h"
 
+// the image packets' JPEG-like payload: Huffman decoding, dequantisation, inverse transform
+#include "dd_lrpt_jpeg.h"
+
 // Funcube BPSK sync detection (decode_funcube.py:148-306)
 #include "dd_funcube.h"
 

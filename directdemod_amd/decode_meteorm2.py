@@ -3,7 +3,8 @@ Meteor-M2 QPSK sync detection -- the reference's decode_meteorm2 surface (decode
 module helpers `lim` / `limBin`, plus `getSymbols`, the PLL-corrected soft symbols (gardnerA after pllObj.loop), and beyond the
 reference `getFrames` / `frameInfo`: the LRPT channel frames decoded from those symbols (lrpt.py), and
 `getVCDUs` / `rsInfo` / `getPackets` / `packetInfo`: the frames after Reed-Solomon correction and the CCSDS source packets
-reassembled from them.
+reassembled from them, and `getImage` / `getChannel` / `imageInfo`: the picture decoded from the image
+packets among them.
 
 One decode pass, cached, feeds both properties.  Per chunk of the recording (the reference's chunker, no chunker handed to the
 signal, so the mixer phase restarts at 0 in every chunk): offsetFreq in the reference's float64 arithmetic (qpsk.mix: the package's
@@ -34,17 +35,61 @@ class decode_meteorm2(symbolsync.SyncDecoder):
     `frameInfo`: one lrpt.INFO record per frame.  Both come from the same cached walk, whether or not the 120-bit sync was seen.
     `getVCDUs`: uint8[n, 892], the frames' data bytes after Reed-Solomon correction, row-aligned with getFrames; `rsInfo`: one
     lrpt.RS_INFO record per frame; `getPackets`: the source packets as bytes, in order of completion; `packetInfo`: one
-    lrpt.PACKET_INFO record per packet."""
+    lrpt.PACKET_INFO record per packet.
+    `getImage`: uint8[H, 1568, 3], the picture decoded from the image packets of the three channels `apids` (keyword, in the
+    order in which they occupy a strip cycle of `period` packets); `getChannel(apid)`: one plane; `imageInfo`: one
+    lrpt.IMAGE_INFO record per image packet."""
     WALKER = qpsk.Walker
     STAGES = ("front_end",)
     SPACING = (0.11, 0.05)
 
-    def __init__(self, sigsrc, offset, bw=None, use_device_raw=True):
+    def __init__(self, sigsrc, offset, bw=None, use_device_raw=True, *, apids=lrpt.IMAGE_APIDS, period=lrpt.IMAGE_PERIOD):
         super().__init__(sigsrc, use_device_raw)
         self._bw = 70000 if bw is None else bw
         self._offset = offset
         self._frames = None
         self._rs = None
+        self._apids = tuple(int(a) for a in apids)
+        self._period = int(period)
+        if len(self._apids) != 3 or len(set(self._apids)) != 3 or self._period < 1:
+            raise ValueError("decode_meteorm2: three different channel APIDs and a period >= 1 expected")
+        self._image = None
+
+    @property
+    def getImage(self):
+        """The picture, uint8[H, 1568, 3]: the three channel planes in `apids` order, 8 rows per strip cycle, zero wherever no packet
+        was placed"""
+        return self._decode_image()[0]
+
+    def getChannel(self, apid):
+        """One channel's plane, uint8[H, 1568]"""
+        if apid not in self._apids:
+            raise ValueError("decode_meteorm2.getChannel: APID %r is none of %r" % (apid, self._apids))
+        return self._decode_image()[0][:, :, self._apids.index(apid)]
+
+    @property
+    def imageInfo(self):
+        """Per image packet (lrpt.IMAGE_INFO): packet (the row of packetInfo), apid, mcun (its first block in the strip), q, mcus
+        (blocks decoded, 14: all), strip (-1: not placed), and the on-board time day, ms, us"""
+        return self._decode_image()[1]
+
+    def _decode_image(self):
+        if self._image is not None:
+            return self._image
+        pkts = self._decode_rs()[2]
+        t0 = time.perf_counter()
+        took = {}
+
+        def decode(*args):
+            _hip.sync()
+            t1 = time.perf_counter()
+            mcus = lrpt.jpeg_decode(*args)
+            took["jpeg"] = took.get("jpeg", 0.0) + time.perf_counter() - t1
+            return mcus
+        self._image = lrpt.image(pkts, self._apids, self._period, decode=decode)
+        self.timings["lrpt_jpeg"] = took.get("jpeg", 0.0)
+        self.timings["lrpt_image_host"] = time.perf_counter() - t0 - self.timings["lrpt_jpeg"]
+        return self._image
 
     @property
     def getFrames(self):

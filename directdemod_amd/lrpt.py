@@ -11,6 +11,10 @@ Section 4.15 finishes the channel decoder: Reed-Solomon (255,223) correction of 
 (`reed_solomon`, dd_lrpt_rs.h) and, on the host, the VCDU / M_PDU layer and the reassembly of CCSDS source packets (`mpdu_header`,
 `packet_header`, `packets`).  Restatements: `gf_tables`, `rs_generator`, `rs_encode`, `rs_syndromes`, `rs_decode_np`, `interleave`,
 `deinterleave`, `rs_frames_np`.
+
+Section 4.16 reads the image packets: the JPEG-like payload's Huffman decoding, dequantisation and 8x8 inverse transform on the
+device (`jpeg_decode`, `image`; dd_lrpt_jpeg.h), the packets' image headers and their placement in the picture on the host
+(`image_header`, `place`).  Restatements: `huffman_tables`, `quantiser`, `jpeg_blocks_np`, `idct_np`, `image_np`.
 """
 import functools
 
@@ -516,3 +520,254 @@ def reed_solomon(bodies):
     check(lib().dd_lrpt_rs(dev.ptr, n, fixed.ptr, errors.ptr, None), "dd_lrpt_rs")
     return (fixed.view(0, n * BODY_BYTES).to_host().reshape(n, BODY_BYTES),
             errors.view(0, RS_DEPTH * n).to_host().reshape(n, RS_DEPTH))
+
+
+# ------------------------------------------------------------------ section 4.16 in NumPy: the image packets' JPEG-like payload
+DC_BITS = (0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0)
+DC_VALUES = bytes(range(12))
+AC_BITS = (0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 125)
+AC_VALUES = bytes.fromhex(
+    "01020300041105122131410613516107227114328191a1082342b1c11552d1f02433627282090a161718191a25262728292a3435363738393a43444546"
+    "4748494a535455565758595a636465666768696a737475767778797a838485868788898a92939495969798999aa2a3a4a5a6a7a8a9aab2b3b4b5b6b7b8"
+    "b9bac2c3c4c5c6c7c8c9cad2d3d4d5d6d7d8d9dae1e2e3e4e5e6e7e8e9eaf1f2f3f4f5f6f7f8f9fa")
+ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
+                   35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55,
+                   62, 63], dtype=np.int64)
+QUANT_STD = np.array([16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51,
+                      87, 80, 62, 18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101,
+                      72, 92, 95, 98, 112, 100, 103, 99], dtype=np.int64)
+IDCT_M = np.array([[2896, 2896, 2896, 2896, 2896, 2896, 2896, 2896],
+                   [4017, 3406, 2276, 799, -799, -2276, -3406, -4017],
+                   [3784, 1567, -1567, -3784, -3784, -1567, 1567, 3784],
+                   [3406, -799, -4017, -2276, 2276, 4017, 799, -3406],
+                   [2896, -2896, -2896, 2896, 2896, -2896, -2896, 2896],
+                   [2276, -4017, 799, 3406, -3406, -799, 4017, -2276],
+                   [1567, -3784, 3784, -1567, -1567, 3784, -3784, 1567],
+                   [799, -2276, 3406, -4017, 4017, -3406, 2276, -799]], dtype=np.int64)       # M[k][n] = round(8192 a_k cos((2n+1) k pi / 16))
+MCU_PER_PACKET, MCU_PER_STRIP, IMAGE_WIDTH = 14, 196, 1568
+IMAGE_HEADER_BYTES = 20                                   # a packet's entropy-coded data starts here
+IMAGE_APIDS, IMAGE_PERIOD = (64, 65, 66), 43
+IMAGE_INFO = np.dtype([("packet", np.int64), ("apid", np.int64), ("mcun", np.int64), ("q", np.int64), ("mcus", np.int64),
+                       ("strip", np.int64), ("day", np.int64), ("ms", np.int64), ("us", np.int64)])
+
+
+@functools.lru_cache(maxsize=None)
+def huffman_tables():
+    """{"dc", "ac"} -> {(length, code): value}: the canonical codes of the two luminance tables of T.81 Annex K -- within a length in
+    value order, the first code of length 1 is 0, then code = (code + count) << 1"""
+    out = {}
+    for name, bits, values in (("dc", DC_BITS, DC_VALUES), ("ac", AC_BITS, AC_VALUES)):
+        table, code, k = {}, 0, 0
+        for length in range(1, 17):
+            for _ in range(bits[length - 1]):
+                table[(length, code)] = values[k]
+                code += 1
+                k += 1
+            code <<= 1
+        out[name] = table
+    return out
+
+
+def quantiser(q):
+    """int64[64], row-major: the standard luminance table scaled for quality factor q (0..255)"""
+    q = int(q)
+    if 21 <= q <= 49:
+        return np.maximum(1, (100 * QUANT_STD + q) // (2 * q))
+    return np.maximum(1, (max(0, 200 - 2 * q) * QUANT_STD + 50) // 100)
+
+
+def extend(v, n):
+    """EXTEND of T.81: the n-bit field v as a signed value"""
+    return v if n == 0 or v >= (1 << (n - 1)) else v - (1 << n) + 1
+
+
+class _Bits:
+    """a packet's bits, MSB first; a read past the last byte raises EOFError: nothing is padded"""
+
+    def __init__(self, data):
+        self.bits = np.unpackbits(np.frombuffer(bytes(data), dtype=np.uint8)).tolist()
+        self.at = 0
+
+    def take(self, n):
+        if self.at + n > len(self.bits):
+            raise EOFError
+        v = 0
+        for b in self.bits[self.at:self.at + n]:
+            v = (v << 1) | b
+        self.at += n
+        return v
+
+    def symbol(self, table):
+        code = 0
+        for length in range(1, 17):
+            code = (code << 1) | self.take(1)
+            if (length, code) in table:
+                return table[(length, code)]
+        raise ValueError("no code matches within 16 bits")
+
+
+def jpeg_blocks_np(payload):
+    """A packet's entropy-coded bytes -> (coefficients int64[14, 64], row-major, not yet dequantised; mcus): the blocks decoded before
+    the first failure (a code that does not exist, a position past 63, a needed bit past the last byte).  Rows from mcus on are 0."""
+    tables = huffman_tables()
+    rd = _Bits(payload)
+    coef = np.zeros((MCU_PER_PACKET, 64), dtype=np.int64)
+    pred = 0
+    for m in range(MCU_PER_PACKET):
+        block = np.zeros(64, dtype=np.int64)
+        try:
+            n = rd.symbol(tables["dc"])
+            pred += extend(rd.take(n), n)
+            block[0] = pred
+            k = 1
+            while k < 64:
+                rs = rd.symbol(tables["ac"])
+                run, size = rs >> 4, rs & 15
+                if size == 0:
+                    if run == 0:
+                        break
+                    if run != 15:
+                        raise ValueError("size 0 with run %d" % run)
+                    k += 16
+                    if k > 63:
+                        raise ValueError("run of sixteen past 63")
+                    continue
+                k += run
+                if k > 63:
+                    raise ValueError("run past 63")
+                block[ZIGZAG[k]] = extend(rd.take(size), size)
+                k += 1
+        except (EOFError, ValueError):
+            return coef, m
+        coef[m] = block
+    return coef, MCU_PER_PACKET
+
+
+def idct_np(coef, table):
+    """coefficients int[..., 64] (row-major, u vertical) and a quantiser table int[64] -> pixels uint8[..., 8, 8]: dequantised and
+    clamped to -2048..2047, the column pass (+1024 >> 11), the row pass (+16384 >> 15), +128, clamped to 0..255"""
+    coef = np.asarray(coef, dtype=np.int64)
+    F = np.clip(coef * np.asarray(table, dtype=np.int64), -2048, 2047).reshape(coef.shape[:-1] + (8, 8))
+    t = (np.einsum("uy,...uv->...yv", IDCT_M, F) + 1024) >> 11
+    p = (np.einsum("...yv,vx->...yx", t, IDCT_M) + 16384) >> 15
+    return np.clip(p + 128, 0, 255).astype(np.uint8)
+
+
+def image_header(pkt, apids=IMAGE_APIDS):
+    """A source packet's image header as a dict (apid, count, day, ms, us, mcun, q), or None when it is not an image packet: its
+    APID is none of `apids`, it has no secondary header, it is shorter than 21 bytes, or mcun is no multiple of 14 up to 182"""
+    pkt = bytes(pkt)
+    if len(pkt) < IMAGE_HEADER_BYTES + 1:
+        return None
+    h = packet_header(pkt)
+    mcun = pkt[14]
+    if h["apid"] not in apids or not h["secondary"] or mcun % MCU_PER_PACKET or mcun > MCU_PER_STRIP - MCU_PER_PACKET:
+        return None
+    return dict(apid=h["apid"], count=h["count"], day=(pkt[6] << 8) | pkt[7], ms=int.from_bytes(pkt[8:12], "big"),
+                us=(pkt[12] << 8) | pkt[13], mcun=mcun, q=pkt[19])
+
+
+def place(heads, apids=IMAGE_APIDS, period=IMAGE_PERIOD):
+    """image headers (image_header's dicts, in getPackets order) -> int64[n]: each packet's strip, or -1 where it is not placed.
+    a = the sequence count unwrapped modulo 16384; base = a - mcun / 14 - 14 j for channel j; the first packet's base is the
+    origin; strip = (base - origin) / period where that divides and is >= 0; of two packets with one (channel, strip, mcun) the
+    later is placed."""
+    strips = np.full(len(heads), -1, dtype=np.int64)
+    a = prev = origin = None
+    owner = {}
+    for i, h in enumerate(heads):
+        a = h["count"] if a is None else a + (h["count"] - prev) % 16384
+        prev = h["count"]
+        j = tuple(apids).index(h["apid"])
+        base = a - h["mcun"] // MCU_PER_PACKET - MCU_PER_PACKET * j
+        if origin is None:
+            origin = base
+        if base < origin or (base - origin) % period:
+            continue
+        strips[i] = (base - origin) // period
+        key = (j, int(strips[i]), h["mcun"])
+        if key in owner:
+            strips[owner[key]] = -1
+        owner[key] = i
+    return strips
+
+
+def image_packets(packets, apids=IMAGE_APIDS):
+    """source packets -> (rows of the image packets among them, their image_header dicts)"""
+    rows, heads = [], []
+    for i, p in enumerate(packets):
+        h = image_header(p, apids)
+        if h is not None:
+            rows.append(i)
+            heads.append(h)
+    return rows, heads
+
+
+def _image_info(rows, heads, strips, mcus):
+    info = np.zeros(len(rows), dtype=IMAGE_INFO)
+    info["packet"], info["strip"], info["mcus"] = rows, strips, mcus
+    for k in ("apid", "mcun", "q", "day", "ms", "us"):
+        info[k] = [h[k] for h in heads]
+    return info
+
+
+def image_np(packets, apids=IMAGE_APIDS, period=IMAGE_PERIOD):
+    """source packets (bytes, in getPackets order) -> (image uint8[H, 1568, 3], info IMAGE_INFO[m]): every image packet decoded
+    (mcus), the placed ones' decoded blocks written into their channel's plane; zero wherever nothing was placed"""
+    rows, heads = image_packets(packets, apids)
+    strips = place(heads, apids, period)
+    height = 8 * (int(strips.max()) + 1) if len(strips) else 0
+    img = np.zeros((height, IMAGE_WIDTH, len(apids)), dtype=np.uint8)
+    mcus = np.zeros(len(rows), dtype=np.int64)
+    for i, (r, h) in enumerate(zip(rows, heads)):
+        coef, mcus[i] = jpeg_blocks_np(packets[r][IMAGE_HEADER_BYTES:])
+        if strips[i] < 0:
+            continue
+        pix = idct_np(coef[:mcus[i]], quantiser(h["q"]))
+        for m in range(int(mcus[i])):
+            x = 8 * (h["mcun"] + m)
+            img[8 * strips[i]:8 * strips[i] + 8, x:x + 8, tuple(apids).index(h["apid"])] = pix[m]
+    return img, _image_info(rows, heads, strips, mcus)
+
+
+# ------------------------------------------------------------------ device stage of section 4.16
+def jpeg_decode(payloads, q, dst, out, pitch):
+    """payloads (bytes each: the packets' entropy-coded data), q and dst per packet (dst: the byte offset in the device uint8 array
+    `out` of the packet's top-left pixel, -1: decode without writing), rows `pitch` bytes apart -> mcus int32[n] on the host"""
+    n = len(payloads)
+    offsets = np.zeros(n + 1, dtype=np.int64)
+    offsets[1:] = np.cumsum([len(p) for p in payloads])
+    q = np.ascontiguousarray(q, dtype=np.uint8)
+    dst = np.ascontiguousarray(dst, dtype=np.int64)
+    if len(q) != n or len(dst) != n:
+        raise ValueError("jpeg_decode: one q and one dst per packet")
+    lim = out.n - 7 * pitch - 8 * MCU_PER_PACKET
+    if n and (dst.max() > lim or dst.min() < -1):
+        raise ValueError("jpeg_decode: a packet's strip does not fit the output")
+    data = DevArray.from_host(np.frombuffer(b"".join(payloads) or b"\0", dtype=np.uint8))
+    mcus = DevArray(max(n, 1), np.int32)
+    check(lib().dd_lrpt_jpeg(data.ptr, offsets.ctypes.data, q.ctypes.data, dst.ctypes.data, n, pitch, out.ptr, mcus.ptr, None),
+          "dd_lrpt_jpeg")
+    return mcus.view(0, n).to_host()
+
+
+def image(packets, apids=IMAGE_APIDS, period=IMAGE_PERIOD, decode=jpeg_decode):
+    """image_np's result with the blocks decoded on the device: one dd_lrpt_jpeg call per channel plane, into a plane zeroed on the
+    device.  A packet that is not placed is decoded too, for its mcus, and writes nothing.  (`decode`: jpeg_decode, or the caller's
+    wrapper of it that keeps the time.)"""
+    rows, heads = image_packets(packets, apids)
+    strips = place(heads, apids, period)
+    height = 8 * (int(strips.max()) + 1) if len(strips) else 0
+    img = np.zeros((height, IMAGE_WIDTH, len(apids)), dtype=np.uint8)
+    mcus = np.zeros(len(rows), dtype=np.int64)
+    for j, apid in enumerate(apids):
+        mine = [i for i, h in enumerate(heads) if h["apid"] == apid]
+        if not mine:
+            continue
+        plane = DevArray(max(height * IMAGE_WIDTH, 1), np.uint8)
+        check(lib().dd_memset(plane.ptr, 0, plane.nbytes, None), "dd_memset")
+        dst = [8 * strips[i] * IMAGE_WIDTH + 8 * heads[i]["mcun"] if strips[i] >= 0 else -1 for i in mine]
+        mcus[mine] = decode([packets[rows[i]][IMAGE_HEADER_BYTES:] for i in mine], [heads[i]["q"] for i in mine], dst, plane,
+                                 IMAGE_WIDTH)
+        img[:, :, j] = plane.view(0, height * IMAGE_WIDTH).to_host().reshape(height, IMAGE_WIDTH)
+    return img, _image_info(rows, heads, strips, mcus)

@@ -476,7 +476,13 @@ int dd_meteor_maxcorr(const void* lim, int64_t lim_len, const int64_t* bufs_host
  * dd_lrpt_rs -- Reed-Solomon (255,223) correction (GF(256) modulo 0x187, roots (alpha^11)^j for
  *     j = 112..143, conventional basis, interleave depth 4) of the four codewords of each of nframes 1020-byte bodies:
  *     fixed[1020 i ..] = the body with every codeword that lies within 16 byte errors of a codeword replaced by it (parity
- *     included), the others as received; errors[4 i + w] = the bytes changed in codeword w (0..16), or -1 where it was left. */
+ *     included), the others as received; errors[4 i + w] = the bytes changed in codeword w (0..16), or -1 where it was left.
+ * dd_lrpt_jpeg -- the image packets' payload (the two luminance Huffman tables of T.81 Annex K, no byte
+ *     stuffing, 14 blocks per packet, the DC predictor 0 at the packet's start, the luminance quantiser scaled by q, an integer
+ *     8x8 inverse transform).  Packet i's entropy-coded bytes are data[offsets_host[i] .. offsets_host[i+1]) (an empty range is
+ *     allowed), q_host[i] its quality factor.  mcus[i] = the blocks decoded before the first failure (0..14, always written);
+ *     block m < mcus[i] goes to the 8x8 bytes at out[dst_host[i] + 8 m + y * pitch + x]; dst_host[i] = -1 decodes without
+ *     writing pixels.  pitch >= 112, offsets not decreasing, a packet below 2^27 bytes.  No byte past offsets_host[i+1] is read for packet i. */
 int dd_lrpt_soft(const void* sym, int64_t nsym, int8_t* soft, void* stream);
 int dd_lrpt_asm_search(const int8_t* soft, int64_t nsym, int min_score, int64_t cap, int64_t* cand, unsigned long long* count,
                        void* stream);
@@ -485,6 +491,8 @@ int dd_lrpt_viterbi(const int8_t* soft, int64_t nsym, const int64_t* spans_host,
 int dd_lrpt_finish(const uint8_t* bits_packed, const int8_t* soft, int64_t nsym, const int64_t* spans_host, int64_t nspans,
                    uint8_t* bodies, int32_t* info, void* stream);
 int dd_lrpt_rs(const uint8_t* bodies, int64_t nframes, uint8_t* fixed, int32_t* errors, void* stream);
+int dd_lrpt_jpeg(const uint8_t* data, const int64_t* offsets_host, const uint8_t* q_host, const int64_t* dst_host, int64_t npackets,
+                 int64_t pitch, uint8_t* out, int32_t* mcus, void* stream);
 
 /* ---- Funcube BPSK sync detection (decode_funcube.py:148-306) ------------------------------------------------------------
  * dd_funcube_mix_ramp -- dd_meteor_mix with the frequency formed per sample: th = ((w * f[k]) * k) * inv_fs, w = -2 pi,

@@ -11,8 +11,16 @@ warm (median of --reps, a fresh decoder object each time).  Prints one JSON line
 A tiled case (b) repeats its frames' counters: each tile delivers the same packets again, and whatever packet is under way at a seam
 is dropped there, by the counter's jump back or by the broken frame.  "packets" counts them all, "packets_distinct" the different ones.
 
-    python tools/bench_lrpt.py [--reps 3] [--duration 60] [--case a|b]
+--case c is the image layer (decode_meteorm2.getImage).  First dd_lrpt_jpeg alone, 4096 packets per call --
+flat strips, noise strips at q = 80, random bytes of 1..300 -- between device events, the median of 20 calls after 3 (the entry
+uploads its 3 n + 1 descriptor words and waits for the kernel, so the figure is the upload and the kernel; --kernel-only stops
+there, for a kernel trace taken in a run of its own), beside the NumPy restatement's time for the same packets on the host.  Then
+the stages of getImage on tests/_jpeg.py's case (c) tiled: a tile's sequence counts repeat, so from the second tile on the packets
+are decoded (mcus) and mostly not placed.
+
+    python tools/bench_lrpt.py [--reps 3] [--duration 60] [--case a|b|c] [--kernel-only]
 """
+import ctypes as C
 import argparse
 import json
 import os
@@ -29,17 +37,114 @@ import numpy as np  # noqa: E402
 def recording(dur, case="a"):
     import _lrpt
     import _rs
-    base = (_lrpt if case == "a" else _rs).case(case)[0]
+    if case == "c":
+        import _jpeg
+        base = _jpeg.case("c")[0]
+    else:
+        base = (_lrpt if case == "a" else _rs).case(case)[0]
     n = int(dur * _lrpt.FS)
     return np.tile(base, (-(-n // base.shape[0]), 1))[:n], _lrpt.FS
+
+
+def jpeg_kernel(npackets=4096, calls=20, warm=3):
+    """dd_lrpt_jpeg over npackets packets of three kinds -> {kind: {...}}: the entry between events, the restatement on the host"""
+    import _jpeg
+    from directdemod_amd import _hip, lrpt
+    rng = np.random.Generator(np.random.PCG64(41))
+    lib = _hip.lib()
+
+    def flat():
+        w, pred = _jpeg.Writer(), 0
+        for v in rng.integers(-60, 60, 14):
+            w.dc(int(v) - pred).eob()
+            pred = int(v)
+        return w.bytes()
+    kinds = {
+        "flat": (lambda: flat(), 80),
+        "noise_q80": (lambda: _jpeg.encode_strip(np.clip(128 + 40 * rng.standard_normal((8, 112)), 0, 255).astype(np.uint8), 80)[0], 80),
+        "random": (lambda: rng.integers(0, 256, int(rng.integers(1, 301)), dtype=np.uint8).tobytes(), 80),
+    }
+    ev = [C.c_void_p() for _ in range(2)]
+    for e in ev:
+        _hip.check(lib.dd_event_create(C.byref(e)), "event")
+    out = {}
+    for kind, (make, q) in kinds.items():
+        distinct = [make() for _ in range(256)]
+        payloads = [distinct[i % 256] for i in range(npackets)]
+        t0 = time.perf_counter()
+        want = np.zeros(256, dtype=np.int32)
+        for i, p in enumerate(distinct):
+            coef, want[i] = lrpt.jpeg_blocks_np(p)
+            lrpt.idct_np(coef[:want[i]], lrpt.quantiser(q))
+        host_ms = (time.perf_counter() - t0) * 1e3 * npackets / 256                    # 256 different packets, each npackets / 256 times
+        offsets = np.concatenate(([0], np.cumsum([len(p) for p in payloads]))).astype(np.int64)
+        data = _hip.DevArray.from_host(np.frombuffer(b"".join(payloads), dtype=np.uint8))
+        qs = np.full(npackets, q, dtype=np.uint8)
+        dst = (896 * np.arange(npackets)).astype(np.int64)
+        pix = _hip.DevArray(896 * npackets, np.uint8)
+        mcus = _hip.DevArray(npackets, np.int32)
+        ms, times = C.c_float(0), []
+        for i in range(warm + calls):
+            lib.dd_event_record(ev[0], None)
+            _hip.check(lib.dd_lrpt_jpeg(data.ptr, offsets.ctypes.data, qs.ctypes.data, dst.ctypes.data, npackets, 112, pix.ptr, mcus.ptr, None),
+                       "dd_lrpt_jpeg")
+            lib.dd_event_record(ev[1], None)
+            _hip.check(lib.dd_event_sync(ev[1]), "event sync")
+            _hip.check(lib.dd_event_elapsed_ms(ev[0], ev[1], C.byref(ms)), "elapsed")
+            if i >= warm:
+                times.append(ms.value)
+        assert np.array_equal(mcus.to_host(), np.tile(want, npackets // 256))
+        out[kind] = {"packets": npackets, "bytes": int(offsets[-1]), "blocks": int(want.sum()) * (npackets // 256),
+                     "entry_us_median": round(float(np.median(times)) * 1e3, 1), "entry_us_min": round(float(np.min(times)) * 1e3, 1),
+                     "restatement_host_ms": round(host_ms, 1)}
+    for e in ev:
+        lib.dd_event_destroy(e)
+    return out
+
+
+def main_image(a):
+    from directdemod_amd import _hip, decode_meteorm2, lrpt, source
+    _hip.require_gpu()
+    res = {"stage": "meteorm2.getImage", "case": "c", "device": _hip.device_name(), "dd_lrpt_jpeg": jpeg_kernel()}
+    if a.kernel_only:
+        print(json.dumps(res), flush=True)
+        return
+    raw, fs = recording(a.duration, "c")
+    src = source.IQarray(raw, fs)
+
+    def run():
+        o = decode_meteorm2.decode_meteorm2(src, 0, None)
+        pk = o.getPackets
+        _hip.sync()
+        t0 = time.perf_counter()
+        img = o.getImage
+        return o, img, time.perf_counter() - t0, pk
+    obj, img, first, pkts = run()
+    runs = [run() for _ in range(a.reps)]
+    assert all(np.array_equal(r[1], img) for r in runs)
+    info = obj.imageInfo
+    t0 = time.perf_counter()
+    want, _ = lrpt.image_np(pkts)
+    host = time.perf_counter() - t0
+    assert np.array_equal(want, img)
+    res.update({"duration_s": a.duration, "samples": int(raw.shape[0]), "frames": int(len(obj.getFrames)), "packets": len(pkts),
+                "image_packets": int(len(info)), "placed": int(np.sum(info["strip"] >= 0)), "whole": int(np.sum(info["mcus"] == 14)),
+                "image_shape": list(img.shape), "first_image_ms": round(first * 1e3, 3),
+                "warm_image_ms": round(float(np.median([r[2] for r in runs])) * 1e3, 3),
+                "warm_stage_ms": {k: round(float(np.median([r[0].timings[k] for r in runs])) * 1e3, 3) for k in runs[0][0].timings},
+                "image_np_host_ms": round(host * 1e3, 1)})
+    print(json.dumps(res), flush=True)
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--duration", type=float, default=60.0)
-    ap.add_argument("--case", choices=("a", "b"), default="a")
+    ap.add_argument("--case", choices=("a", "b", "c"), default="a")
+    ap.add_argument("--kernel-only", action="store_true", help="case c: stop after the dd_lrpt_jpeg calls")
     a = ap.parse_args()
+    if a.case == "c":
+        return main_image(a)
     from directdemod_amd import _hip, decode_meteorm2, source
     _hip.require_gpu()
     raw, fs = recording(a.duration, a.case)
