@@ -2,9 +2,11 @@
 // recording resident in HBM, and the per-row band argmax of find_shift (:92-95).  Included by dd_runtime.hip.
 //
 // dd_waterfall_u8 runs two kernels.  k_waterfall_fft: one workgroup of 256 threads per (row, segment of the row's windows); a
-// window's pairs are read once, widened in registers (I - 127, Q - 127) and written to LDS as complex f32 (8 B x window, 64 KB
+// window's pairs are read once, widened in registers (I - 127, Q - 127) and written to LDS as complex f64 (16 B x window, 128 KB
 // at 8192), transformed in place by radix-4 decimation-in-frequency passes (one radix-2 pass at the end when log2(window) is
-// odd: 8192 = 4^6 x 2), and |X| is added to per-thread accumulators in LDS-position order.  The output of an in-place DIF
+// odd: 8192 = 4^6 x 2), and |X|, rounded to f32, is added to per-thread f32 accumulators in LDS-position order.  The transform
+// is float64 like the reference's (np.fft.fft): a row of one window is the log of single bins, and a bin far below the
+// spectrum's rms keeps none of its digits through a float32 transform, whose error is 1e-7 of the rms.  The output of an in-place DIF
 // is digit reversed; the permutation is undone once per row, not per window, by k_waterfall_rows, which sums a row's segments
 // in segment order, applies fftshift and log(sum / window / every) in float64 and stores float32.  The split of a row's windows
 // into segments depends on the row length alone, every sum has one order, and nothing is accumulated with atomics.
@@ -37,19 +39,20 @@ __device__ __forceinline__ int dd_wf_pos_of_bin(int k, int n) {
     return p;
 }
 
-__device__ __forceinline__ float2 dd_wf_twiddle(int j, int len, int m) {      // exp(-2 pi i m j / len); m j / len is exact in f32
-    float sn, cs;
-    sincospif(2.0f * (float)(m * j) / (float)len, &sn, &cs);
-    return make_float2(cs, -sn);
+// exp(-2 pi i j / len): 2 j / len is exact, sincospi is good to an ulp of float64
+__device__ __forceinline__ double2 dd_wf_twiddle(int j, int len) {
+    double sn, cs;
+    sincospi(2.0 * (double)j / (double)len, &sn, &cs);
+    return make_double2(cs, -sn);
 }
 
-__device__ __forceinline__ float2 dd_wf_cmul(float2 a, float2 w) {
-    return make_float2(a.x * w.x - a.y * w.y, a.x * w.y + a.y * w.x);
+__device__ __forceinline__ double2 dd_wf_cmul(double2 a, double2 w) {
+    return make_double2(a.x * w.x - a.y * w.y, a.x * w.y + a.y * w.x);
 }
 
 template <bool ALIGN4>
 __global__ void __launch_bounds__(DD_WF_THREADS) k_waterfall_fft(const uint8_t* __restrict__ raw, DDWfGeom g, float* __restrict__ partial) {
-    extern __shared__ float2 wf_s[];
+    extern __shared__ double2 wf_s[];
     const int tid = threadIdx.x;
     const int n = g.n;
     const long long row = blockIdx.x / g.nseg;
@@ -65,17 +68,16 @@ __global__ void __launch_bounds__(DD_WF_THREADS) k_waterfall_fft(const uint8_t* 
         const uint8_t* src = raw + w * 2 * (long long)n;
         if (ALIGN4) {
             const uint32_t* s4 = reinterpret_cast<const uint32_t*>(src);
-            float4* d4 = reinterpret_cast<float4*>(wf_s);
             for (int v = tid; v < n / 2; v += DD_WF_THREADS) {
                 const uint32_t u = s4[v];
-                d4[v] = make_float4((float)(int)(u & 0xff) - 127.0f, (float)(int)((u >> 8) & 0xff) - 127.0f,
-                                    (float)(int)((u >> 16) & 0xff) - 127.0f, (float)(int)(u >> 24) - 127.0f);
+                wf_s[2 * v] = make_double2((double)(int)(u & 0xff) - 127.0, (double)(int)((u >> 8) & 0xff) - 127.0);
+                wf_s[2 * v + 1] = make_double2((double)(int)((u >> 16) & 0xff) - 127.0, (double)(int)(u >> 24) - 127.0);
             }
         } else {
             const uint16_t* s2 = reinterpret_cast<const uint16_t*>(src);
             for (int v = tid; v < n; v += DD_WF_THREADS) {
                 const uint32_t u = s2[v];
-                wf_s[v] = make_float2((float)(int)(u & 0xff) - 127.0f, (float)(int)(u >> 8) - 127.0f);
+                wf_s[v] = make_double2((double)(int)(u & 0xff) - 127.0, (double)(int)(u >> 8) - 127.0);
             }
         }
         __syncthreads();
@@ -85,22 +87,24 @@ __global__ void __launch_bounds__(DD_WF_THREADS) k_waterfall_fft(const uint8_t* 
             for (int b = tid; b < n / 4; b += DD_WF_THREADS) {
                 const int j = b & (q - 1);
                 const int base = ((b >> lq) << (lq + 2)) + j;
-                const float2 a0 = wf_s[base], a1 = wf_s[base + q], a2 = wf_s[base + 2 * q], a3 = wf_s[base + 3 * q];
-                const float2 t0 = make_float2(a0.x + a2.x, a0.y + a2.y), t1 = make_float2(a0.x - a2.x, a0.y - a2.y);
-                const float2 t2 = make_float2(a1.x + a3.x, a1.y + a3.y);
-                const float2 t3 = make_float2(a1.y - a3.y, -(a1.x - a3.x));           // -j (a1 - a3)
-                wf_s[base] = make_float2(t0.x + t2.x, t0.y + t2.y);
-                wf_s[base + q] = dd_wf_cmul(make_float2(t1.x + t3.x, t1.y + t3.y), dd_wf_twiddle(j, len, 1));
-                wf_s[base + 2 * q] = dd_wf_cmul(make_float2(t0.x - t2.x, t0.y - t2.y), dd_wf_twiddle(j, len, 2));
-                wf_s[base + 3 * q] = dd_wf_cmul(make_float2(t1.x - t3.x, t1.y - t3.y), dd_wf_twiddle(j, len, 3));
+                const double2 a0 = wf_s[base], a1 = wf_s[base + q], a2 = wf_s[base + 2 * q], a3 = wf_s[base + 3 * q];
+                const double2 t0 = make_double2(a0.x + a2.x, a0.y + a2.y), t1 = make_double2(a0.x - a2.x, a0.y - a2.y);
+                const double2 t2 = make_double2(a1.x + a3.x, a1.y + a3.y);
+                const double2 t3 = make_double2(a1.y - a3.y, -(a1.x - a3.x));          // -j (a1 - a3)
+                const double2 tw1 = dd_wf_twiddle(j, len);
+                const double2 tw2 = dd_wf_cmul(tw1, tw1), tw3 = dd_wf_cmul(tw2, tw1);
+                wf_s[base] = make_double2(t0.x + t2.x, t0.y + t2.y);
+                wf_s[base + q] = dd_wf_cmul(make_double2(t1.x + t3.x, t1.y + t3.y), tw1);
+                wf_s[base + 2 * q] = dd_wf_cmul(make_double2(t0.x - t2.x, t0.y - t2.y), tw2);
+                wf_s[base + 3 * q] = dd_wf_cmul(make_double2(t1.x - t3.x, t1.y - t3.y), tw3);
             }
             __syncthreads();
         }
         if (len == 2) {
             for (int b = tid; b < n / 2; b += DD_WF_THREADS) {
-                const float2 a0 = wf_s[2 * b], a1 = wf_s[2 * b + 1];
-                wf_s[2 * b] = make_float2(a0.x + a1.x, a0.y + a1.y);
-                wf_s[2 * b + 1] = make_float2(a0.x - a1.x, a0.y - a1.y);
+                const double2 a0 = wf_s[2 * b], a1 = wf_s[2 * b + 1];
+                wf_s[2 * b] = make_double2(a0.x + a1.x, a0.y + a1.y);
+                wf_s[2 * b + 1] = make_double2(a0.x - a1.x, a0.y - a1.y);
             }
             __syncthreads();
         }
@@ -108,8 +112,8 @@ __global__ void __launch_bounds__(DD_WF_THREADS) k_waterfall_fft(const uint8_t* 
         for (int e = 0; e < DD_WF_ACC; e++) {
             const int p = tid + e * DD_WF_THREADS;
             if (p < n) {
-                const float2 x = wf_s[p];
-                acc[e] += sqrtf(x.x * x.x + x.y * x.y);
+                const double2 x = wf_s[p];
+                acc[e] += (float)sqrt(x.x * x.x + x.y * x.y);
             }
         }
         __syncthreads();                                 // (the next window's samples overwrite the spectrum)
@@ -181,7 +185,15 @@ extern "C" int dd_waterfall_u8(const uint8_t* raw_iq, int64_t raw_bytes, int win
     if (src != DD_OK) return src;
     float* partial = reinterpret_cast<float*>(scr.ptr);
     const dim3 grid((unsigned)(rows * g.nseg)), block(DD_WF_THREADS);
-    const size_t lds = sizeof(float2) * (size_t)window;
+    const size_t lds = sizeof(double2) * (size_t)window;             // 128 KB at 8192: above the 64 KB a launch gets unasked
+    static DDOncePerDevice attr;
+    if (attr.need()) {
+        DD_HIP_CHECK(hipFuncSetAttribute((const void*)k_waterfall_fft<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         (int)(sizeof(double2) * DD_WF_MAXWIN)));
+        DD_HIP_CHECK(hipFuncSetAttribute((const void*)k_waterfall_fft<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         (int)(sizeof(double2) * DD_WF_MAXWIN)));
+        attr.mark();
+    }
     if (((uintptr_t)raw_iq & 3) == 0) hipLaunchKernelGGL(k_waterfall_fft<true>, grid, block, lds, s, raw_iq, g, partial);
     else hipLaunchKernelGGL(k_waterfall_fft<false>, grid, block, lds, s, raw_iq, g, partial);
     DD_LAUNCH_CHECK();
@@ -192,8 +204,15 @@ extern "C" int dd_waterfall_u8(const uint8_t* raw_iq, int64_t raw_bytes, int win
     return DD_OK;
 }
 
-// np.argmax over [band_start, band_stop) of each row: the first maximum.  One workgroup per row; a thread keeps the first
-// maximum of its strided columns, the 256 candidates are reduced pairwise with the lower index winning a tie.
+// np.argmax over [band_start, band_stop) of each row: the first maximum, and like np.argmax a NaN counts as larger than every
+// number, so the first NaN of the band wins.  One workgroup per row; a thread keeps the best of its strided columns, the 256
+// candidates are reduced pairwise in one fixed order, the lower index winning a tie (two NaNs tie).  A thread without a column
+// offers (-inf, 0x7fffffff), which loses every tie: thread 0 always has a column, so the result lies inside the band.
+__device__ __forceinline__ bool dd_argmax_better(float v, int c, float best, int idx) {
+    if (v != v) return best == best || c < idx;
+    return best == best && (v > best || (v == best && c < idx));
+}
+
 __global__ void __launch_bounds__(256) k_band_argmax_f32(const float* __restrict__ rows, int width, int band_start, int band_stop,
                                                          int32_t* __restrict__ out) {
     __shared__ float sv[256];
@@ -203,7 +222,7 @@ __global__ void __launch_bounds__(256) k_band_argmax_f32(const float* __restrict
     int idx = 0x7fffffff;
     for (int c = band_start + (int)threadIdx.x; c < band_stop; c += 256) {
         const float v = r[c];
-        if (v > best || (v == best && c < idx)) { best = v; idx = c; }
+        if (dd_argmax_better(v, c, best, idx)) { best = v; idx = c; }
     }
     sv[threadIdx.x] = best;
     si[threadIdx.x] = idx;
@@ -212,7 +231,7 @@ __global__ void __launch_bounds__(256) k_band_argmax_f32(const float* __restrict
         if ((int)threadIdx.x < h) {
             const float v = sv[threadIdx.x + h];
             const int c = si[threadIdx.x + h];
-            if (v > sv[threadIdx.x] || (v == sv[threadIdx.x] && c < si[threadIdx.x])) { sv[threadIdx.x] = v; si[threadIdx.x] = c; }
+            if (dd_argmax_better(v, c, sv[threadIdx.x], si[threadIdx.x])) { sv[threadIdx.x] = v; si[threadIdx.x] = c; }
         }
         __syncthreads();
     }

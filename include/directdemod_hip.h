@@ -131,7 +131,8 @@ int dd_nco_c64_ramp(const float* in_c64, float* out_c64, int64_t n, double start
 int dd_waterfall_u8(const uint8_t* raw_iq, int64_t raw_bytes, int window, double every, float* out_rows, int64_t max_rows,
                     int64_t* n_rows, void* stream);
 /* per row of a [rows x width] float32 array the index, relative to band_start, of the first maximum over columns
- * [band_start, band_stop): np.argmax of frequency_shift.py:95 (the row minimum subtracted at :94 does not move it) */
+ * [band_start, band_stop): np.argmax of frequency_shift.py:95 (the row minimum subtracted at :94 does not move it).
+ * Like np.argmax, the first NaN of the band wins; the result always lies in [0, band_stop - band_start). */
 int dd_band_argmax_f32(const float* rows_f32, int64_t rows, int width, int band_start, int band_stop, int32_t* out_idx,
                        void* stream);
 

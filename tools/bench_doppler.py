@@ -7,9 +7,9 @@ and the time of a plain NumPy statement of the same sums on the host (measured o
 
 dd_waterfall_u8 is timed as one interval (its two kernels run back to back inside the call), so its bounds cover both: on the
 HBM side the raw bytes read once, the per-segment partial sums written by the FFT kernel and read by the row pass, and the rows
-written, at the 8 TB/s peak; on the LDS side the FFT's traffic -- per window one 8 x window write on the way in, a read and a
-write of 8 x window per pass (six radix-4 passes and one radix-2 pass at 8192) and one read for the magnitudes -- at the LDS
-rates with every CU streaming (reads 150 TB/s as ds_read_b64, writes 51 TB/s).  Both are computed, not measured; the line
+written, at the 8 TB/s peak; on the LDS side the FFT's traffic -- per window one 16 x window write on the way in (complex float64), a read and a
+write of 16 x window per pass (six radix-4 passes and one radix-2 pass at 8192) and one read for the magnitudes -- at the LDS
+rates with every CU streaming (reads 150 TB/s, writes 51 TB/s).  Both are computed, not measured; the line
 gives both, names the larger and the share of it that the measured time reaches.  Prints one JSON line.
 
     python tools/bench_doppler.py [--reps 5] [--log2 27]
@@ -97,8 +97,8 @@ def main():
     n_win = n // window
     row_len = int(np.ceil(every))
     passes = (window.bit_length() - 1 + 1) // 2
-    lds_r = n_win * 8 * window * (passes + 1)
-    lds_w = n_win * 8 * window * (passes + 1)
+    lds_r = n_win * 16 * window * (passes + 1)
+    lds_w = n_win * 16 * window * (passes + 1)
     nseg = min(16, -(-row_len // 8))                                   # DD_WF_SEG_WINDOWS, DD_WF_MAX_SEGS
     hbm_bytes = 2 * n + 2 * rows * nseg * window * 4 + rows * window * 4
     hbm_ms = hbm_bytes / HBM_PEAK * 1e3
