@@ -81,6 +81,8 @@ SIGNATURES = {
     "dd_debug_seam": (_int, [_int, _int]),
     "dd_debug_fft1k_plan": (_int, [_i64, _int, _int, _int, _int, C.POINTER(_int)]),
     "dd_debug_cos1k_plan": (_int, [_i64, _int, _int, _int, C.POINTER(_int)]),
+    "dd_debug_cos1k_shape": (_int, [_int, _int]),
+    "dd_debug_cos1k_runs": (_int, [_int, _int, C.POINTER(_int)]),
     "dd_debug_decimw_plan": (_int, [_i64, _i64, _int, _int, _int, _int, C.POINTER(_i64)]),
     "dd_debug_decimb_lds_check": (_int, [_int, _int, _int, C.POINTER(_i64)]),
     "dd_debug_chain_select": (_int, [C.POINTER(C.c_double), _int, _int, _int, _int, C.c_char_p, C.POINTER(_int)]),

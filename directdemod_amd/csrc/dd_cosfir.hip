@@ -169,17 +169,53 @@ struct C1Carry {
 };
 
 #define C1_NO_PEND ((int64_t)-4611686018427387904LL)
+
+// The cache policy of a streaming access, as the `aux` word of the raw buffer builtins spells it (sc0 = 1, nt = 2, sc1 = 16).  Plain and
+// nt accesses go through a pointer (nt: __builtin_nontemporal_load / _store); the write-through flavours through a raw buffer access on
+// a resource over the row: its base is wave-uniform, the lane's offset 32-bit, and an access outside the row's bytes is dropped by the
+// range check.  Either form is one the compiler counts in vmcnt (an inline-assembly access is not: docs/history.md).
+enum { C1_PLAIN = 0, C1_NT = 2, C1_SC1 = 16, C1_SC0_SC1 = 17, C1_NT_SC1 = 18 };
+// One choice per access site and flavour, each measured (profiles/cos1k_memory_side.txt, sections 1, 2 and 4):
+//   loads   nt.  Plain or sc1 loads cost the memory side a fifth (6.60 -> 5.16 TB/s in the streaming microbenchmark at this kernel's shape).
+//   angles  sc1, write-through: the lines leave the XCD's L2 as they are written instead of piling up dirty behind the sample stream.
+//           Headline 0.1348 -> 0.1303 ms per launch against plain stores, builds alternating, 2^22 samples 14.1 -> 12.2 us; sc0 sc1 is
+//           the same within the spread, nt loses 9 % (0.143-0.148 ms).  The raw u8 flavours follow (0.1131 against 0.1141 ms, not slower).
+//   CX      nt, as before: 8 bytes written per 8 read; sc1 there is 0.2028-0.2040 against 0.2012-0.2029 ms, no gain.
+template <bool U8, bool CX> struct C1Policy {
+    static constexpr int loads = C1_NT;                    // c1_issue_loads: a row's samples
+    static constexpr int prime = C1_NT;                    // c1_prime_issue: the last 2 KB of the row before a run (the run before reads them too)
+    static constexpr int stores = CX ? C1_NT : C1_SC1;     // c1_cx_store / c1_flush_angles
+};
+typedef unsigned v4u __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ const char* c1_uniform(const char* p) {                 // a wave-uniform pointer, in scalar registers
+    const uint64_t a = reinterpret_cast<uint64_t>(p);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(a >> 32)), lo = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)a);
+    return reinterpret_cast<const char*>(((uint64_t)hi << 32) | lo);          // (the builtin returns int: unsigned before it widens)
+}
+// 16 bytes at byte `off` of the row of `row_bytes` bytes at the wave-uniform `row`
+template <int POL>
+__device__ __forceinline__ void c1_st16(char* row, unsigned row_bytes, unsigned off, v4f v) {
+    if (POL == C1_PLAIN) *reinterpret_cast<v4f*>(row + off) = v;
+    else if (POL == C1_NT) __builtin_nontemporal_store(v, reinterpret_cast<v4f*>(row + off));
+    else __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(v4u, v), __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(c1_uniform(row)), 0, row_bytes, 0x00020000), off, 0, POL);
+}
+template <int POL>
+__device__ __forceinline__ v4f c1_ld16(const char* row, unsigned row_bytes, unsigned off) {
+    if (POL == C1_PLAIN) return *reinterpret_cast<const v4f*>(row + off);
+    if (POL == C1_NT) return __builtin_nontemporal_load(reinterpret_cast<const v4f*>(row + off));
+    return __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(__builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(c1_uniform(row)), 0, row_bytes, 0x00020000), off, 0, POL));
+}
+
 // the angles of row S, left in the image at `img` by the row before: four 1 KB row-major stores
+template <int POL>
 __device__ __forceinline__ void c1_flush_angles(const DDCos1kArgs& A, const char* img, int64_t S, int lane) {
-    float* const o = reinterpret_cast<float*>(A.out) + (S - A.s) + 4 * lane;
+    char* const row = reinterpret_cast<char*>(reinterpret_cast<float*>(A.out) + (S - A.s));
     const int G = lane >> 2, sw = (G >> 1) & 3;          // (group 16 g + G: the 16 g part does not reach the swizzle bits)
     v4f v[4];
 #pragma unroll
     for (int g = 0; g < 4; ++g) v[g] = *reinterpret_cast<const v4f*>(img + 64 * (16 * g + G) + 16 * ((lane & 3) ^ sw));
 #pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        *reinterpret_cast<v4f*>(o + 256 * g) = v[g];            // (plain: 0.1514 ms against 0.1633 with the non-temporal hint, same call)
-    }
+    for (int g = 0; g < 4; ++g) c1_st16<POL>(row, 4 * C1_ROW, 16 * lane + 1024 * g, v[g]);
 }
 
 // CX: the 1024 FIR outputs of row S, left in the image at `img` (the padded layout of the sample image) by the row before: eight 16-byte
@@ -189,23 +225,24 @@ __device__ __forceinline__ void c1_cx_read(const char* img, int lane, v4f (&v)[8
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = *reinterpret_cast<const v4f*>(rd + 8 * j * C1_GROUP_BYTES);
 }
+template <int POL>
 __device__ __forceinline__ void c1_cx_store(const DDCos1kArgs& A, int64_t S, int lane, const v4f (&v)[8]) {
-    float2* const o = reinterpret_cast<float2*>(A.out) + S + 2 * lane;
+    char* const row = reinterpret_cast<char*>(reinterpret_cast<float2*>(A.out) + S);
 #pragma unroll
-    // (non-temporal: with 8 bytes written per 8 read the hint pays -- 0.195 against 0.210-0.216 ms in the same calls; the angles' stores, 4 per 8, lose by it)
-    for (int j = 0; j < 8; ++j) __builtin_nontemporal_store(v[j], reinterpret_cast<v4f*>(o + 128 * j));
+    // (non-temporal: with 8 bytes written per 8 read the hint pays -- 0.195 against 0.210-0.216 ms in the same calls)
+    for (int j = 0; j < 8; ++j) c1_st16<POL>(row, 8 * C1_ROW, 16 * lane + 1024 * j, v[j]);
 }
 
-template <bool U8>
+template <bool U8, int POL>
 __device__ __forceinline__ void c1_issue_loads(const DDCos1kArgs& A, int64_t S, int lane, v4f (&xin)[8]) {
     if (U8) {
-        const v4f* p = reinterpret_cast<const v4f*>(reinterpret_cast<const unsigned char*>(A.in) + 2 * (S + 16 * lane));
-        xin[0] = __builtin_nontemporal_load(p);
-        xin[1] = __builtin_nontemporal_load(p + 1);
+        const char* const row = reinterpret_cast<const char*>(A.in) + 2 * S;
+        xin[0] = c1_ld16<POL>(row, 2 * C1_ROW, 32 * lane);
+        xin[1] = c1_ld16<POL>(row, 2 * C1_ROW, 32 * lane + 16);
     } else {
-        const v4f* p = reinterpret_cast<const v4f*>(reinterpret_cast<const float2*>(A.in) + S + 2 * lane);
+        const char* const row = reinterpret_cast<const char*>(reinterpret_cast<const float2*>(A.in) + S);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) xin[j] = __builtin_nontemporal_load(p + 64 * j);
+        for (int j = 0; j < 8; ++j) xin[j] = c1_ld16<POL>(row, 8 * C1_ROW, 16 * lane + 1024 * j);
     }
 }
 
@@ -373,10 +410,11 @@ __device__ __forceinline__ void c1_row(const DDCos1kArgs& A, const DDCos1kLane& 
     }
     // the next row's samples fly during this row's arithmetic (requested ahead of every store of this row: vmcnt retires in order),
     // into the OTHER register set: the caller alternates the two, so that nothing is copied -- or waited for -- at the loop's back edge
-    if (prefetch_next) { c1_issue_loads<U8>(A, S + C1_ROW, lane, xnext); cr.prow = c1_row_phasor<NCO>(A, S + C1_ROW, ql); }
+    typedef C1Policy<U8, CX> Pol;
+    if (prefetch_next) { c1_issue_loads<U8, Pol::loads>(A, S + C1_ROW, lane, xnext); cr.prow = c1_row_phasor<NCO>(A, S + C1_ROW, ql); }
     // the angles of the row before leave now: their LDS round trip and their stores overlap this row's arithmetic
-    if (CX) { if (cx_pend != C1_NO_PEND) c1_cx_store(A, cx_pend, lane, pv); }
-    else if (cr.pend_S != C1_NO_PEND) { c1_flush_angles(A, lds + (C1_BUF_BYTES - cr.cur), cr.pend_S, lane); cr.pend_S = C1_NO_PEND; }
+    if (CX) { if (cx_pend != C1_NO_PEND) c1_cx_store<Pol::stores>(A, cx_pend, lane, pv); }
+    else if (cr.pend_S != C1_NO_PEND) { c1_flush_angles<Pol::stores>(A, lds + (C1_BUF_BYTES - cr.cur), cr.pend_S, lane); cr.pend_S = C1_NO_PEND; }
     if (!EDGE && !U8) {
 #pragma unroll
         for (int t = 0; t < 8; ++t) {
@@ -586,19 +624,19 @@ __device__ __forceinline__ void c1_row(const DDCos1kArgs& A, const DDCos1kLane& 
 // may start at lane 48), the row total, the windowed state and the FIR output at its last sample -- and that output is a0 R + a1 C of the
 // state itself: no second pass, no discriminator.  A quarter of a row's loads and a third of its instructions; lanes 0..47 work on zeros.
 // (Rows that touch the stream start or the carried state go through c1_row<EDGE> instead.)
-template <bool U8>
+template <bool U8, int POL>
 __device__ __forceinline__ void c1_prime_issue(const DDCos1kArgs& A, int64_t S, int lane, v4f (&xp)[2]) {
     xp[0] = xp[1] = (v4f){0.f, 0.f, 0.f, 0.f};
     if (U8) {
         if (lane >= 48) {
-            const v4f* p = reinterpret_cast<const v4f*>(reinterpret_cast<const unsigned char*>(A.in) + 2 * (S + 16 * lane));
-            xp[0] = __builtin_nontemporal_load(p);
-            xp[1] = __builtin_nontemporal_load(p + 1);
+            const char* const row = reinterpret_cast<const char*>(A.in) + 2 * S;
+            xp[0] = c1_ld16<POL>(row, 2 * C1_ROW, 32 * lane);
+            xp[1] = c1_ld16<POL>(row, 2 * C1_ROW, 32 * lane + 16);
         }
     } else {
-        const v4f* p = reinterpret_cast<const v4f*>(reinterpret_cast<const float2*>(A.in) + S + 2 * lane);
-        xp[0] = __builtin_nontemporal_load(p + 64 * 6);
-        xp[1] = __builtin_nontemporal_load(p + 64 * 7);
+        const char* const row = reinterpret_cast<const char*>(reinterpret_cast<const float2*>(A.in) + S);
+        xp[0] = c1_ld16<POL>(row, 8 * C1_ROW, 16 * lane + 1024 * 6);
+        xp[1] = c1_ld16<POL>(row, 8 * C1_ROW, 16 * lane + 1024 * 7);
     }
 }
 template <bool U8, bool NCO>
@@ -702,8 +740,9 @@ template <bool U8, bool NCO, bool CX>
 __global__ void __launch_bounds__(64 * C1_WAVES, 2) k_chain_cos1k(const DDCos1kArgs A) {
     extern __shared__ __attribute__((aligned(16))) char c1_smem[];
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int gw = blockIdx.x * C1_WAVES + wave;
+    typedef C1Policy<U8, CX> Pol;
     const int nrows = A.nrows, nwaves = A.nwaves;
+    const int gw = blockIdx.x * C1_WAVES + wave;
     char* const lds = c1_smem + wave * C1_WAVE_BYTES;
     const DDCos1kLane lt = A.lane_tab[lane];
     v2f ql = (v2f){1.f, 0.f};
@@ -757,13 +796,13 @@ __global__ void __launch_bounds__(64 * C1_WAVES, 2) k_chain_cos1k(const DDCos1kA
             // the row before the run is an interior row: its last 256 samples are all the run needs (c1_prime_light); the run's first row
             // is requested right behind them
             v4f xp[2];
-            c1_prime_issue<U8>(A, S0, lane, xp);
+            c1_prime_issue<U8, Pol::prime>(A, S0, lane, xp);
             ++f0;
-            c1_issue_loads<U8>(A, S0 + C1_ROW, lane, xa);
+            c1_issue_loads<U8, Pol::loads>(A, S0 + C1_ROW, lane, xa);
             c1_prime_light<U8, NCO>(A, lt, lane, lds, S0, xp, ql, cr);
             cr.prow = c1_row_phasor<NCO>(A, S0 + C1_ROW, ql);
         } else {
-            c1_issue_loads<U8>(A, S0, lane, xa);
+            c1_issue_loads<U8, Pol::loads>(A, S0, lane, xa);
             cr.prow = c1_row_phasor<NCO>(A, S0, ql);
         }
         // two rows per trip: the sample registers alternate (xa: even rows of the run, xb: odd ones)
@@ -774,8 +813,8 @@ __global__ void __launch_bounds__(64 * C1_WAVES, 2) k_chain_cos1k(const DDCos1kA
         }
     }
     if (cr.pend_S != C1_NO_PEND) {
-        if (CX) { v4f pv[8]; c1_cx_read(lds + cr.cur, lane, pv); c1_cx_store(A, cr.pend_S, lane, pv); }
-        else c1_flush_angles(A, lds + (C1_BUF_BYTES - cr.cur), cr.pend_S, lane);
+        if (CX) { v4f pv[8]; c1_cx_read(lds + cr.cur, lane, pv); c1_cx_store<Pol::stores>(A, cr.pend_S, lane, pv); }
+        else c1_flush_angles<Pol::stores>(A, lds + (C1_BUF_BYTES - cr.cur), cr.pend_S, lane);
         cr.pend_S = C1_NO_PEND;
     }
     for (int q = f1; q < q1; ++q)
@@ -842,6 +881,33 @@ extern "C" int dd_debug_cos1k_plan(int64_t L, int s, int out_align_elems, int nc
     return DD_OK;
 }
 
+// How long a run is (rows; 0: one run per wave).  Runs of 8 rows dealt to the waves in turn once every wave gets at least two of them: the
+// device then walks one moving window of nwaves x 64 KB instead of nwaves streams far apart (memory side alone 5.64 -> 6.05 TB/s, the kernel
+// 0.1455 -> 0.1417 ms in one call, profiles/r05_cos1k_memory_only.txt; a run start costs c1_prime_light: 2 KB read twice and a third of a row's
+// instructions).  Re-measured with the write-through angle stores (profiles/cos1k_memory_side.txt, section 3): runs of 12 and 16 rows and a
+// later start of the runs all lose.
+static int cos1k_run_rows(int nrows, int nwaves) { return nrows >= 16 * (int64_t)nwaves ? 8 : 0; }
+
+// dd_debug_cos1k_shape: a test door like dd_debug_select_kernel (dd_chain.hip), two words read by every launch; zeros = the plan's own choice
+static std::atomic<int> g_c1_force_nwaves{0}, g_c1_force_rows{0};
+extern "C" int dd_debug_cos1k_shape(int nwaves, int run_rows) {
+    DD_REQUIRE(nwaves >= 0 && nwaves <= 65536 && nwaves % C1_WAVES == 0 && run_rows >= 0 && run_rows <= 4096, "nwaves: 0 or a multiple of 4, run_rows >= 0");
+    g_c1_force_nwaves.store(nwaves, std::memory_order_relaxed);
+    g_c1_force_rows.store(run_rows, std::memory_order_relaxed);
+    return DD_OK;
+}
+// what a launch over `nrows` rows takes, from cos1k_plan's waves: workgroups, waves, run length -- the override's, where one is set
+static void cos1k_shape(int nrows, int* grid, int* nwaves, int* run_rows) {
+    const int fw = g_c1_force_nwaves.load(std::memory_order_relaxed), fr = g_c1_force_rows.load(std::memory_order_relaxed);
+    if (fw > 0) { *nwaves = fw; *grid = fw / C1_WAVES; }
+    *run_rows = fr > 0 ? fr : cos1k_run_rows(nrows, *nwaves);
+}
+extern "C" int dd_debug_cos1k_runs(int nrows, int nwaves, int* out) {
+    DD_REQUIRE(nrows >= 1 && nwaves >= C1_WAVES && nwaves % C1_WAVES == 0 && out, "arguments");
+    out[0] = nwaves / C1_WAVES; out[1] = nwaves;
+    cos1k_shape(nrows, &out[0], &out[1], &out[2]);
+    return DD_OK;
+}
 static const void* cos1k_kernel(bool u8, bool nco, bool cx) {
     static const void* const k[8] = {
         (const void*)k_chain_cos1k<false, false, false>, (const void*)k_chain_cos1k<true, false, false>,
@@ -876,10 +942,8 @@ int dd_cos1k_launch(void* stv, const DDChainParams& P, hipStream_t stream) {
     const int a16 = (int)((reinterpret_cast<uintptr_t>(P.out) >> (cx ? 3 : 2)) & 15);
     int grid;
     cos1k_plan(P.L, P.s, a16, dd_cu_count(), 2, &A.base, &A.nrows, &grid, &A.nwaves);
-    // runs of 8 rows dealt to the waves in turn once every wave gets at least two of them: the device then walks one moving window of
-    // nwaves x 64 KB instead of nwaves streams far apart (memory side alone 5.64 -> 6.05 TB/s, the kernel 0.1455 -> 0.1417 ms in one call,
-    // profiles/r05_cos1k_memory_only.txt; a run start costs c1_prime_light: 2 KB read twice and a third of a row's instructions)
-    A.run_rows = A.nrows >= 16 * A.nwaves ? 8 : 0;
+    // workgroups, waves and run length: the plan's and cos1k_run_rows', or what dd_debug_cos1k_shape forces
+    cos1k_shape(A.nrows, &grid, &A.nwaves, &A.run_rows);
     const bool u8 = (P.flags & DD_CHAIN_U8_INPUT) != 0;
     const dim3 g(grid), b(64 * C1_WAVES);
     void* kargs[1] = {&A};

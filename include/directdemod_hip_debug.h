@@ -42,6 +42,13 @@ int  dd_debug_fft1k_plan(int64_t L, int s, int out_align_elems, int ncu, int rou
 /* dd_debug_cos1k_plan -- the row grid of a k_chain_cos1k launch (same arguments): out[0..3] = base (first sample of row 0; row q covers
  *   samples [base + 1024 q, +1024)), rows, workgroups, waves (wave w takes rows [rows w / waves, rows (w + 1) / waves)). */
 int  dd_debug_cos1k_plan(int64_t L, int s, int out_align_elems, int ncu, int* out);
+/* dd_debug_cos1k_shape -- a test door, not a tuning knob: every later k_chain_cos1k launch of this process runs on `nwaves` waves (a
+ *   multiple of 4: nwaves / 4 workgroups; 0: the plan's own) with runs of `run_rows` rows dealt to the waves in turn (0: the launch
+ *   path's own rule), so that a chunk of a few dozen rows walks the run map that otherwise needs 2^25 samples.  0, 0 restores the default.
+ * dd_debug_cos1k_runs -- what a launch over `nrows` rows takes, given the plan's `nwaves`: out[0..2] = workgroups, waves, run length
+ *   (0: one run per wave, rows [rows w / waves, rows (w + 1) / waves)), the override included where one is set.  Host arithmetic. */
+int  dd_debug_cos1k_shape(int nwaves, int run_rows);
+int  dd_debug_cos1k_runs(int nrows, int nwaves, int* out);
 /* dd_debug_decimw_plan -- the row grid of a k_chain_decim_w / k_chain_decim_b launch over a chunk that starts at absolute sample abs0 with
  *   decimation phase off and keeps Ld samples: out[0..11] = R0 (absolute index of the first row: row R is the block of 2048 samples
  *   [2048 R, 2048 (R + 1))), rows, phi = (abs0 + off) mod M, samples kept in LDS in front of a block, start shift (0 / 1), taps per lane
