@@ -191,6 +191,10 @@ SIGNATURES = {
     "dd_funcube_lim": (_int, [_p, _i64, _i64, _p, _i64, _p, _p, _i64, _p]),
     "dd_funcube_minsync": (_int, [_p, _i64, _p, _p, _i64, _p, _p, _p]),
     "dd_funcube_maxcorr": (_int, [_p, _i64, _p, _i64, _p, C.c_int, _p, _i64, _p, _p]),
+    "dd_fc_diff": (_int, [_p, _i64, _p, _p]),
+    "dd_fc_sync_search": (_int, [_p, _i64, _int, _i64, _p, _p, _p]),
+    "dd_fc_viterbi": (_int, [_p, _i64, _p, _i64, _p, _p, _p]),
+    "dd_fc_rs": (_int, [_p, _i64, _p, _p, _p]),
     "dd_median_segments_f64": (_int, [_p, _pi64, _pi64, _int, _p, _p]),
     "dd_apt_lines_f64": (_int, [_p, _i64, _pi64, _pi64, _int, _pi64, C.c_uint64, _int, _p, _p, _p, _p]),
     "dd_apt_map_u8": (_int, [_p, _i64, _int, C.POINTER(C.c_double), _p, _p]),

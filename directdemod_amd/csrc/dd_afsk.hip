@@ -97,6 +97,9 @@ extern "C" int dd_afsk_edges_f64(const double* binary_filter, int64_t n, int spb
 // Funcube BPSK sync detection (decode_funcube.py:148-306)
 #include "dd_funcube.h"
 
+// Funcube telemetry frames: soft symbols to the AO-40 FEC block's 256 bytes
+#include "dd_funcube_frames.h"
+
 // dd_code_warmup (dd_runtime.hip): the runtime loads a translation unit's code object when one of its kernels is first named
 int dd_code_touch_afsk(void) {
     hipFuncAttributes a;

@@ -1,7 +1,7 @@
 """
 Funcube BPSK sync detection -- the reference's decode_funcube surface (decode_funcube.py): `useful`, `getSyncs` and the module
-helpers `lim` / `limBin`, plus `getSymbols`, the PLL-corrected soft symbols (gardnerA after pllObj.loop) a later telemetry decoder
-would read.
+helpers `lim` / `limBin`, plus `getSymbols`, the PLL-corrected soft symbols (gardnerA after pllObj.loop), and beyond the reference
+`getFrames` / `frameInfo`: the 256-byte telemetry frames decoded from those symbols (funcube_fec.py).
 
 One decode pass, cached, feeds every property.  Per chunk of the recording (the reference's chunker, no chunker handed to the
 signal, so the mixer phase restarts at 0 in every chunk): offsetFreq in the reference's float64 arithmetic (bpsk.mix; with
@@ -17,10 +17,11 @@ Deviations from the reference:
   - with exactly one MAXSYNC the reference raises ValueError (np.min of an empty np.diff); here getSyncs returns [] with useful 0.
 """
 import logging
+import time
 
 import numpy as np
 
-from . import bpsk, frequency_shift, symbolsync
+from . import _hip, bpsk, frequency_shift, funcube_fec, symbolsync
 from .bpsk import lim, limBin  # noqa: F401  (module-level helpers, as in the reference)
 
 
@@ -30,7 +31,10 @@ class decode_funcube(symbolsync.SyncDecoder):
     (source.read_device_raw).
     `useful`: 1 if two MAXSYNCs lie 4.98 s +- 0.2 s apart; `getSyncs`: np.int64 positions; `getSymbols`: at 12000 Hz.
     minsyncs: the MINSYNC ctr values; buffers: (intervals, maxBuffStart); ramps: with corrfreq, per chunk (chunk_offset,
-    frequency_shift.ramp, doppCorrect_current after it)."""
+    frequency_shift.ramp, doppCorrect_current after it).
+    `getFrames`: uint8[n, 256], the telemetry frames of the AO-40 FEC blocks found in the symbols, in stream order; `frameInfo`:
+    one funcube_fec.INFO record per frame.  Both are cached and come from the same cached walk as getSyncs, whether or not the
+    33-bit sync fired; their stages' times are timings["fc_soft"], ["fc_sync"], ["fc_viterbi"], ["fc_rs"]."""
     WALKER = bpsk.Walker
     STAGES = ("doppler", "mix", "lowpass")
     SPACING = (4.98, 0.2)
@@ -43,6 +47,52 @@ class decode_funcube(symbolsync.SyncDecoder):
         self._signal_freq = int(signal_freq)
         self._corrfreq = corrfreq
         self.ramps = []
+        self._frames = None
+
+    @property
+    def getFrames(self):
+        """The telemetry frames, uint8[n, 256], in stream order: each codeword's bytes corrected where Reed-Solomon decoded it, as
+        received where it did not (frameInfo's rs_errors, ok)"""
+        return self._decode_frames()[0]
+
+    @property
+    def frameInfo(self):
+        """Per frame (funcube_fec.INFO): symbol (the first symbol of the frame's first channel bit), sample (the walk's A sample of
+        that symbol), inverted, sync_score (of 65), sync_corr, corrected (channel bits the Viterbi decoder changed), rs_errors (bytes
+        changed in each of the two codewords, -1: not decodable), ok (both decoded), and sat_id, frame_type from byte 0
+        (meaningful when ok)"""
+        return self._decode_frames()[1]
+
+    def _decode_frames(self):
+        if self._frames is not None:
+            return self._frames
+        w = self.walker()
+        t0 = time.perf_counter()
+
+        def lap(name):
+            nonlocal t0
+            _hip.sync()
+            now = time.perf_counter()
+            self.timings["fc_" + name] = now - t0
+            t0 = now
+        D = funcube_fec.soft_bits(w.view("sym"))
+        lap("soft")
+        starts = funcube_fec.frame_starts(funcube_fec.sync_candidates(D))
+        lap("sync")
+        inv = (starts[:, 1] < 0).astype(np.int64)
+        blocks, corrected = funcube_fec.viterbi(D, np.stack((starts[:, 0], inv), axis=1))
+        lap("viterbi")
+        frames, errors = funcube_fec.reed_solomon(blocks)
+        lap("rs")
+        info = np.zeros(len(starts), dtype=funcube_fec.INFO)
+        info["symbol"] = starts[:, 0] + funcube_fec.SYMBOLS_PER_BIT
+        info["sample"] = [int(w.aidx.view(int(k), 1).to_host()[0]) for k in info["symbol"]]
+        info["inverted"], info["sync_corr"], info["sync_score"] = inv, starts[:, 1], starts[:, 2]
+        info["corrected"], info["rs_errors"] = corrected, errors
+        info["ok"] = np.all(errors >= 0, axis=1)
+        info["sat_id"], info["frame_type"] = frames[:, 0] >> 6, frames[:, 0] & 0x3F
+        self._frames = (frames, info)
+        return self._frames
 
     def _front_end(self, src, ck, lap):
         bf = bpsk.Lowpass(src.sampFreq, self._bw)

@@ -525,6 +525,26 @@ int dd_funcube_minsync(const void* sym, int64_t nsym, const uint8_t* sync_bits_h
 int dd_funcube_maxcorr(const int8_t* lim, int64_t lim_len, const int64_t* bufs_host, int64_t nbuf, const uint8_t* sync_bits_host,
                        int rep, int32_t* scratch, int64_t scratch_len, int64_t* out, void* stream);
 
+/* ---- Funcube telemetry frames (beyond the reference; DESIGN.md section 4.17 defines every stage) ----------------------------
+ * dd_fc_diff -- r[k] = soft[2k] (dd_lrpt_soft's pairs of the walk's nsym symbols), S[i] = r[i] + .. + r[i+9]; for i < nsym - 19,
+ *     with a = S[i+10], b = S[i]: D[i] = 0 when a or b is 0, else +-min(min(|a|, |b|) / 10, 127), + where the signs differ.
+ *     nsym < 20 writes nothing.
+ * dd_fc_sync_search -- for every position p <= m - 51991 of D[m]: C = sum over k < 65 of (2 V[k] - 1) D[p + 800 k], V the sync
+ *     vector; score = how many k have (D > 0), or (D < 0) when C < 0, equal to V[k]; every score >= min_score appends
+ *     cand[3c .. 3c+2] = (p, C, score), *count = the number of such p (entries past cap are dropped).  The order is not defined.
+ * dd_fc_viterbi -- per frame i (frames_host[2i], [2i+1] = position p, polarity inv in 0..1; 0 <= p <= m - 51991): the 5132 soft
+ *     code values +-D[p + 10 pos(j)] through the 80 x 65 interleaver, the terminated rate-1/2, K = 7 trellis of 2566 steps from
+ *     state 0 to state 0, blocks[320 i ..] = the first 2560 decoded bits packed MSB first XOR the CCSDS pseudo-noise sequence,
+ *     corrected[i] = how many of the 5132 hard bits differ from the re-encoded decoded bits.
+ * dd_fc_rs -- per block i: codeword c in 0..1 is blocks[320 i + c + 2 k], k < 160, decoded as dd_lrpt_rs's (255,223) code behind
+ *     95 zero bytes; frames[256 i + c + 2 k], k < 128, = its data bytes, corrected where it decoded and as received where not;
+ *     errors[2 i + c] = the bytes changed (0..16), or -1 (no codeword within 16 errors, or one with a non-zero byte among the 95). */
+int dd_fc_diff(const int8_t* soft, int64_t nsym, int8_t* D, void* stream);
+int dd_fc_sync_search(const int8_t* D, int64_t m, int min_score, int64_t cap, int64_t* cand, unsigned long long* count, void* stream);
+int dd_fc_viterbi(const int8_t* D, int64_t m, const int64_t* frames_host, int64_t nframes, uint8_t* blocks, int32_t* corrected,
+                  void* stream);
+int dd_fc_rs(const uint8_t* blocks, int64_t nframes, uint8_t* frames, int32_t* errors, void* stream);
+
 /* APT image extraction (decode_noaa.getImage / getColor).
  * dd_median_segments_f64 -- out[i] = np.median(src[off_host[i] : off_host[i] + len_host[i]]) for `count` segments (device out):
  *      numpy's semantics (odd: middle element, even: (a + b) / 2, empty or holding a NaN: NaN); segments of any length.
