@@ -84,7 +84,8 @@ SIGNATURES = {
     "dd_debug_cos1k_shape": (_int, [_int, _int]),
     "dd_debug_cos1k_runs": (_int, [_int, _int, C.POINTER(_int)]),
     "dd_debug_decimw_plan": (_int, [_i64, _i64, _int, _int, _int, _int, C.POINTER(_i64)]),
-    "dd_debug_decimb_lds_check": (_int, [_int, _int, _int, C.POINTER(_i64)]),
+    "dd_debug_decim_tile_plan": (_int, [_i64, _int, _int, _int, _int, _int, _int, _int, C.POINTER(_i64)]),
+    "dd_debug_decimb_lds_check":(_int, [_int, _int, _int, C.POINTER(_i64)]),
     "dd_debug_chain_select": (_int, [C.POINTER(C.c_double), _int, _int, _int, _int, C.c_char_p, C.POINTER(_int)]),
     "dd_debug_cos_fit": (_int, [C.POINTER(C.c_double), _int, C.POINTER(C.c_double), C.POINTER(_int)]),
     "dd_debug_sync_envelope": (_int, [_p, _i64, _int, _int, _p, _p]),

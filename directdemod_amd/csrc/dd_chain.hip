@@ -173,7 +173,7 @@ static int fir_usable(dd_fir* f) {
 
 extern "C" int dd_fir_create(dd_fir** h, const double* taps, int ntaps) {
     DD_REQUIRE(h && taps, "null argument");
-    DD_REQUIRE(ntaps >= 1 && ntaps <= 4096, "ntaps must be in [1, 4096]");
+    DD_REQUIRE(ntaps >= 1 && ntaps <= 8192, "ntaps must be in [1, 8192]");
     if (!dd_nco_table()) {
         dd_set_error("no usable GPU: the HIP path is mandatory (there is no CPU fallback)");
         return DD_ERR_NODEVICE;
@@ -333,10 +333,13 @@ static DDChainParams chain_params(const dd_fir* fir, const dd_fm* fm, const DDFu
 }
 
 // tiles of T FIR outputs over a chunk's kept samples (an FM tile recomputes the output before its first one)
+static int tile_count(int64_t Ld, int s, bool isfm, int T) {
+    const int nblocks = isfm ? (int)((Ld - s + (T - 2)) / (T - 1)) : (int)((Ld + T - 1) / T);
+    return nblocks < 1 ? 1 : nblocks;
+}
 static void tile_grid(DDChainParams& P, int T) {
     P.T = T;
-    P.nblocks = (P.flags & DD_CHAIN_FM) ? (int)((P.Ld - P.s + (P.T - 2)) / (P.T - 1)) : (int)((P.Ld + P.T - 1) / P.T);
-    if (P.nblocks < 1) P.nblocks = 1;
+    P.nblocks = tile_count(P.Ld, P.s, (P.flags & DD_CHAIN_FM) != 0, T);
 }
 
 static int launch_dense(DDChainParams& P, hipStream_t s, int* kernel_id) {
@@ -369,68 +372,109 @@ static int raise_decim_lds_limit() {
     return DD_OK;
 }
 
-// geometry of one chunk through the tile kernels (M > 1): tile size, tile count, LDS, and -- when the chunk has an
-// interior run worth a persistent grid -- that run [lo, hi) (P.skip_lo / skip_hi) and the workgroups a CU holds
+// geometry of one chunk through the tile kernels (M > 1): tile size, tile count, spans, LDS, and -- when the chunk has an
+// interior run worth a persistent grid -- that run [lo, hi).  Host arithmetic only (dd_debug_decim_tile_plan hands it out):
+//   T          FIR outputs per tile (an FM tile recomputes the output before its first one); S the samples a tile stages,
+//              S2 that span rounded up to whole load granules (sample pairs for complex64, octets for raw u8)
+//   [lo, hi)   the interior tiles: span S2 inside the chunk, all T outputs valid, not the chunk's last tile (that one
+//              writes the carried state), input on a load granule -- the tiles whose loads are unconditional
+//   lds, lds_p dynamic LDS of the edge kernel / of a launch with persistent workgroups
+struct DDDecimGeom {
+    int T, nblocks, S, S2, lo, hi;
+    bool persistent;
+    size_t lds, lds_p;
+};
+static int decim_geometry(int64_t L, int K, int M, int off, bool isfm, int s, bool u8in, unsigned in_align, DDDecimGeom& g) {
+    int T = (DD_DECIM_SPAN_MAX - K - (M - 1)) / M + 1;
+    if (T > DD_DECIM_THREADS) T = DD_DECIM_THREADS;
+    if (T < 2) T = 2;
+    const int64_t Ld = kept_count(L, off, M);
+    g.T = T;
+    g.nblocks = tile_count(Ld, s, isfm, T);
+    const int64_t S64 = (int64_t)(T - 1) * M + K + (M - 1);
+    const int64_t SP = S64 + 4;
+    const int64_t lds64 = (int64_t)sizeof(float2) * (SP + (S64 + 63) / 64 + 1 + DD_DECIM_THREADS) + (int64_t)sizeof(float) * ((K + 7) & ~7) + 16;
+    DD_REQUIRE(lds64 <= 160 * 1024, "filter/decimation too large for the decimating kernel's LDS tile");
+    const int S = (int)S64;
+    const size_t lds = (size_t)lds64;
+    g.S = S;
+    g.S2 = u8in ? ((S + 7) & ~7) : ((S + 1) & ~1);
+    g.lds = lds;
+    g.lds_p = lds;
+    g.persistent = false;
+    g.lo = g.hi = g.nblocks;
+    const int S2 = g.S2;
+    if (S2 <= DD_DECIM_SPAN_MAX && (in_align & (u8in ? 3 : 7)) == 0) {
+        const int64_t adv = isfm ? (T - 1) : T;                      // outputs a tile advances by
+        const int64_t pf0 = isfm ? (int64_t)s - 1 : 0;               // pfirst of tile 0
+        // ns(b) = off + (pf0 + b adv) M - (K-1) >= 0 ;  ns(b) + S2 <= L ;  pf0 + b adv >= 0 ;  pf0 + b adv + T <= Ld
+        int64_t lo = 0;
+        while (lo < g.nblocks && ((int64_t)off + (pf0 + lo * adv) * M - (K - 1) < 0 || pf0 + lo * adv < 0)) ++lo;
+        int64_t hi = g.nblocks - 1;                                  // exclusive bound candidates, walk down
+        while (hi > lo && ((int64_t)off + (pf0 + (hi - 1) * adv) * M - (K - 1) + S2 > L || pf0 + (hi - 1) * adv + T > Ld)) --hi;
+        if (hi - lo >= 64) {
+            g.lo = (int)lo;
+            g.hi = (int)hi;
+            g.persistent = true;
+            const size_t lds_p0 = sizeof(float2) * ((size_t)S2 + 4 + S2 / 64 + 2 + DD_DECIM_THREADS) + sizeof(float) * ((K + 7) & ~7) + 16;
+            g.lds_p = lds_p0 > lds ? lds_p0 : lds;                   // the edge workgroups of the same launch need `lds`
+        }
+    }
+    return DD_OK;
+}
+
+extern "C" int dd_debug_decim_tile_plan(int64_t L, int K, int M, int off, int fm, int has_last, int u8, int in_align_bytes, int64_t* out) {
+    DD_REQUIRE(out && L >= 0 && K >= 1 && M >= 2 && off >= 0 && off < M && in_align_bytes >= 0, "arguments");
+    DDDecimGeom g;
+    const int rc = decim_geometry(L, K, M, off, fm != 0, (fm && !has_last) ? 1 : 0, u8 != 0, (unsigned)in_align_bytes, g);
+    if (rc != DD_OK) return rc;
+    out[0] = g.T; out[1] = g.nblocks; out[2] = g.S; out[3] = g.S2; out[4] = g.persistent ? 1 : 0; out[5] = g.lo; out[6] = g.hi;
+    out[7] = (int64_t)g.lds; out[8] = (int64_t)g.lds_p;
+    return DD_OK;
+}
+
+// one chunk's plan: its geometry into the parameter block (P.T, P.nblocks, P.skip_lo / skip_hi), and what the device has to
+// be told and asked for it -- the dynamic-LDS limits, and how many persistent workgroups a CU holds
 struct DDDecimPlan {
     size_t lds, lds_p;
     bool persistent;
     int lo, hi, per_cu;
 };
 static int decim_plan(DDChainParams& P, DDDecimPlan& pl) {
-    const bool isfm = (P.flags & DD_CHAIN_FM) != 0;
-    int T = (DD_DECIM_SPAN_MAX - P.K - (P.M - 1)) / P.M + 1;
-    if (T > DD_DECIM_THREADS) T = DD_DECIM_THREADS;
-    if (T < 2) T = 2;
-    tile_grid(P, T);
-    const int S = (T - 1) * P.M + P.K + (P.M - 1);
-    const int SP = S + 4;
-    const size_t lds = sizeof(float2) * ((size_t)SP + (S + 63) / 64 + 1 + DD_DECIM_THREADS) + sizeof(float) * ((P.K + 7) & ~7) + 16;
-    DD_REQUIRE(lds <= 160 * 1024, "filter/decimation too large for the decimating kernel's LDS tile");
-    if (lds > 64 * 1024)
-        DD_HIP_CHECK(hipFuncSetAttribute((const void*)k_chain_decim, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    pl.lds = lds;
-    pl.lds_p = lds;
-    pl.persistent = false;
-    pl.per_cu = 1;
-    // interior tiles [b_lo, b_hi): span (rounded up to a sample pair) inside the chunk, all T outputs valid,
-    // complex64 input, not the chunk's last tile (that one writes the carried state)
-    P.skip_lo = P.skip_hi = P.nblocks;
-    pl.lo = pl.hi = P.nblocks;
     const bool u8in = (P.flags & DD_CHAIN_U8_INPUT) != 0;
-    const int S2 = u8in ? ((S + 7) & ~7) : ((S + 1) & ~1);
-    if (S2 <= DD_DECIM_SPAN_MAX && (reinterpret_cast<uintptr_t>(P.in) & (u8in ? 3 : 7)) == 0) {
-        const int64_t adv = isfm ? (P.T - 1) : P.T;                  // outputs a tile advances by
-        const int64_t pf0 = isfm ? (int64_t)P.s - 1 : 0;             // pfirst of tile 0
-        // ns(b) = off + (pf0 + b adv) M - (K-1) >= 0 ;  ns(b) + S2 <= L ;  pf0 + b adv >= 0 ;  pf0 + b adv + T <= Ld
-        int64_t lo = 0;
-        while (lo < P.nblocks && ((int64_t)P.off + (pf0 + lo * adv) * P.M - (P.K - 1) < 0 || pf0 + lo * adv < 0)) ++lo;
-        int64_t hi = P.nblocks - 1;                                  // exclusive bound candidates, walk down
-        while (hi > lo && ((int64_t)P.off + (pf0 + (hi - 1) * adv) * P.M - (P.K - 1) + S2 > P.L || pf0 + (hi - 1) * adv + P.T > P.Ld)) --hi;
-        if (hi - lo >= 64) {
-            P.skip_lo = (int)lo;
-            P.skip_hi = (int)hi;
-            pl.lo = (int)lo;
-            pl.hi = (int)hi;
-            pl.persistent = true;
-            const size_t lds_p0 = sizeof(float2) * ((size_t)S2 + 4 + S2 / 64 + 2 + DD_DECIM_THREADS) + sizeof(float) * ((P.K + 7) & ~7) + 16;
-            pl.lds_p = lds_p0 > lds ? lds_p0 : lds;                  // the edge workgroups of the same launch need `lds`
-            const int rc = raise_decim_lds_limit();
-            if (rc != DD_OK) return rc;
-            // every workgroup must be resident from the start (a persistent grid with queued workgroups
-            // runs in rounds): ask the runtime how many fit (LDS and registers)
-            static std::mutex occ_mu;
-            static size_t occ_lds[2] = {0, 0};          // the answer depends on (flavour, LDS size) only: asked once per change
-            static int occ_val[2] = {0, 0};
-            std::lock_guard<std::mutex> lk(occ_mu);
-            int per_cu = occ_val[u8in];
-            if (occ_lds[u8in] != pl.lds_p || per_cu < 1) {
-                if ((u8in ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_chain_decim_p<true>, DD_DECIM_THREADS, pl.lds_p)
-                          : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_chain_decim_p<false>, DD_DECIM_THREADS, pl.lds_p)) != hipSuccess || per_cu < 1) per_cu = 1;
-                occ_lds[u8in] = pl.lds_p;
-                occ_val[u8in] = per_cu;
-            }
-            pl.per_cu = per_cu;
+    DDDecimGeom g;
+    const int rc0 = decim_geometry(P.L, P.K, P.M, P.off, (P.flags & DD_CHAIN_FM) != 0, P.s, u8in,
+                                   (unsigned)(reinterpret_cast<uintptr_t>(P.in) & 15), g);
+    if (rc0 != DD_OK) return rc0;
+    P.T = g.T;
+    P.nblocks = g.nblocks;
+    P.skip_lo = g.lo;
+    P.skip_hi = g.hi;
+    pl.lds = g.lds;
+    pl.lds_p = g.lds_p;
+    pl.persistent = g.persistent;
+    pl.lo = g.lo;
+    pl.hi = g.hi;
+    pl.per_cu = 1;
+    if (g.lds > 64 * 1024)
+        DD_HIP_CHECK(hipFuncSetAttribute((const void*)k_chain_decim, hipFuncAttributeMaxDynamicSharedMemorySize, (int)g.lds));
+    if (g.persistent) {
+        const int rc = raise_decim_lds_limit();
+        if (rc != DD_OK) return rc;
+        // every workgroup must be resident from the start (a persistent grid with queued workgroups
+        // runs in rounds): ask the runtime how many fit (LDS and registers)
+        static std::mutex occ_mu;
+        static size_t occ_lds[2] = {0, 0};          // the answer depends on (flavour, LDS size) only: asked once per change
+        static int occ_val[2] = {0, 0};
+        std::lock_guard<std::mutex> lk(occ_mu);
+        int per_cu = occ_val[u8in];
+        if (occ_lds[u8in] != pl.lds_p || per_cu < 1) {
+            if ((u8in ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_chain_decim_p<true>, DD_DECIM_THREADS, pl.lds_p)
+                      : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_chain_decim_p<false>, DD_DECIM_THREADS, pl.lds_p)) != hipSuccess || per_cu < 1) per_cu = 1;
+            occ_lds[u8in] = pl.lds_p;
+            occ_val[u8in] = per_cu;
         }
+        pl.per_cu = per_cu;
     }
     return DD_OK;
 }

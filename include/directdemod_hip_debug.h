@@ -56,7 +56,15 @@ int  dd_debug_cos1k_runs(int nrows, int nwaves, int* out);
  *   k_chain_decim_w), partial sums per output ceil(K / M), first block sample of the second accumulator set, samples of the LDS image.
  *   DD_ERR_UNSUPPORTED when the kernels do not take (K, M). */
 int  dd_debug_decimw_plan(int64_t abs0, int64_t Ld, int K, int M, int off, int ncu, int64_t* out);
-/* dd_debug_decimb_lds_check -- k_chain_decim_b's LDS image for K taps, decimation M and stream phase phi (absolute index of the first kept
+/* dd_debug_decim_tile_plan -- the tile grid of a k_chain_decim / k_chain_decim_p / k_chain_decim_multi launch over a chunk of L samples
+ *   through K taps and decimation M >= 2 with decimation phase off (fm: FM output, has_last: an FM sample precedes the chunk; u8: raw u8
+ *   input; in_align_bytes: the input pointer's address modulo 16): out[0..8] = T (FIR outputs per tile), tiles, S (samples a tile stages),
+ *   S2 (S rounded up to whole 16-byte loads), persistent (1: the interior run goes to persistent workgroups, DD_KERNEL_DECIM_PERSISTENT;
+ *   0: every tile through k_chain_decim, DD_KERNEL_DECIM_TILES), lo, hi (the interior run [lo, hi): the tiles staged with unconditional
+ *   16-byte loads over the whole of S2; lo = hi = tiles when there is none), dynamic LDS bytes of k_chain_decim, and of the persistent
+ *   launch.  DD_ERR_INVALID where the launch refuses (a tile beyond 160 KB of LDS) and for arguments no launch takes. */
+int  dd_debug_decim_tile_plan(int64_t L, int K, int M, int off, int fm, int has_last, int u8, int in_align_bytes, int64_t* out);
+/* dd_debug_decimb_lds_check --k_chain_decim_b's LDS image for K taps, decimation M and stream phase phi (absolute index of the first kept
  *   sample mod M), evaluated on the host with the kernel's own address functions: a run starts from a row before it whose first kept
  *   sample sits at offset phi (staged in part, no halo; both ways of staging it) over a fresh image, and goes on row by row (halo of the
  *   row before, whole row, tail zeros) until every row phase of the stream has come.  The cells that the matrix steps of the blocks that

@@ -1262,14 +1262,19 @@ def test_nco_per_sample_frequency_array(dd):
         dd.comm.commSignal(fs, x).offsetFreq(f[:-1])
 
 
-@pytest.mark.parametrize("M,fm", [(34, True), (50, True), (34, False), (3, True)])
-def test_u8_ingest_long_chunks_persistent_path(dd, M, fm):
+@pytest.mark.parametrize("M,fm", [(34, True), (50, True), (34, False), (3, True), (68, True), (108, False), (3, False)])
+def test_u8_ingest_long_chunks_persistent_path(dd, M, fm, select_kernel):
     """raw u8 input long enough for the persistent decimating kernel's u8 flavour (>= 64 interior tiles),
-    two chunks with carried state, against the oracle on the widened samples"""
+    two chunks with carried state, against the oracle on the widened samples.  M = 34 / 50 belong to the row kernels under the default
+    selector: they run under "decimp"; odd M and M > 64 (the reference's /68 and /108) reach the tile kernels by default.  The first chunk
+    must be k_chain_decim_p<true>; the second starts on an odd sample, 2 bytes off the 4-byte boundary of the persistent kernel's loads,
+    so all of it goes through k_chain_decim."""
     import ctypes as C
     hip = dd.hip
     lib = hip.lib()
     fs = 2048000
+    if M in (34, 50):
+        select_kernel("decimp")
     L1, L2 = 64 * 6144 * 2 + 12345, 300001
     raw = O.synth_iq_fm(L1 + L2, fs, 41, f_carrier=30e3)
     d = hip.DevArray.from_host(raw.reshape(-1))
@@ -1279,12 +1284,13 @@ def test_u8_ingest_long_chunks_persistent_path(dd, M, fm):
                                   hip.DD_CHAIN_NCO | hip.DD_CHAIN_U8_INPUT | (hip.DD_CHAIN_FM if fm else 0)))
     outs = []
     pos = 0
-    for n in (L1, L2):
+    for n, kern in ((L1, hip.DD_KERNEL_DECIM_PERSISTENT), (L2, hip.DD_KERNEL_DECIM_TILES)):
         no = lib.dd_chain_out_count(h, n)
         o = hip.DevArray(max(1, no), np.float32 if fm else np.complex64)
         got = C.c_int64(0)
         hip.check(lib.dd_chain_process(h, d.ptr + 2 * pos, o.ptr, n, C.byref(got), None))
         assert got.value == no
+        assert lib.dd_chain_last_kernel(h) == kern, (n, lib.dd_chain_last_kernel(h))
         outs.append(o.to_host()[:no])
         pos += n
     lib.dd_chain_destroy(h)

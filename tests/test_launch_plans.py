@@ -205,6 +205,120 @@ def test_decimw_plan_refuses_what_the_kernel_does_not_take():
         assert _hip.lib().dd_debug_decimw_plan(0, 1000, K, M, 0, 256, out) == _hip.DD_ERR_UNSUPPORTED
 
 
+# ---- the tile family (k_chain_decim / k_chain_decim_p / k_chain_decim_multi): dd_debug_decim_tile_plan --------------------------------
+# The kernels' index formulas, restated from dd_chain_kernels.h / dd_chain_tile_kernels.h:
+#   dd_tile_pfirst(b) = s - 1 + b (T - 1) for FM (a tile recomputes the output before its first one), b T for complex output
+#   ns(b)             = off + pfirst(b) M - (K - 1): the chunk index of the first sample tile b stages; it stages S of them
+#   an edge tile (dd_decim_edge_tile) stores p = pfirst + t, t in [0, T) (FM: t in [1, T), p >= 0), where p < Ld
+#   an interior tile (dd_decim_tile) stores all of them without a test, after 16-byte loads over [ns, ns + S2) without a test
+_SPAN_MAX, _TILE_THREADS, _LDS_MAX = 6144, 256, 160 * 1024
+_TP_K = (1, 2, 7, 8, 9, 151, 255, 256, 257, 513, 514, 600, 6200)
+_TP_M = (2, 3, 7, 33, 65, 66, 68, 92, 108, 200, 3100, 4000, 6200)
+
+
+def _tile_plan(L, K, M, off, fm, has_last, u8, align):
+    out = (C.c_int64 * 9)()
+    rc = _hip.lib().dd_debug_decim_tile_plan(L, K, M, off, fm, has_last, u8, align, out)
+    if rc != 0:
+        return rc, None
+    return 0, dict(zip(("T", "nblocks", "S", "S2", "persistent", "lo", "hi", "lds", "lds_p"), list(out)))
+
+
+def _tile_T(K, M):
+    return min(_TILE_THREADS, max(2, int((_SPAN_MAX - K - (M - 1)) / M) + 1))          # (C division: towards zero)
+
+
+def _xcd_tile(bid, n):
+    """dd_xcd_tile: workgroup bid of n -> tile; XCD x = bid mod 8 owns n // 8 (+ 1 if x < n mod 8) consecutive tiles"""
+    q, r = n // 8, n % 8
+    x, i = bid % 8, bid // 8
+    return x * q + np.minimum(x, r) + i
+
+
+def _check_tile_plan(L, K, M, off, fm, has_last, u8, align):
+    """every property of one plan; returns (persistent, interior tiles)"""
+    T = _tile_T(K, M)
+    S = (T - 1) * M + K + M - 1
+    K8 = (K + 7) & ~7
+    need = ((8 * (S + 4 + (S + 63) // 64 + 1 + _TILE_THREADS) + 15) & ~15) + 4 * K8      # dd_decim_edge_tile: image, group phasors, outputs; taps
+    rc, p = _tile_plan(L, K, M, off, fm, has_last, u8, align)
+    what = (L, K, M, off, fm, has_last, u8, align, p)
+    if rc != 0:
+        assert rc == _hip.DD_ERR_INVALID and need + 16 > _LDS_MAX, what
+        return None
+    assert 2 <= p["T"] <= 256 and p["T"] == T and p["S"] == S, what
+    assert need <= p["lds"] <= need + 16 and p["lds"] <= _LDS_MAX, what
+    S2 = (S + 7) & ~7 if u8 else (S + 1) & ~1
+    assert p["S2"] == S2, what
+    s = 1 if fm and not has_last else 0
+    Ld = len(range(off, L, M))
+    nb, lo, hi = p["nblocks"], p["lo"], p["hi"]
+    assert nb >= 1 and 0 <= lo <= hi <= nb, what
+    b = np.arange(nb, dtype=np.int64)
+    pfirst = s - 1 + b * (T - 1) if fm else b * T
+    ns = off + pfirst * M - (K - 1)
+    # every kept output (complex: p in [0, Ld); FM: p in [s, Ld)) is written by exactly one tile
+    first = np.minimum(np.maximum(pfirst + 1, 0) if fm else pfirst, Ld)
+    last = np.minimum(pfirst + T, Ld)                                  # exclusive
+    assert np.all(first[1:] == last[:-1]) and first[0] == s and last[-1] == Ld or Ld - s <= 0, what
+    if Ld - s > 0:
+        assert np.all(last > first), what                              # (no idle tile either)
+    if Ld > 0:
+        # the chunk's last tile stages the chunk's last K - 1 samples (it writes the carried history) and holds output Ld - 1
+        assert pfirst[-1] <= Ld - 1 <= pfirst[-1] + T - 1 and ns[-1] <= L - (K - 1) and L - 1 <= ns[-1] + S - 1, what
+    # the tiles that may load without a test
+    aligned = align % (4 if u8 else 8) == 0
+    ok = (ns >= 0) & (ns + S2 <= L) & (pfirst >= 0) & (pfirst + T <= Ld) & (b != nb - 1) & (S2 <= _SPAN_MAX) & aligned
+    if lo < hi:
+        assert np.all(ok[lo:hi]), what
+        # (what the persistent kernels allocate: image of S2 + 4 samples, S2 / 64 + 2 group phasors, T outputs; taps)
+        need_p = ((8 * (S2 + 4 + S2 // 64 + 2 + _TILE_THREADS) + 15) & ~15) + 4 * K8
+        assert max(need_p, p["lds"]) <= p["lds_p"] <= max(need_p + 16, p["lds"]) and p["lds_p"] <= _LDS_MAX, what
+    assert bool(p["persistent"]) == (hi - lo >= 64), what
+    if p["persistent"]:
+        assert (lo == 0 or not ok[lo - 1]) and not ok[hi], what
+    else:
+        assert lo == hi == nb and p["lds_p"] == p["lds"], what
+    # ... and no run of 64 or more such tiles is left to the edge kernel
+    assert int(ok.sum()) == hi - lo if p["persistent"] else int(ok.sum()) < 64, what
+    # the edge workgroups' tile map: dd_xcd_tile over the tiles outside [lo, hi), then the skip of [lo, hi)
+    n_edge = nb - (hi - lo)
+    e = _xcd_tile(np.arange(n_edge, dtype=np.int64), n_edge)
+    e = np.where(e >= lo, e + (hi - lo), e)
+    assert np.array_equal(np.sort(e), np.concatenate([b[:lo], b[hi:]])), what
+    return bool(p["persistent"]), hi - lo
+
+
+@pytest.mark.parametrize("K", _TP_K)
+def test_decim_tile_plan_interior_run_stays_inside_the_chunk(K):
+    """dd_debug_decim_tile_plan: the geometry every launch of the tile family takes (decim_geometry of dd_chain.hip).  The interior run
+    [lo, hi) is staged by unconditional 16-byte loads over the whole rounded span and stored without a test: one tile too many at either
+    end is a read outside the caller's buffer or a store past the outputs.  Checked for every tile against the kernels' index formulas."""
+    seen_persistent = 0
+    for M in _TP_M:
+        T = _tile_T(K, M)
+        for off in sorted({0, 1, M - 1}):
+            for L in sorted({1, M, K - 1, K, 3001, 4096 + 5, 72 * T * M + 2 * K} - {0}):
+                for fm, has_last in ((0, 0), (0, 1), (1, 0), (1, 1)):
+                    for u8, align in ((0, 0), (0, 8), (0, 4), (0, 12), (1, 0), (1, 4), (1, 2), (1, 14)):
+                        r = _check_tile_plan(L, K, M, off, fm, has_last, u8, align)
+                        if r is not None and r[0]:
+                            seen_persistent += 1
+                            assert L == 72 * T * M + 2 * K and r[1] >= 64
+    assert seen_persistent > 0 or K == 6200             # (K = 6200: every span is beyond DD_DECIM_SPAN_MAX)
+
+
+def test_decim_tile_plan_refuses_what_no_launch_takes():
+    out = (C.c_int64 * 9)()
+    f = _hip.lib().dd_debug_decim_tile_plan
+    assert f(1000, 151, 108, 0, 1, 0, 0, 0, out) == 0
+    for args in ((-1, 151, 108, 0, 1, 0, 0, 0), (1000, 0, 108, 0, 1, 0, 0, 0), (1000, 151, 1, 0, 1, 0, 0, 0), (1000, 151, 108, 108, 1, 0, 0, 0),
+                 (1000, 151, 108, -1, 1, 0, 0, 0), (1000, 151, 108, 0, 1, 0, 0, -8),
+                 (100000, 6200, 6200, 0, 0, 0, 0, 0), (100000, 8000, 8000, 0, 1, 0, 1, 0)):             # (beyond 160 KB of LDS)
+        assert f(*args, out) == _hip.DD_ERR_INVALID, args
+    assert f(1000, 151, 108, 0, 1, 0, 0, 0, None) == _hip.DD_ERR_INVALID
+
+
 def test_a_variant_library_is_loaded_through_dd_lib_path_and_says_so(tmp_path):
     """measurement scripts no longer copy ablation builds over the product library; DD_LIB_PATH makes _hip load another build of
     the same C-ABI instead, with a line on stderr.  (Here: a copy of the product library under another name.)"""
