@@ -88,6 +88,9 @@ extern "C" int dd_afsk_edges_f64(const double* binary_filter, int64_t n, int spb
 // Meteor-M2 LRPT channel decoding: soft symbols to frame bodies
 #include "dd_lrpt.h"
 
+// the Meteor-M N2-x modes from soft symbols: NRZ-M, the 80 ksym/s interleaver and its marker
+#include "dd_lrpt_modes.h"
+
 // Reed-Solomon (255,223) correction of the frame bodies
 #include "dd_lrpt_rs.h"
 

@@ -218,6 +218,20 @@ static int dd_lrpt_with_spans(const int64_t* spans_host, int64_t nspans, const c
     return DD_OK;
 }
 
+// the pseudo-noise sequence's period as bytes (host): register all ones, output r[0], feedback r[0] ^ r[3] ^ r[5] ^ r[7]
+static DDLrptPn dd_lrpt_pn() {
+    DDLrptPn pn;
+    uint8_t r[8] = {1, 1, 1, 1, 1, 1, 1, 1};
+    memset(pn.b, 0, sizeof(pn.b));
+    for (int i = 0; i < 255 * 8; ++i) {
+        pn.b[i >> 3] |= (uint8_t)(r[0] << (7 - (i & 7)));
+        const uint8_t fb = r[0] ^ r[3] ^ r[5] ^ r[7];
+        for (int q = 0; q < 7; ++q) r[q] = r[q + 1];
+        r[7] = fb;
+    }
+    return pn;
+}
+
 extern "C" int dd_lrpt_soft(const void* sym, int64_t nsym, int8_t* soft, void* stream) {
     DD_REQUIRE(nsym >= 0, "dd_lrpt_soft: sizes");
     if (nsym == 0) return DD_OK;
@@ -262,15 +276,7 @@ extern "C" int dd_lrpt_finish(const uint8_t* bits_packed, const int8_t* soft, in
                "dd_lrpt_finish: null buffer");
     const int rc = dd_lrpt_check_spans(spans_host, nspans, DD_LRPT_FRAME, nsym, "dd_lrpt_finish");
     if (rc != DD_OK) return rc;
-    DDLrptPn pn;
-    uint8_t r[8] = {1, 1, 1, 1, 1, 1, 1, 1};
-    memset(pn.b, 0, sizeof(pn.b));
-    for (int i = 0; i < 255 * 8; ++i) {
-        pn.b[i >> 3] |= (uint8_t)(r[0] << (7 - (i & 7)));
-        const uint8_t fb = r[0] ^ r[3] ^ r[5] ^ r[7];
-        for (int q = 0; q < 7; ++q) r[q] = r[q + 1];
-        r[7] = fb;
-    }
+    const DDLrptPn pn = dd_lrpt_pn();
     return dd_lrpt_with_spans(spans_host, nspans, "dd_lrpt_finish", stream, [&](const int64_t* d) {
         hipLaunchKernelGGL(k_lrpt_finish, dim3((unsigned)nspans), dim3(256), 0, dd_stream(stream), bits_packed, (const char2*)soft, d, pn,
                            bodies, info);

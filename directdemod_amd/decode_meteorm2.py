@@ -18,15 +18,15 @@ Deviations from the reference:
   - with exactly one MAXSYNC the reference raises ValueError (np.min of an empty np.diff); here getSyncs returns [] with useful 0.
 """
 import logging
-import time
 
 import numpy as np
 
-from . import _hip, comm, filters, lrpt, qpsk, symbolsync
+from . import comm, filters, lrpt, qpsk, symbolsync
+from .decode_lrpt import LrptChain
 from .qpsk import lim, limBin  # noqa: F401  (module-level helpers, as in the reference)
 
 
-class decode_meteorm2(symbolsync.SyncDecoder):
+class decode_meteorm2(symbolsync.SyncDecoder, LrptChain):
     """Object to decode Meteor m2: decode_meteorm2(sigsrc, offset, bw) as in the reference (bw None -> 70000).
     use_device_raw: read the recording as raw u8 pairs resident on the device when the source offers it (source.read_device_raw).
     `useful`: 1 if two MAXSYNCs lie 0.11 s +- 0.05 s apart; `getSyncs`: np.float64 positions; `getSymbols`: at 72000 Hz.
@@ -38,7 +38,8 @@ class decode_meteorm2(symbolsync.SyncDecoder):
     lrpt.PACKET_INFO record per packet.
     `getImage`: uint8[H, 1568, 3], the picture decoded from the image packets of the three channels `apids` (keyword, in the
     order in which they occupy a strip cycle of `period` packets); `getChannel(apid)`: one plane; `imageInfo`: one
-    lrpt.IMAGE_INFO record per image packet."""
+    lrpt.IMAGE_INFO record per image packet.  The chain from the soft symbols on is decode_lrpt.LrptChain,
+    shared with decode_lrpt; `getSoft`: the walk's int8 soft pairs, what decode_lrpt reads."""
     WALKER = qpsk.Walker
     STAGES = ("front_end",)
     SPACING = (0.11, 0.05)
@@ -47,129 +48,21 @@ class decode_meteorm2(symbolsync.SyncDecoder):
         super().__init__(sigsrc, use_device_raw)
         self._bw = 70000 if bw is None else bw
         self._offset = offset
-        self._frames = None
-        self._rs = None
-        self._apids = tuple(int(a) for a in apids)
-        self._period = int(period)
-        if len(self._apids) != 3 or len(set(self._apids)) != 3 or self._period < 1:
-            raise ValueError("decode_meteorm2: three different channel APIDs and a period >= 1 expected")
-        self._image = None
+        self._init_chain(apids, period)
 
     @property
-    def getImage(self):
-        """The picture, uint8[H, 1568, 3]: the three channel planes in `apids` order, 8 rows per strip cycle, zero wherever no packet
-        was placed"""
-        return self._decode_image()[0]
+    def getSoft(self):
+        """The int8 soft pairs of the walk's symbols (lim(re / 2), lim(im / 2) per symbol) as a host array, int8[2 nsym]: what
+        decode_lrpt takes and lrpt.write_soft writes"""
+        return self._lrpt_soft()[0].to_host()
 
-    def getChannel(self, apid):
-        """One channel's plane, uint8[H, 1568]"""
-        if apid not in self._apids:
-            raise ValueError("decode_meteorm2.getChannel: APID %r is none of %r" % (apid, self._apids))
-        return self._decode_image()[0][:, :, self._apids.index(apid)]
+    def _lrpt_prepare(self):
+        self.walker()
 
-    @property
-    def imageInfo(self):
-        """Per image packet (lrpt.IMAGE_INFO): packet (the row of packetInfo), apid, mcun (its first block in the strip), q, mcus
-        (blocks decoded, 14: all), strip (-1: not placed), and the on-board time day, ms, us"""
-        return self._decode_image()[1]
-
-    def _decode_image(self):
-        if self._image is not None:
-            return self._image
-        pkts = self._decode_rs()[2]
-        t0 = time.perf_counter()
-        took = {}
-
-        def decode(*args):
-            _hip.sync()
-            t1 = time.perf_counter()
-            mcus = lrpt.jpeg_decode(*args)
-            took["jpeg"] = took.get("jpeg", 0.0) + time.perf_counter() - t1
-            return mcus
-        self._image = lrpt.image(pkts, self._apids, self._period, decode=decode)
-        self.timings["lrpt_jpeg"] = took.get("jpeg", 0.0)
-        self.timings["lrpt_image_host"] = time.perf_counter() - t0 - self.timings["lrpt_jpeg"]
-        return self._image
-
-    @property
-    def getFrames(self):
-        """The LRPT frame bodies, uint8[n, 1020], in stream order"""
-        return self._decode_frames()[0]
-
-    @property
-    def frameInfo(self):
-        """Per frame (lrpt.INFO): symbol (of the marker's first bit), sample (the walk's A sample of that symbol), hypothesis,
-        asm_score (of 52), asm_errors (of 32 decoded marker bits), corrected (channel bits the decoder changed), vcid, counter"""
-        return self._decode_frames()[1]
-
-    @property
-    def getVCDUs(self):
-        """The frames' 892 data bytes, uint8[n, 892], row-aligned with getFrames: corrected where the codeword was decodable, as
-        received where it was not"""
-        return self._decode_rs()[0]
-
-    @property
-    def rsInfo(self):
-        """Per frame (lrpt.RS_INFO): errors (bytes changed in each of the four codewords, -1: not decodable), ok (all four decoded),
-        and vcid, counter from the corrected header (meaningful when ok)"""
-        return self._decode_rs()[1]
-
-    @property
-    def getPackets(self):
-        """The CCSDS source packets (bytes, header included) reassembled from the ok frames, in order of completion"""
-        return self._decode_rs()[2]
-
-    @property
-    def packetInfo(self):
-        """Per packet (lrpt.PACKET_INFO): apid, flags, count, vcid, frame (the row of getFrames in which its first byte lies), length"""
-        return self._decode_rs()[3]
-
-    def _decode_rs(self):
-        if self._rs is not None:
-            return self._rs
-        bodies = self._decode_frames()[0]
-        t0 = time.perf_counter()
-        fixed, errors = lrpt.reed_solomon(bodies)
-        info = np.zeros(len(bodies), dtype=lrpt.RS_INFO)
-        info["errors"] = errors
-        info["ok"] = np.all(errors >= 0, axis=1)
-        info["vcid"] = fixed[:, 1] & 0x3F
-        info["counter"] = (fixed[:, 2].astype(np.int64) << 16) | (fixed[:, 3].astype(np.int64) << 8) | fixed[:, 4]
-        vcdus = np.ascontiguousarray(fixed[:, :lrpt.VCDU_BYTES])
-        t1 = time.perf_counter()
-        pkts, pinfo = lrpt.packets(vcdus, info["ok"], info["vcid"], info["counter"])
-        self.timings["lrpt_rs"] = t1 - t0
-        self.timings["lrpt_packets"] = time.perf_counter() - t1
-        self._rs = (vcdus, info, pkts, pinfo)
-        return self._rs
-
-    def _decode_frames(self):
-        if self._frames is not None:
-            return self._frames
+    def _lrpt_soft(self):
         w = self.walker()
-        t0 = time.perf_counter()
-
-        def lap(name):
-            nonlocal t0
-            _hip.sync()
-            now = time.perf_counter()
-            self.timings["lrpt_" + name] = now - t0
-            t0 = now
-        soft = lrpt.soft_symbols(w.view("sym"))
-        lap("soft")
-        starts = lrpt.frame_starts(lrpt.asm_candidates(soft, w.nsym), w.nsym)
-        lap("asm")
-        bits = lrpt.viterbi(soft, w.nsym, starts[:, :2])
-        lap("viterbi")
-        bodies, fin = lrpt.finish(bits, soft, w.nsym, starts[:, :2])
-        info = np.zeros(len(starts), dtype=lrpt.INFO)
-        info["symbol"], info["hypothesis"], info["asm_score"] = starts[:, 0], starts[:, 1], starts[:, 2]
-        info["asm_errors"], info["corrected"], info["vcid"] = fin[:, 0], fin[:, 1], fin[:, 2]
-        info["sample"] = [int(w.aidx.view(int(k), 1).to_host()[0]) for k in starts[:, 0]]
-        info["counter"] = [lrpt.vcdu_header(b)["counter"] for b in bodies]
-        lap("finish")
-        self._frames = (bodies, info)
-        return self._frames
+        return (lrpt.soft_symbols(w.view("sym")), w.nsym,
+                lambda symbols: np.array([int(w.aidx.view(int(k), 1).to_host()[0]) for k in symbols], dtype=np.int64))
 
     def _front_end(self, src, ck, lap):
         bf = filters.butter(src.sampFreq, self._bw)

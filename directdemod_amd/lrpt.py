@@ -15,7 +15,14 @@ Section 4.15 finishes the channel decoder: Reed-Solomon (255,223) correction of 
 Section 4.16 reads the image packets: the JPEG-like payload's Huffman decoding, dequantisation and 8x8 inverse transform on the
 device (`jpeg_decode`, `image`; dd_lrpt_jpeg.h), the packets' image headers and their placement in the picture on the host
 (`image_header`, `place`).  Restatements: `huffman_tables`, `quantiser`, `jpeg_blocks_np`, `idct_np`, `image_np`.
+
+Section 4.18 is the modes of the Meteor-M N2-x satellites, from soft symbols: differential (NRZ-M) coding -- the marker search with
+another template (`asm_candidates(template=ASM_ENCODED_NRZM)`) and `finish(nrzm=True)` -- and the 80 ksym/s mode's convolutional
+interleaver behind its 8-bit marker: `deint_scores`, `deint_lock` (host), `deint` (dd_lrpt_modes.h); the soft-symbol file
+(`read_soft`, `write_soft`).  Restatements: `nrzm_encode`, `nrzm_decode`, `finish_nrzm_np`, `interleave_np`, `deinterleave_np`,
+`add_markers_np`, `deint_scores_np`, `deint_np`.  decode_lrpt.py runs the whole chain on such a stream.
 """
+import ctypes
 import functools
 
 import numpy as np
@@ -91,19 +98,19 @@ def soft_np(sym):
     return out.astype(np.int8)
 
 
-def _asm_code_bits():
-    return np.array([(ASM_ENCODED >> (63 - j)) & 1 for j in range(64)], dtype=np.uint8)
+def _asm_code_bits(template=ASM_ENCODED):
+    return np.array([(template >> (63 - j)) & 1 for j in range(64)], dtype=np.uint8)
 
 
-def asm_scores(soft, nsym):
-    """int64[nsym - 31, 8]: score(p, h) = how many of the code bits j in 12..63 of the encoded marker equal the hard bit 2p + j
-    under h (0..52); empty for nsym < 32"""
+def asm_scores(soft, nsym, template=ASM_ENCODED):
+    """int64[nsym - 31, 8]: score(p, h) = how many of the code bits j in 12..63 of the encoded marker (`template`) equal the hard
+    bit 2p + j under h (0..52); empty for nsym < 32"""
     soft = np.asarray(soft, dtype=np.int8)[:2 * nsym]
     npos = max(nsym - 31, 0)
     out = np.zeros((npos, 8), dtype=np.int64)
     if npos == 0:
         return out
-    e = _asm_code_bits()[ASM_SKIP:]
+    e = _asm_code_bits(template)[ASM_SKIP:]
     for h in range(8):
         a, b = hypothesis(soft[0::2], soft[1::2], h)
         hard = np.stack((a > 0, b > 0), axis=1).ravel().astype(np.uint8)
@@ -112,9 +119,9 @@ def asm_scores(soft, nsym):
     return out
 
 
-def asm_candidates_np(soft, nsym, min_score=MIN_SCORE):
+def asm_candidates_np(soft, nsym, min_score=MIN_SCORE, template=ASM_ENCODED):
     """int64[m, 3] = every (p, h, score) with score >= min_score, sorted by (p, h)"""
-    sc = asm_scores(soft, nsym)
+    sc = asm_scores(soft, nsym, template)
     p, h = np.nonzero(sc >= min_score)
     return np.stack((p, h, sc[p, h]), axis=1).astype(np.int64).reshape(-1, 3)
 
@@ -191,6 +198,152 @@ def finish_np(bits, soft, nsym, p, h):
         for j in _taps(g):
             code[:, col] ^= bits[j:j + FRAME_BITS - 6]
     return body, asm_errors, int(np.sum(code.ravel() != hard))
+
+
+# ------------------------------------------------------------------ section 4.18 in NumPy: NRZ-M, the 80k interleaver and its marker
+ASM_ENCODED_NRZM = 0x03B10B02F33D2076     # encode(nrzm_encode(ASM bits, 0)) from state 0, first code bit in bit 63
+INTERLEAVER_BRANCHES, INTERLEAVER_DELAY = 36, 2048
+MARKER, MARKER_BITS, GROUP_BITS = 0x27, 8, 72            # the marker byte in front of every 72 interleaved bits
+PERIOD_SYMBOLS, MARKER_SYMBOLS = 40, 4                   # (8 + 72) / 2 symbols per period, the first four the marker
+DEINT_SEGMENT = 256                                       # periods per segment of the marker score
+LOCK_MIN_NUM, LOCK_MIN_DEN = 3, 4                         # locked: at least 3/4 of the counted markers' bits match
+DEINT_INFO = np.dtype([("score", np.int64), ("markers", np.int64), ("offset", np.int64), ("hypothesis", np.int64),
+                       ("best_score", np.int64)])
+
+
+def nrzm_encode(d, prev=0):
+    """m[i] = m[i-1] ^ d[i] with m[-1] = prev: a 1 changes the level"""
+    d = np.asarray(d, dtype=np.uint8)
+    return (np.bitwise_xor.accumulate(d) ^ np.uint8(prev & 1)).astype(np.uint8) if len(d) else d.copy()
+
+
+def nrzm_decode(v):
+    """d[i] = v[i] ^ v[i-1] for i >= 1; d[0] = 0 (the bit before lies in another decode span)"""
+    v = np.asarray(v, dtype=np.uint8)
+    d = np.zeros(len(v), dtype=np.uint8)
+    d[1:] = v[1:] ^ v[:-1]
+    return d
+
+
+def finish_nrzm_np(bits, soft, nsym, p, h):
+    """finish_np for a differential stream: d = nrzm_decode(bits); asm_errors over bits 1..31 of d, body = packbits(d)[4:] XOR PN;
+    corrected is finish_np's, from the Viterbi bits themselves"""
+    d = nrzm_decode(bits)
+    _, _, corrected = finish_np(bits, soft, nsym, p, h)
+    asm_errors = int(np.sum(d[1:32] != np.unpackbits(ASM)[1:]))
+    return np.packbits(d)[4:] ^ pn_sequence(), asm_errors, corrected
+
+
+def _check_interleaver(branches, delay):
+    if branches < 1 or GROUP_BITS % branches or delay < 0:
+        raise ValueError("interleaver: branches must divide 72 and delay must be >= 0")
+    return branches * delay * (branches - 1)
+
+
+def interleave_np(x, branches=INTERLEAVER_BRANCHES, delay=INTERLEAVER_DELAY):
+    """code bits (or any values) x[n] -> y with y[n + B M (n mod B)] = x[n], len(x) + B M (B - 1) long, 0 where nothing lands"""
+    x = np.asarray(x)
+    span = _check_interleaver(branches, delay)
+    y = np.zeros(len(x) + span, dtype=x.dtype)
+    n = np.arange(len(x), dtype=np.int64)
+    y[n + branches * delay * (n % branches)] = x
+    return y
+
+
+def deinterleave_np(y, branches=INTERLEAVER_BRANCHES, delay=INTERLEAVER_DELAY):
+    """x[n] = y[n + B M (n mod B)] for 0 <= n < N = len(y) - B M (B - 1), rounded down to even; empty where N <= 0"""
+    y = np.asarray(y)
+    N = max(len(y) - _check_interleaver(branches, delay), 0) & ~1
+    n = np.arange(N, dtype=np.int64)
+    return y[n + branches * delay * (n % branches)]
+
+
+def marker_bits():
+    return np.unpackbits(np.array([MARKER], dtype=np.uint8))
+
+
+def add_markers_np(bits):
+    """The interleaved bits in groups of 72 (the last one filled with 0), each preceded by the 8 bits of 0x27: uint8[80 groups]"""
+    bits = np.asarray(bits, dtype=np.uint8)
+    groups = -(-len(bits) // GROUP_BITS)
+    body = np.zeros((groups, GROUP_BITS), dtype=np.uint8)
+    body.ravel()[:len(bits)] = bits
+    return np.concatenate((np.tile(marker_bits(), (groups, 1)), body), axis=1).ravel()
+
+
+def deint_scores_np(soft, nsym, seg=DEINT_SEGMENT):
+    """int64[nseg, 40, 8]: for the symbols q with q + 4 <= nsym, how many of the 8 hard bits from bit 2q under h equal the marker's,
+    summed into [q // (40 seg), q % 40, h]; nseg = ceil(nsym / (40 seg))"""
+    if seg < 1:
+        raise ValueError("deint_scores_np: seg")
+    soft = np.asarray(soft, dtype=np.int8)[:2 * nsym]
+    nseg = -(-nsym // (PERIOD_SYMBOLS * seg))
+    out = np.zeros((nseg, PERIOD_SYMBOLS, 8), dtype=np.int64)
+    npos = nsym - MARKER_SYMBOLS + 1
+    if npos <= 0:
+        return out
+    q = np.arange(npos, dtype=np.int64)
+    for h in range(8):
+        a, b = hypothesis(soft[0::2], soft[1::2], h)
+        hard = np.stack((a > 0, b > 0), axis=1).ravel().astype(np.uint8)
+        sc = np.sum(np.lib.stride_tricks.sliding_window_view(hard, MARKER_BITS)[::2][:npos] == marker_bits(), axis=1)
+        np.add.at(out[:, :, h], (q // (PERIOD_SYMBOLS * seg), q % PERIOD_SYMBOLS), sc)
+    return out
+
+
+def _markers(nsym, o, lo=0, hi=None):
+    """how many markers of offset o lie wholly inside the symbols and start in [lo, hi)"""
+    hi = nsym - MARKER_SYMBOLS + 1 if hi is None else min(hi, nsym - MARKER_SYMBOLS + 1)
+    first = max(-(-(lo - o) // PERIOD_SYMBOLS), 0)
+    return max(-(-(hi - o) // PERIOD_SYMBOLS) - first, 0)
+
+
+def deint_lock(scores, nsym, seg=DEINT_SEGMENT):
+    """The marker scores int[nseg, 40, 8] of nsym symbols -> dict(offset, hypothesis, score, markers, groups, locked, info): the
+    (o, h) with the largest total over the segments (among equals the lower o, then the lower h), how many markers it counts, the
+    whole periods from o on, locked = score >= 3/4 of 8 bits per counted marker (and there is one), and per segment a DEINT_INFO
+    record: score and markers at the lock, and the segment's own best offset, hypothesis and best_score"""
+    sc = np.asarray(scores, dtype=np.int64).reshape(-1, PERIOD_SYMBOLS, 8)
+    total = sc.sum(axis=0)
+    o, h = (int(v) for v in np.unravel_index(np.argmax(total), total.shape))
+    markers = _markers(nsym, o)
+    info = np.zeros(len(sc), dtype=DEINT_INFO)
+    info["score"] = sc[:, o, h]
+    info["markers"] = [_markers(nsym, o, s * PERIOD_SYMBOLS * seg, (s + 1) * PERIOD_SYMBOLS * seg) for s in range(len(sc))]
+    best = sc.reshape(len(sc), -1).argmax(axis=1) if len(sc) else np.zeros(0, dtype=np.int64)
+    info["offset"], info["hypothesis"] = best // 8, best % 8
+    info["best_score"] = sc.reshape(len(sc), -1).max(axis=1) if len(sc) else 0
+    score = int(total[o, h])
+    return dict(offset=o, hypothesis=h, score=score, markers=markers, groups=max(nsym - o, 0) // PERIOD_SYMBOLS,
+                locked=bool(markers > 0 and LOCK_MIN_DEN * score >= LOCK_MIN_NUM * MARKER_BITS * markers), info=info)
+
+
+def deint_np(soft, nsym, o, h, branches=INTERLEAVER_BRANCHES, delay=INTERLEAVER_DELAY):
+    """The deinterleaved soft pairs int8[2 nsym_out] of the stream locked at (o, h): y[72 t + i] = rail i % 2 of symbol
+    o + 40 t + 4 + i // 2 under h (128 stored as 127) for t < (nsym - o) // 40, then deinterleave_np"""
+    if not (0 <= o < PERIOD_SYMBOLS and 0 <= h < 8):
+        raise ValueError("deint_np: offset in 0..39 and hypothesis in 0..7 expected")
+    soft = np.asarray(soft, dtype=np.int8)[:2 * nsym]
+    groups = (nsym - o) // PERIOD_SYMBOLS
+    sym = (o + PERIOD_SYMBOLS * np.arange(groups, dtype=np.int64)[:, None] + MARKER_SYMBOLS
+           + np.arange(GROUP_BITS // 2, dtype=np.int64)[None, :]).ravel()
+    a, b = hypothesis(soft[2 * sym], soft[2 * sym + 1], h)
+    y = np.minimum(np.stack((a, b), axis=1).ravel(), 127).astype(np.int8)
+    return deinterleave_np(y, branches, delay)
+
+
+def read_soft(path):
+    """A soft-symbol file (raw int8 I, Q pairs, one pair per symbol) -> int8[2 n]; a trailing odd byte is dropped"""
+    soft = np.fromfile(path, dtype=np.int8)
+    return soft[:len(soft) & ~1]
+
+
+def write_soft(path, soft):
+    """int8 soft pairs -> a soft-symbol file"""
+    soft = np.asarray(soft)
+    if soft.dtype != np.dtype(np.int8) or soft.size % 2:
+        raise ValueError("write_soft: int8 I, Q pairs expected")
+    np.ascontiguousarray(soft).ravel().tofile(path)
 
 
 # ------------------------------------------------------------------ section 4.15 in NumPy: GF(256), RS(255,223), interleave
@@ -472,11 +625,15 @@ def soft_symbols(sym):
     return out.view(0, 2 * sym.n)
 
 
-def asm_candidates(soft, nsym, min_score=MIN_SCORE, cap=1 << 16):
-    """int64[m, 3] = every (p, h, score) with score >= min_score, sorted by (p, h); more than `cap` of them raise"""
+def asm_candidates(soft, nsym, min_score=MIN_SCORE, cap=1 << 16, template=ASM_ENCODED):
+    """int64[m, 3] = every (p, h, score) with score >= min_score, sorted by (p, h); more than `cap` of them raise.  `template`: the
+    encoded marker, ASM_ENCODED (dd_lrpt_asm_search) or another 64-bit code word such as ASM_ENCODED_NRZM (dd_lrpt_asm_search_t)"""
     cand = DevArray(3 * max(cap, 1), np.int64)
     cnt = DevArray(1, np.uint64)
-    check(lib().dd_lrpt_asm_search(soft.ptr, nsym, min_score, cap, cand.ptr, cnt.ptr, None), "dd_lrpt_asm_search")
+    if template == ASM_ENCODED:
+        check(lib().dd_lrpt_asm_search(soft.ptr, nsym, min_score, cap, cand.ptr, cnt.ptr, None), "dd_lrpt_asm_search")
+    else:
+        check(lib().dd_lrpt_asm_search_t(soft.ptr, nsym, template, min_score, cap, cand.ptr, cnt.ptr, None), "dd_lrpt_asm_search_t")
     m = int(cnt.to_host()[0])
     if m > cap:
         raise RuntimeError("LRPT marker search: %d candidates, more than %d" % (m, cap))
@@ -492,13 +649,32 @@ def viterbi(soft, nsym, spans, nbits=FRAME_BITS):
     return out.view(0, n * nbits // 8)
 
 
-def finish(bits, soft, nsym, spans):
-    """The frames decoded by viterbi(soft, nsym, spans) -> (bodies uint8[n, 1020], info int32[n, 3] = asm_errors, corrected, vcid)"""
+def finish(bits, soft, nsym, spans, nrzm=False):
+    """The frames decoded by viterbi(soft, nsym, spans) -> (bodies uint8[n, 1020], info int32[n, 3] = asm_errors, corrected, vcid);
+    nrzm: the stream is differential, the frames' bits are nrzm_decode of the Viterbi bits (dd_lrpt_finish_nrzm)"""
     s, n = _spans(spans)
     bodies = DevArray(max(n * BODY_BYTES, 1), np.uint8)
     info = DevArray(max(3 * n, 1), np.int32)
-    check(lib().dd_lrpt_finish(bits.ptr, soft.ptr, nsym, s.ctypes.data, n, bodies.ptr, info.ptr, None), "dd_lrpt_finish")
+    entry = "dd_lrpt_finish_nrzm" if nrzm else "dd_lrpt_finish"
+    check(getattr(lib(), entry)(bits.ptr, soft.ptr, nsym, s.ctypes.data, n, bodies.ptr, info.ptr, None), entry)
     return bodies.view(0, n * BODY_BYTES).to_host().reshape(n, BODY_BYTES), info.view(0, 3 * n).to_host().reshape(n, 3)
+
+
+def deint_scores(soft, nsym, seg=DEINT_SEGMENT):
+    """deint_scores_np on the device -> int64[nseg, 40, 8] on the host"""
+    nseg = -(-nsym // (PERIOD_SYMBOLS * seg)) if seg >= 1 and nsym >= 0 else 0
+    sc = DevArray(max(nseg * PERIOD_SYMBOLS * 8, 1), np.int32)
+    check(lib().dd_lrpt_deint_scores(soft.ptr, nsym, seg, sc.ptr, None), "dd_lrpt_deint_scores")
+    return sc.view(0, nseg * PERIOD_SYMBOLS * 8).to_host().astype(np.int64).reshape(nseg, PERIOD_SYMBOLS, 8)
+
+
+def deint(soft, nsym, o, h, branches=INTERLEAVER_BRANCHES, delay=INTERLEAVER_DELAY):
+    """deint_np on the device (dd_lrpt_deinterleave) -> device int8[2 nsym_out].  (`deinterleave` is section 4.15's, of the
+    Reed-Solomon codewords.)"""
+    out = DevArray(max(GROUP_BITS * (max(nsym, 0) // PERIOD_SYMBOLS), 1), np.int8)        # 36 pairs per period at the most
+    nout = ctypes.c_int64(0)
+    check(lib().dd_lrpt_deinterleave(soft.ptr, nsym, o, h, branches, delay, out.ptr, ctypes.byref(nout), None), "dd_lrpt_deinterleave")
+    return out.view(0, 2 * nout.value)
 
 
 def reed_solomon(bodies):

@@ -492,6 +492,28 @@ int dd_lrpt_viterbi(const int8_t* soft, int64_t nsym, const int64_t* spans_host,
 int dd_lrpt_finish(const uint8_t* bits_packed, const int8_t* soft, int64_t nsym, const int64_t* spans_host, int64_t nspans,
                    uint8_t* bodies, int32_t* info, void* stream);
 int dd_lrpt_rs(const uint8_t* bodies, int64_t nframes, uint8_t* fixed, int32_t* errors, void* stream);
+
+/* ---- The LRPT modes of the Meteor-M N2-x satellites, from soft symbols (DESIGN.md section 4.18 defines every stage) ----------
+ * dd_lrpt_asm_search_t -- dd_lrpt_asm_search against the 64-bit code word `encoded` (first code bit in bit 63) instead of the
+ *     encoded sync marker; with encoded = 0x035D49C24FF2686B it finds what dd_lrpt_asm_search finds.
+ * dd_lrpt_finish_nrzm -- dd_lrpt_finish for a differential (NRZ-M) stream: with v the frame's 8192 decoded bits, d[0] = 0 and
+ *     d[i] = v[i] ^ v[i-1]; bodies = bytes 4..1023 of d XOR the pseudo-noise sequence; info = (bits 1..31 of d that differ from
+ *     the marker, the re-encode count of v as dd_lrpt_finish gives it, the virtual channel id from d).
+ * dd_lrpt_deint_scores -- the marker of the 80 ksym/s interleaver: for every symbol q <= nsym - 4 and hypothesis h, how many of
+ *     the 8 hard bits from bit 2q under h equal those of 0x27 (MSB first), added into scores[((q / (40 seg)) * 40 + q % 40) * 8 + h].
+ *     scores holds ceil(nsym / (40 seg)) * 320 values and is zeroed by the call; 1 <= seg <= 2^24.
+ * dd_lrpt_deinterleave -- for the stream locked at symbol offset o (0..39) under hypothesis h: y[72 t + i] = rail i % 2 of symbol
+ *     o + 40 t + 4 + i / 2 under h (128 stored as 127), t < (nsym - o) / 40; out pair k = (x[2k], x[2k+1]) with
+ *     x[n] = y[n + branches * delay * (n % branches)], for n < N = 72 groups - branches * delay * (branches - 1) rounded down to even.
+ *     *nsym_out (host) = N / 2, 0 when the stream does not fill the branches.  out has room for 36 * (nsym / 40) pairs.
+ *     branches must divide 72, delay >= 0. */
+int dd_lrpt_asm_search_t(const int8_t* soft, int64_t nsym, unsigned long long encoded, int min_score, int64_t cap, int64_t* cand,
+                         unsigned long long* count, void* stream);
+int dd_lrpt_finish_nrzm(const uint8_t* bits_packed, const int8_t* soft, int64_t nsym, const int64_t* spans_host, int64_t nspans,
+                        uint8_t* bodies, int32_t* info, void* stream);
+int dd_lrpt_deint_scores(const int8_t* soft, int64_t nsym, int64_t seg, int32_t* scores, void* stream);
+int dd_lrpt_deinterleave(const int8_t* soft, int64_t nsym, int o, int h, int branches, int delay, int8_t* out, int64_t* nsym_out,
+                         void* stream);
 int dd_lrpt_jpeg(const uint8_t* data, const int64_t* offsets_host, const uint8_t* q_host, const int64_t* dst_host, int64_t npackets,
                  int64_t pitch, uint8_t* out, int32_t* mcus, void* stream);
 

@@ -18,7 +18,14 @@ there, for a kernel trace taken in a run of its own), beside the NumPy restateme
 the stages of getImage on tests/_jpeg.py's case (c) tiled: a tile's sequence counts repeat, so from the second tile on the packets
 are decoded (mcus) and mostly not placed.
 
-    python tools/bench_lrpt.py [--reps 3] [--duration 60] [--case a|b|c] [--kernel-only]
+--case d is the soft-symbol entry in the Meteor-M N2-x modes (decode_lrpt): a differential stream through
+the (36, 2048) interleaver with its markers, --duration seconds at 80 ksym/s, built by tests/_lrpt_modes.py from 16 seeded frame
+bodies tiled to the length (the frames are tiled, not the symbols: the interleaver spreads every bit over 1.43 M symbols, so a
+stream tiled from a short one would hold no whole frame).  Timed with a device synchronisation after each stage: the marker
+scores and the lock (lrpt_deint_scores), the gather (lrpt_deinterleave), and the frame stages behind it with the NRZ-M template
+and finish (lrpt_asm, lrpt_viterbi, lrpt_finish).
+
+    python tools/bench_lrpt.py [--reps 3] [--duration 60] [--case a|b|c|d] [--kernel-only]
 """
 import ctypes as C
 import argparse
@@ -136,15 +143,48 @@ def main_image(a):
     print(json.dumps(res), flush=True)
 
 
+def main_modes(a):
+    import _lrpt_modes
+    from directdemod_amd import _hip, decode_lrpt, lrpt
+    _hip.require_gpu()
+    nsym = int(a.duration * 80000)
+    depth = lrpt.INTERLEAVER_BRANCHES * lrpt.INTERLEAVER_DELAY * (lrpt.INTERLEAVER_BRANCHES - 1)       # bits
+    nframes = max((nsym * 72 // 80 - depth) // lrpt.FRAME_BITS, 1)            # the run-out after them is the interleaver's depth again
+    bodies = np.tile(_lrpt_modes.random_bodies(51, 16), (-(-nframes // 16), 1))[:nframes]
+    s = _lrpt_modes.stream(bodies, 52, differential=True, interleaved=True, branches=lrpt.INTERLEAVER_BRANCHES,
+                           delay=lrpt.INTERLEAVER_DELAY, start=3000, prefix=17, hyp=5)
+    soft = _hip.DevArray.from_host(s["soft"])
+
+    def run():
+        o = decode_lrpt.decode_lrpt(soft, differential=True, interleaved=True)
+        _hip.sync()
+        t0 = time.perf_counter()
+        frames = o.getFrames
+        return o, frames, time.perf_counter() - t0
+    obj, frames, first = run()
+    runs = [run() for _ in range(a.reps)]
+    assert all(np.array_equal(r[1], frames) for r in runs)
+    info = obj.frameInfo
+    assert obj.locked and info["symbol"].tolist() == s["starts"][1:] and np.array_equal(frames, bodies[1:])
+    print(json.dumps({"stage": "decode_lrpt.getFrames", "case": "d", "duration_s": a.duration, "symbols": s["nsym"],
+                      "symbols_deinterleaved": int(obj._deint()[2]), "frames": int(len(frames)),
+                      "frames_asm_clean": int(np.sum(info["asm_errors"] == 0)), "lock": {k: int(v) for k, v in obj.lock.items()},
+                      "first_frames_ms": round(first * 1e3, 3), "warm_frames_ms": round(float(np.median([r[2] for r in runs])) * 1e3, 3),
+                      "warm_stage_ms": {k: round(float(np.median([r[0].timings[k] for r in runs])) * 1e3, 3) for k in runs[0][0].timings},
+                      "device": _hip.device_name()}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--duration", type=float, default=60.0)
-    ap.add_argument("--case", choices=("a", "b", "c"), default="a")
+    ap.add_argument("--case", choices=("a", "b", "c", "d"), default="a")
     ap.add_argument("--kernel-only", action="store_true", help="case c: stop after the dd_lrpt_jpeg calls")
     a = ap.parse_args()
     if a.case == "c":
         return main_image(a)
+    if a.case == "d":
+        return main_modes(a)
     from directdemod_amd import _hip, decode_meteorm2, source
     _hip.require_gpu()
     raw, fs = recording(a.duration, a.case)
