@@ -82,6 +82,9 @@ extern "C" int dd_afsk_edges_f64(const double* binary_filter, int64_t n, int spb
 // the symbol walk of the two sync detectors below, and what else they share
 #include "dd_symbol_walk.h"
 
+// OQPSK symbol recovery for the Meteor-M N2-x satellites: one serial walk, no libm call in the loop
+#include "dd_oqpsk.h"
+
 // Meteor-M2 QPSK sync detection (decode_meteorm2.py:229-324)
 #include "dd_meteor.h"
 

@@ -6,6 +6,7 @@
 //   k_lrpt_deint_scores -- the 8-bit marker 0x27 against the hard bits at every symbol under the eight hypotheses, summed per
 //                          (segment, symbol mod 40, hypothesis)
 //   k_lrpt_deinterleave -- the gather through the convolutional interleaver: marker symbols dropped, one output pair per lane
+//   k_lrpt_restagger    -- the rails of an OQPSK demodulator's output brought back together: pair k = (I[k], Q[k + s]) (section 4.19)
 #pragma once
 
 #define DD_LRPT_PERIOD 40             // symbols per marker period: 4 of the marker, 36 of interleaved code bits
@@ -161,6 +162,27 @@ __global__ void __launch_bounds__(256) k_lrpt_deinterleave(const char2* __restri
         v[e] = w > 127 ? 127 : w;
     }
     out[k] = make_char2((signed char)v[0], (signed char)v[1]);
+}
+
+// s = -1, 0, +1: output pair j = (I[j + lead], Q[j + lead + s]) with lead = 1 for s = -1, else 0; nout = nsym - |s| pairs, so both
+// indices lie inside the nsym input pairs.  One lane per pair, one char2 store.
+__global__ void __launch_bounds__(256) k_lrpt_restagger(const signed char* __restrict__ soft, int s, char2* __restrict__ out, int64_t nout) {
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= nout) return;
+    const int64_t k = j + (s < 0 ? 1 : 0);
+    out[j] = make_char2(soft[2 * k], soft[2 * (k + s) + 1]);
+}
+
+extern "C" int dd_lrpt_restagger(const int8_t* soft, int64_t nsym, int s, int8_t* out, void* stream) {
+    DD_REQUIRE(nsym >= 0 && s >= -1 && s <= 1, "dd_lrpt_restagger: nsym >= 0 and a stagger of -1, 0 or 1 expected");
+    const int64_t nout = nsym - (s != 0 ? 1 : 0);
+    if (nout <= 0) return DD_OK;
+    DD_REQUIRE(soft != nullptr && out != nullptr, "dd_lrpt_restagger: null buffer");
+    DD_REQUIRE((nout + 255) / 256 <= 0x7fffffff, "dd_lrpt_restagger: too many symbols");
+    hipLaunchKernelGGL(k_lrpt_restagger, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, dd_stream(stream), (const signed char*)soft, s,
+                       (char2*)out, nout);
+    DD_LAUNCH_CHECK();
+    return DD_OK;
 }
 
 extern "C" int dd_lrpt_asm_search_t(const int8_t* soft, int64_t nsym, unsigned long long encoded, int min_score, int64_t cap, int64_t* cand,

@@ -1,10 +1,12 @@
 """
 LRPT decoding from soft symbols -- the int8 I, Q pairs that demodulators write and decoders read (the `.s` file), in the mode of
 Meteor-M N2 and in the modes of the N2-x satellites: differential (NRZ-M) coding in front of the convolutional encoder, and the
-80 ksym/s mode's convolutional interleaver with its 8-bit marker (lrpt.py).
+80 ksym/s mode's convolutional interleaver with its 8-bit marker (lrpt.py), with the rails of an OQPSK
+demodulator's output brought back together where they lie one symbol apart (`stagger`, section 4.19).
 
 `LrptChain` is the chain behind the soft symbols -- frames (section 4.14), Reed-Solomon correction and source packets (4.15), the
-picture (4.16) -- that `decode_lrpt` here and `decode_meteorm2` (whose soft symbols come from its symbol walk) both run.
+picture (4.16) -- that `decode_lrpt` here, `decode_meteorm2` (whose soft symbols come from its symbol walk) and `decode_meteorm2x`
+(decode_lrpt behind the OQPSK walk) all run.
 """
 import os
 import time
@@ -17,7 +19,8 @@ from . import _hip, lrpt
 class LrptChain:
     """getFrames / frameInfo, getVCDUs / rsInfo / getPackets / packetInfo, getImage / getChannel / imageInfo over the soft symbols a
     subclass supplies: _lrpt_prepare() does what has to be there before them (not timed here); _lrpt_soft() -> (device int8 pairs,
-    nsym, samples) with samples(symbols) -> frameInfo['sample'] of frames that start at those symbols.  Every stage runs once and is cached; `timings` gains lrpt_* (seconds per stage)."""
+    nsym, samples) with samples(symbols) -> frameInfo['sample'] of frames that start at those symbols; _lrpt_starts(soft, nsym) is
+    the marker search, which a subclass that has searched already answers from what it found.  Every stage runs once and is cached; `timings` gains lrpt_* (seconds per stage)."""
 
     def _init_chain(self, apids, period, differential=False):
         self._nrzm = bool(differential)
@@ -119,6 +122,10 @@ class LrptChain:
         self._rs = (vcdus, info, pkts, pinfo)
         return self._rs
 
+    def _lrpt_starts(self, soft, nsym):
+        """the frame starts int64[m, 3] = (symbol, hypothesis, asm_score) among the soft pairs"""
+        return lrpt.frame_starts(lrpt.asm_candidates(soft, nsym, template=self._template), nsym)
+
     def _decode_frames(self):
         if self._frames is not None:
             return self._frames
@@ -133,7 +140,7 @@ class LrptChain:
             t0 = now
         soft, nsym, samples = self._lrpt_soft()
         lap("soft")
-        starts = lrpt.frame_starts(lrpt.asm_candidates(soft, nsym, template=self._template), nsym)
+        starts = self._lrpt_starts(soft, nsym)
         lap("asm")
         bits = lrpt.viterbi(soft, nsym, starts[:, :2])
         lap("viterbi")
@@ -149,19 +156,29 @@ class LrptChain:
 
 
 class decode_lrpt(LrptChain):
-    """decode_lrpt(soft, *, differential=False, interleaved=False, branches=36, delay=2048, apids=..., period=...): `soft` is a path
+    """decode_lrpt(soft, *, differential=False, interleaved=False, branches=36, delay=2048, apids=..., period=..., stagger=0): `soft` is a path
     to a soft-symbol file, an int8 NumPy array of I, Q pairs or a device int8 array of them.
     differential: the data are NRZ-M coded in front of the convolutional encoder (the N2-x satellites).
     interleaved: the 80 ksym/s mode -- the code bits pass a convolutional interleaver of `branches` branches and `delay` bits per
     branch step and come in groups of 72 behind the marker 0x27.  `locked`: whether the marker was found (at least 3/4 of the counted
     markers' bits match at the best offset and hypothesis); a stream that is not locked gives zero frames.  `deintInfo`: one
     lrpt.DEINT_INFO record per segment of 256 periods.  Without `interleaved`, `locked` is True and `deintInfo` is empty.
+    stagger: the rails of an OQPSK demodulator's output may lie one symbol apart.  0, -1 or +1 decodes the
+    pairs (I[k], Q[k + stagger]); "auto" tries 0, -1, +1 in that order and keeps the stream whose frame starts have the largest
+    sum of asm_score -- with `interleaved`, the largest marker score of the lock -- the earlier one among equals.  `stagger` (the
+    attribute) is the one used; with "auto" the three marker searches' time is timings["lrpt_stagger"] (and lrpt_deint_scores is
+    not set: the chosen candidate's lock is reused).
     The results are LrptChain's, with the dtypes of decode_meteorm2's; frameInfo['sample'] is -1 (there is no walk) and
     frameInfo['symbol'] counts in the deinterleaved stream when `interleaved`."""
 
     def __init__(self, soft, *, differential=False, interleaved=False, branches=lrpt.INTERLEAVER_BRANCHES, delay=lrpt.INTERLEAVER_DELAY,
-                 apids=lrpt.IMAGE_APIDS, period=lrpt.IMAGE_PERIOD):
+                 apids=lrpt.IMAGE_APIDS, period=lrpt.IMAGE_PERIOD, stagger=0):
         self._init_chain(apids, period, differential)
+        if isinstance(stagger, bool) or stagger not in (0, -1, 1, "auto"):
+            raise ValueError("decode_lrpt: a stagger of 0, -1, +1 or \"auto\" expected, got %r" % (stagger,))
+        self._stagger_arg = stagger
+        self._stagger = None
+        self._starts = None
         self.timings = {}
         self._interleaved = bool(interleaved)
         self._branches, self._delay = int(branches), int(delay)
@@ -190,6 +207,12 @@ class decode_lrpt(LrptChain):
         return self._deint()[0]["info"]
 
     @property
+    def stagger(self):
+        """The stagger the stream was decoded with: the keyword's, or the one "auto" chose"""
+        self._deint()
+        return self._stagger
+
+    @property
     def lock(self):
         """lrpt.deint_lock's dict: offset, hypothesis, score, markers, groups, locked"""
         return {k: v for k, v in self._deint()[0].items() if k != "info"}
@@ -202,6 +225,12 @@ class decode_lrpt(LrptChain):
         soft = self._input if isinstance(self._input, _hip.DevArray) else _hip.DevArray.from_host(self._input)
         nsym = soft.n // 2
         self._input = soft
+        if self._stagger_arg == "auto":
+            return self._deint_auto(soft, nsym)
+        self._stagger = self._stagger_arg
+        if self._stagger:
+            soft = lrpt.restagger(soft, nsym, self._stagger)
+            nsym = soft.n // 2
         if not self._interleaved:
             self._lock = (dict(offset=0, hypothesis=0, score=0, markers=0, groups=0, locked=True, info=np.zeros(0, dtype=lrpt.DEINT_INFO)),
                           soft, nsym)
@@ -218,6 +247,38 @@ class decode_lrpt(LrptChain):
         self.timings["lrpt_deint_scores"], self.timings["lrpt_deinterleave"] = t1 - t0, time.perf_counter() - t1
         self._lock = (lock, out, out.n // 2)
         return self._lock
+
+    def _deint_auto(self, soft, nsym):
+        """stagger="auto": the three candidate streams, each through the marker search of its mode, and the best of them"""
+        t0 = time.perf_counter()
+        tried = []
+        for s in lrpt.STAGGERS:
+            cand = lrpt.restagger(soft, nsym, s) if s else soft
+            n = cand.n // 2
+            if self._interleaved:
+                found = lrpt.deint_lock(lrpt.deint_scores(cand, n), n)
+                tried.append((found["score"], cand, n, found))
+            else:
+                found = LrptChain._lrpt_starts(self, cand, n)
+                tried.append((int(found[:, 2].sum()), cand, n, found))
+        self._stagger = lrpt.stagger_pick([t[0] for t in tried])
+        _, cand, n, found = tried[lrpt.STAGGERS.index(self._stagger)]
+        _hip.sync()
+        self.timings["lrpt_stagger"] = time.perf_counter() - t0
+        if not self._interleaved:
+            self._starts = found
+            self._lock = (dict(offset=0, hypothesis=0, score=0, markers=0, groups=0, locked=True, info=np.zeros(0, dtype=lrpt.DEINT_INFO)),
+                          cand, n)
+            return self._lock
+        t1 = time.perf_counter()
+        out = lrpt.deint(cand, n, found["offset"], found["hypothesis"], self._branches, self._delay) if found["locked"] else cand.view(0, 0)
+        _hip.sync()
+        self.timings["lrpt_deinterleave"] = time.perf_counter() - t1      # (the three marker searches are in lrpt_stagger)
+        self._lock = (found, out, out.n // 2)
+        return self._lock
+
+    def _lrpt_starts(self, soft, nsym):
+        return self._starts if self._starts is not None else super()._lrpt_starts(soft, nsym)
 
     def _lrpt_prepare(self):
         self._deint()

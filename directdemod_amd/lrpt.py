@@ -21,6 +21,9 @@ another template (`asm_candidates(template=ASM_ENCODED_NRZM)`) and `finish(nrzm=
 interleaver behind its 8-bit marker: `deint_scores`, `deint_lock` (host), `deint` (dd_lrpt_modes.h); the soft-symbol file
 (`read_soft`, `write_soft`).  Restatements: `nrzm_encode`, `nrzm_decode`, `finish_nrzm_np`, `interleave_np`, `deinterleave_np`,
 `add_markers_np`, `deint_scores_np`, `deint_np`.  decode_lrpt.py runs the whole chain on such a stream.
+
+Section 4.19 adds the one-symbol stagger between the rails that an OQPSK demodulator leaves at two of its four carrier-phase
+ambiguities: `restagger` (dd_lrpt_modes.h), restated as `restagger_np`; decode_lrpt's `stagger` keyword tries the three of them.
 """
 import ctypes
 import functools
@@ -330,6 +333,43 @@ def deint_np(soft, nsym, o, h, branches=INTERLEAVER_BRANCHES, delay=INTERLEAVER_
     a, b = hypothesis(soft[2 * sym], soft[2 * sym + 1], h)
     y = np.minimum(np.stack((a, b), axis=1).ravel(), 127).astype(np.int8)
     return deinterleave_np(y, branches, delay)
+
+
+def restagger_np(soft, nsym, s):
+    """The rails of an OQPSK demodulator's output brought together: int8[2 (nsym - |s|)], output pairs
+    (I[k], Q[k + s]) for every k with both indices in range, s in -1, 0, +1"""
+    if s not in (-1, 0, 1) or nsym < 0:
+        raise ValueError("restagger_np: a stagger of -1, 0 or 1 expected")
+    soft = np.asarray(soft, dtype=np.int8)[:2 * nsym]
+    nout = max(nsym - abs(s), 0)
+    lead = 1 if s < 0 else 0
+    out = np.zeros(2 * nout, dtype=np.int8)
+    out[0::2] = soft[0::2][lead:lead + nout]
+    out[1::2] = soft[1::2][lead + s:lead + s + nout]
+    return out
+
+
+STAGGERS = (0, -1, 1)                                     # the order in which stagger="auto" tries them
+
+
+def stagger_pick(scores):
+    """the stagger of STAGGERS with the largest score, the earlier one among equals"""
+    return STAGGERS[int(np.argmax(np.asarray(scores, dtype=np.int64)))]
+
+
+def stagger_scores_np(soft, nsym, interleaved=False, template=ASM_ENCODED):
+    """Per stagger of STAGGERS the score of the re-staggered stream: the sum of asm_score over its frame starts, or with
+    `interleaved` the marker score of its deint_lock.  (Under a wrong stagger half of a frame marker's bits are random and it stays
+    below MIN_SCORE; the 8-bit marker still finds 15/16 of its bits at a neighbouring offset with one rail inverted.)"""
+    out = []
+    for s in STAGGERS:
+        c = restagger_np(soft, nsym, s)
+        n = len(c) // 2
+        if interleaved:
+            out.append(int(deint_lock(deint_scores_np(c, n), n)["score"]))
+        else:
+            out.append(int(frame_starts(asm_candidates_np(c, n, template=template), n)[:, 2].sum()))
+    return out
 
 
 def read_soft(path):
@@ -675,6 +715,14 @@ def deint(soft, nsym, o, h, branches=INTERLEAVER_BRANCHES, delay=INTERLEAVER_DEL
     nout = ctypes.c_int64(0)
     check(lib().dd_lrpt_deinterleave(soft.ptr, nsym, o, h, branches, delay, out.ptr, ctypes.byref(nout), None), "dd_lrpt_deinterleave")
     return out.view(0, 2 * nout.value)
+
+
+def restagger(soft, nsym, s):
+    """restagger_np on the device (dd_lrpt_restagger) -> device int8[2 (nsym - |s|)]"""
+    nout = max(nsym - abs(s), 0) if s in (-1, 0, 1) else 0
+    out = DevArray(max(2 * nout, 1), np.int8)
+    check(lib().dd_lrpt_restagger(soft.ptr, nsym, s, out.ptr, None), "dd_lrpt_restagger")
+    return out.view(0, 2 * nout)
 
 
 def reed_solomon(bodies):

@@ -517,6 +517,19 @@ int dd_lrpt_deinterleave(const int8_t* soft, int64_t nsym, int o, int h, int bra
 int dd_lrpt_jpeg(const uint8_t* data, const int64_t* offsets_host, const uint8_t* q_host, const int64_t* dst_host, int64_t npackets,
                  int64_t pitch, uint8_t* out, int32_t* mcus, void* stream);
 
+/* ---- OQPSK demodulation for the Meteor-M N2-x satellites (beyond the reference; DESIGN.md section 4.19 defines every operation) ----
+ * dd_oqpsk_walk -- the OQPSK symbol walk over x[n] (complex128, absolute sample index base + j): Gardner timing on both staggered
+ *     rails of the derotated samples, agc (gain cap 200) and a Costas loop whose phase is kept in turns, in one serial chain with no
+ *     libm call.  state = DDOqpskState (csrc/dd_oqpsk.h; 15 doubles, 5 int64), carried from chunk to chunk; params_host =
+ *     DDMeteorParams with the loop gains in turns; table = device double[1024][2] = (cos, sin)(2 pi i / 1024).  Symbol k (the k-th B
+ *     event after an A) writes bidx[k], aidx[k] (the samples its Q and its I were read at), sym[k] = (I, Q) and uf[k] = (phase in
+ *     turns, frequency in turns per symbol) after its step; k >= cap sets the state's overflow flag instead.
+ * dd_lrpt_restagger -- out pair j = (I[j + lead], Q[j + lead + s]) of the nsym soft pairs, lead = 1 for s = -1, else 0:
+ *     nsym - |s| pairs (none for nsym <= |s|); s in -1, 0, 1. */
+int dd_oqpsk_walk(const void* x, int64_t n, int64_t base, void* state, const double* params_host, const void* table, int64_t cap,
+                  int64_t* bidx, int64_t* aidx, void* sym, void* uf, void* stream);
+int dd_lrpt_restagger(const int8_t* soft, int64_t nsym, int s, int8_t* out, void* stream);
+
 /* ---- Funcube BPSK sync detection (decode_funcube.py:148-306) ------------------------------------------------------------
  * dd_funcube_mix_ramp -- dd_meteor_mix with the frequency formed per sample: th = ((w * f[k]) * k) * inv_fs, w = -2 pi,
  *     f[k] = f0 + k * delta (np.arange's fill) clipped to target from above when target > f0, from below otherwise.
