@@ -85,6 +85,9 @@ extern "C" int dd_afsk_edges_f64(const double* binary_filter, int64_t n, int spb
 // OQPSK symbol recovery for the Meteor-M N2-x satellites: one serial walk, no libm call in the loop
 #include "dd_oqpsk.h"
 
+// G3RUH 9600 baud FSK: bit timing on FM audio, descrambler, NRZI
+#include "dd_fsk.h"
+
 // Meteor-M2 QPSK sync detection (decode_meteorm2.py:229-324)
 #include "dd_meteor.h"
 

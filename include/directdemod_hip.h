@@ -530,6 +530,20 @@ int dd_oqpsk_walk(const void* x, int64_t n, int64_t base, void* state, const dou
                   int64_t* bidx, int64_t* aidx, void* sym, void* uf, void* stream);
 int dd_lrpt_restagger(const int8_t* soft, int64_t nsym, int s, int8_t* out, void* stream);
 
+/* ---- G3RUH 9600 baud FSK (beyond the reference; DESIGN.md section 4.20 defines every operation) --------------------------------
+ * dd_fsk_walk -- bit-timing recovery over FM-demodulated audio x[n] (float64, absolute sample index base + j): a dc tracker and a
+ *     mean-|y| normaliser on every sample, linearly interpolated transition and eye samples, a clamped Gardner error; one serial
+ *     chain of + - * / comparisons and fabs.  state = DDFskState (csrc/dd_fsk.h; 6 doubles t, dc, am, prev, mid, last and 2 int64
+ *     ctr, overflow), carried from call to call; params_host = 4 doubles P, P / 2, P / 2 + 1, g with 2 <= P <= 64.  Symbol k writes
+ *     sym[k] (the eye), sidx[k] (its sample) and tmu[k] (the timing after its update); k >= cap sets the state's overflow flag
+ *     instead and ctr counts on.
+ * dd_fsk_bits -- r[k] = sym[k] > 0, d[k] = r[k] ^ r[k-12] ^ r[k-17] (0 before the start), bits[0] = 1, bits[k] = (d[k] == d[k-1]);
+ *     marks and flags as dd_afsk_bits_f64 gives them.  Device outputs int8[nsym] and flags[cap_flags]; counts_host[2] = (nsym, flags). */
+int dd_fsk_walk(const double* x, int64_t n, int64_t base, void* state, const double* params_host, int64_t cap, double* sym,
+                int64_t* sidx, double* tmu, void* stream);
+int dd_fsk_bits(const double* sym, int64_t nsym, int8_t* r, int8_t* bits, int8_t* marks, int64_t* flags, int64_t cap_flags,
+                int64_t* counts_host, void* stream);
+
 /* ---- Funcube BPSK sync detection (decode_funcube.py:148-306) ------------------------------------------------------------
  * dd_funcube_mix_ramp -- dd_meteor_mix with the frequency formed per sample: th = ((w * f[k]) * k) * inv_fs, w = -2 pi,
  *     f[k] = f0 + k * delta (np.arange's fill) clipped to target from above when target > f0, from below otherwise.
