@@ -88,6 +88,9 @@ extern "C" int dd_afsk_edges_f64(const double* binary_filter, int64_t n, int spb
 // G3RUH 9600 baud FSK: bit timing on FM audio, descrambler, NRZI
 #include "dd_fsk.h"
 
+// Slow-scan television, PD modes: lag product, tone classes, windowed runs, pixels, colour
+#include "dd_sstv.h"
+
 // Meteor-M2 QPSK sync detection (decode_meteorm2.py:229-324)
 #include "dd_meteor.h"
 

@@ -544,6 +544,30 @@ int dd_fsk_walk(const double* x, int64_t n, int64_t base, void* state, const dou
 int dd_fsk_bits(const double* sym, int64_t nsym, int8_t* r, int8_t* bits, int8_t* marks, int64_t* flags, int64_t cap_flags,
                 int64_t* counts_host, void* stream);
 
+/* ---- Slow-scan television, PD modes (beyond the reference; DESIGN.md section 4.21 defines every stage) ----------------------------
+ * All float64, + - * / comparisons, ceil and rint, each rounded on its own; sstv.py restates every entry in NumPy.
+ * dd_sstv_lag -- z[i] = sum over k < K of h[k] x[i - k] (x = 0 before the start; real and imaginary sums apart, k ascending),
+ *     d[i] = z[i] conj(z[i - 1]) with z[-1] = 0, as n (re, im) pairs.  taps_host = K real parts, then K imaginary parts; K odd, <= 511.
+ * dd_sstv_classes -- cls[i] in 0..4 (none, 1100, 1200, 1300 Hz, leader) from the angle of d[i] against six band edges,
+ *     edges_host = six cosines then six sines, ascending angles in (0, pi): class j + 1 for [edge j, edge j + 1), j < 3, and 4 for
+ *     [edge 4, edge 5); an imaginary part <= 0 and a NaN give 0.
+ * dd_sstv_runs -- count(i) = how many of cls[i .. i + window) equal target, i <= n - window; every maximal run of count >= thresh
+ *     gives one position, the first index of its largest count, in ascending order: pos[min(*count_host, cap)], *count_host = the
+ *     number of runs.  More runs than cap: DD_ERR_INVALID with the count filled and nothing written past cap.  n < window: no runs.
+ * dd_sstv_pixels -- per segment g < nseg and pixel p < W: a = ceil(t0[g] + p step), b = ceil(t0[g] + (p + 1) step), clipped to
+ *     [0, n], D = d[a] + .. + d[b - 1] ascending, levels[g W + p] = clip(rint((angle(D) c1 - 1500) 255 / 800), 0, 255) with
+ *     sstv.atan_host's polynomial angle (0 for a negative imaginary part), c1 = rate / 2 pi; an empty interval or D = 0 gives level 0
+ *     and counts in *empty_host.  t0 is a device array.
+ * dd_sstv_color -- levels[pair][4][W] = Y0, Cr, Cb, Y1 -> rgb[2 pair + row][W][3]: R = (100 Y + 140 Cr - 17850) / 100,
+ *     G = (100 Y - 71 Cr - 33 Cb + 13260) / 100, B = (100 Y + 178 Cb - 22695) / 100, floor division, clipped to 0..255. */
+int dd_sstv_lag(const double* x, int64_t n, const double* taps_host, int K, void* d, void* stream);
+int dd_sstv_classes(const void* d, int64_t n, const double* edges_host, int8_t* cls, void* stream);
+int dd_sstv_runs(const int8_t* cls, int64_t n, int target, int64_t window, int64_t thresh, int64_t* pos, int64_t cap,
+                 int64_t* count_host, void* stream);
+int dd_sstv_pixels(const void* d, int64_t n, const double* t0, int64_t nseg, int W, double step, double c1, uint8_t* levels,
+                   int64_t* empty_host, void* stream);
+int dd_sstv_color(const uint8_t* levels, int64_t npairs, int W, uint8_t* rgb, void* stream);
+
 /* ---- Funcube BPSK sync detection (decode_funcube.py:148-306) ------------------------------------------------------------
  * dd_funcube_mix_ramp -- dd_meteor_mix with the frequency formed per sample: th = ((w * f[k]) * k) * inv_fs, w = -2 pi,
  *     f[k] = f0 + k * delta (np.arange's fill) clipped to target from above when target > f0, from below otherwise.
