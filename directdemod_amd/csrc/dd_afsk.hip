@@ -94,6 +94,9 @@ extern "C" int dd_afsk_edges_f64(const double* binary_filter, int64_t n, int spb
 // Meteor-M2 QPSK sync detection (decode_meteorm2.py:229-324)
 #include "dd_meteor.h"
 
+// what the channel decoders below share: the K = 7 trellis, the pseudo-noise bytes, the candidate list
+#include "dd_fec.h"
+
 // Meteor-M2 LRPT channel decoding: soft symbols to frame bodies
 #include "dd_lrpt.h"
 

@@ -1,13 +1,13 @@
 // Funcube telemetry frames (beyond the reference; DESIGN.md section 4.17 defines every stage bit for bit, funcube_fec.py restates it
-// in NumPy), included by dd_afsk.hip after dd_lrpt.h, dd_lrpt_rs.h and dd_funcube.h.  All arithmetic is integer.
+// in NumPy), included by dd_afsk.hip after dd_fec.h, dd_lrpt_rs.h and dd_funcube.h.  All arithmetic is integer.
 //
 //   k_fc_diff     -- ten-symbol bit sums of the int8 soft symbols and the differential metric D of two sums ten symbols apart
 //   k_fc_sync     -- the 65-bit sync vector, spread over a frame at stride 800, against D at every position: (position,
 //                    correlation, score) of every score >= min_score is a candidate
-//   k_fc_viterbi  -- one wave per frame: the de-interleaving gather, the terminated K = 7 trellis with lane = state (the
-//                    add-compare-select and traceback of k_lrpt_viterbi), descrambling, and the re-encode count
-//   k_fc_rs       -- one wave per codeword of the (160,128) code, two per frame: the word behind 95 zero bytes, decoded as k_lrpt_rs
-//                    decodes its words; a root among the 95 rejects the word
+//   k_fc_viterbi  -- one wave per frame: the de-interleaving gather, the terminated K = 7 trellis with lane = state (dd_fec.h),
+//                    descrambling, and the re-encode count
+//   k_fc_rs       -- one wave per codeword of the (160,128) code, two per frame: the word behind 95 zero bytes, decoded by
+//                    dd_rs_wave; a root among the 95 rejects the word
 //
 // The format's constants (public descriptions of the AO-40 FEC block; not checked against a recording) are all here.
 #pragma once
@@ -30,7 +30,6 @@
 
 struct DDFcFormat {
     int8_t sync[DD_FCF_SYNC];         // 2 V[k] - 1
-    uint8_t pn[255];                  // the CCSDS pseudo-noise sequence's first 255 bytes (its period: 255 bits)
 };
 
 static constexpr DDFcFormat dd_fc_make_format() {
@@ -41,13 +40,6 @@ static constexpr DDFcFormat dd_fc_make_format() {
         int t = sr & DD_FCF_SYNC_TAPS, par = 0;
         for (; t; t >>= 1) par ^= t & 1;
         sr = ((sr << 1) | par) & 0x7F;
-    }
-    int r[8] = {1, 1, 1, 1, 1, 1, 1, 1};
-    for (int i = 0; i < 255 * 8; ++i) {
-        f.pn[i >> 3] = (uint8_t)(f.pn[i >> 3] | (r[0] << (7 - (i & 7))));
-        const int fb = r[0] ^ r[3] ^ r[5] ^ r[7];
-        for (int q = 0; q < 7; ++q) r[q] = r[q + 1];
-        r[7] = fb;
     }
     return f;
 }
@@ -93,22 +85,18 @@ __global__ void __launch_bounds__(256) k_fc_sync(const int8_t* __restrict__ D, i
         neg += (d < 0) == (v > 0);
     }
     const int score = C < 0 ? neg : pos;
-    if (score >= min_score) {
-        const unsigned long long c = atomicAdd(count, 1ull);
-        if ((int64_t)c < cap) {
-            cand[3 * c] = p;
-            cand[3 * c + 1] = C;
-            cand[3 * c + 2] = score;
-        }
+    if (score < min_score) return;
+    if (int64_t* t = dd_cand_slot(cap, cand, count)) {
+        t[0] = p;
+        t[1] = C;
+        t[2] = score;
     }
 }
 
 // Frame blockIdx.x = (p, inv), one wave.  xs[j] = D[p + 10 pos(j)], kept as received and negated in int32 where inv (-(-128) = 128
-// survives).  Then k_lrpt_viterbi's walk over all 2566 steps: lane ns is state ns, its predecessors ((ns & 31) << 1) | x come by
-// cross-lane reads, x = 1 survives only when strictly larger, a step's 64 decisions are one ballot word and the words of 64 steps
-// sit one per lane until they go to LDS together.  State 0 starts at 0 and the others at -(1 << 24); traceback starts from state 0.
-// Metrics stay within 2566 * 256 of their start: int32.  The workgroup is one wave and no lane leaves early: every barrier is met
-// by all 64 lanes.
+// survives).  Then dd_fec.h's trellis over all 2566 steps, the decision words of 64 steps going to LDS together.  State 0 starts at 0
+// and the others at -(1 << 24); traceback starts from state 0.  Metrics stay within 2566 * 256 of their start: int32.  The
+// workgroup is one wave and no lane leaves early: every barrier is met by all 64 lanes.
 __global__ void __launch_bounds__(64) k_fc_viterbi(const int8_t* __restrict__ D, const int64_t* __restrict__ frames,
                                                     uint8_t* __restrict__ blocks, int* __restrict__ corrected) {
     __shared__ unsigned long long dec[DD_FCF_STEPS_PAD];
@@ -128,46 +116,22 @@ __global__ void __launch_bounds__(64) k_fc_viterbi(const int8_t* __restrict__ D,
     }
     __syncthreads();
     const int T = DD_FCF_STEPS;
-    const int pred0 = (lane & 31) << 1;
-    int s1[2], s2[2];                                                 // 2 c - 1 of the branches from the two predecessors
-    for (int x = 0; x < 2; ++x) {
-        const int r = ((lane >> 5) << 6) | pred0 | x;
-        s1[x] = 2 * (__popc(r & DD_LRPT_G1) & 1) - 1;
-        s2[x] = 2 * (__popc(r & DD_LRPT_G2) & 1) - 1;
-    }
+    int s1[2], s2[2];
+    dd_k7_signs(lane, s1, s2);
     int m = lane == 0 ? 0 : DD_FCF_START;
     for (int c = 0; c < T; c += 64) {
         const int a = sgn * xs[2 * (c + lane)], b = sgn * xs[2 * (c + lane) + 1];      // 0 past the last step
-        unsigned long long w = 0;
-        const int nj = T - c < 64 ? T - c : 64;
-        for (int j = 0; j < nj; ++j) {
-            const int aj = __builtin_amdgcn_readlane(a, j), bj = __builtin_amdgcn_readlane(b, j);
-            const int c0 = __shfl(m, pred0, 64) + s1[0] * aj + s2[0] * bj;
-            const int c1 = __shfl(m, pred0 | 1, 64) + s1[1] * aj + s2[1] * bj;
-            const bool d = c1 > c0;
-            const unsigned long long word = __ballot(d);
-            m = d ? c1 : c0;
-            if (lane == j) w = word;
-        }
-        dec[c + lane] = w;
+        dec[c + lane] = dd_k7_acs(a, b, T - c < 64 ? T - c : 64, lane, s1, s2, m);
     }
     __syncthreads();
     int st = 0;                                                       // the trellis is terminated
-    for (int c = ((T - 1) >> 6) << 6; c >= 0; c -= 64) {
-        const unsigned long long w = dec[c + lane];
-        const int wl = (int)(uint32_t)w, wh = (int)(uint32_t)(w >> 32);
-        const int nj = T - c < 64 ? T - c : 64;
-        for (int j = nj - 1; j >= 0; --j) {
-            const uint32_t half = (uint32_t)(st < 32 ? __builtin_amdgcn_readlane(wl, j) : __builtin_amdgcn_readlane(wh, j));
-            if (lane == 0) ob[c + j] = (uint8_t)(st >> 5);
-            st = ((st & 31) << 1) | (int)((half >> (st & 31)) & 1);
-        }
-    }
+    for (int c = ((T - 1) >> 6) << 6; c >= 0; c -= 64)                // every step is inside the window: step j of the group to ob[c + j]
+        st = dd_k7_traceback(dec[c + lane], T - c < 64 ? T - c : 64, -c, 64, st, lane, ob);
     __syncthreads();
     for (int i = lane; i < DD_FCF_BLOCK; i += 64) {
         uint32_t byte = 0;
         for (int q = 0; q < 8; ++q) byte = (byte << 1) | ob[8 * i + q];
-        blocks[f * DD_FCF_BLOCK + i] = (uint8_t)(byte ^ dd_fc_format.pn[i % 255]);
+        blocks[f * DD_FCF_BLOCK + i] = (uint8_t)(byte ^ dd_pn.b[i % 255]);
     }
     // step t: r = the decoded bits t-6 .. t, bit t in r's bit 6, zeros before the first (the encoder starts in state 0)
     int mine = 0;
@@ -177,95 +141,14 @@ __global__ void __launch_bounds__(64) k_fc_viterbi(const int8_t* __restrict__ D,
             const int u = t - 6 + j;
             r |= (u >= 0 ? (int)ob[u] : 0) << j;
         }
-        const int a = sgn * xs[2 * t], b = sgn * xs[2 * t + 1];
-        mine += ((__popc(r & DD_LRPT_G1) & 1) != (a > 0)) + ((__popc(r & DD_LRPT_G2) & 1) != (b > 0));
+        mine += dd_k7_mismatch(r, sgn * xs[2 * t], sgn * xs[2 * t + 1]);
     }
     for (int off = 32; off >= 1; off >>= 1) mine += __shfl_xor(mine, off, 64);
     if (lane == 0) corrected[f] = mine;
 }
 
-// One wave, one codeword, by the steps of k_lrpt_rs's wave (that kernel is left as it is; its field helpers and dd_rs_syndrome are
-// shared): row[0] = 0 and row[1 + i] = byte i of the wave's own 256-byte LDS row; pos[q] = lane + 64 q are the lane's positions,
-// got[q] the bytes received there (0 at position 255) and out[] enters equal to got[].  Returns the bytes changed (0..16) with the
-// corrected bytes in out[], or -1 with out[] = got[].  A root among the 95 shortened positions would put a non-zero byte where the
-// shortened code has none: the word is rejected there.  Only wave-level operations: no workgroup barrier.
-__device__ __forceinline__ int dd_fc_rs_wave(const uint8_t* ex, const uint8_t* lg, uint8_t* row, int lane, const int (&pos)[4],
-                                             const int (&got)[4], int (&out)[4]) {
-    const int S = dd_rs_syndrome(ex, lg, row, lane);
-    if (__ballot(S != 0) == 0) return 0;
-    int nerr = -1;
-    // Berlekamp-Massey: lane i holds the coefficients C_i, B_i; the discrepancy and all that follows from it are wave-uniform
-    int C = lane == 0, B = C, L = 0, m = 1, b = 1;
-    for (int n = 0; n < 2 * DD_RS_T; ++n) {
-        const int sv = __shfl(S, (n - lane) & 63, 64);                  // S_(n-i)
-        int d = (lane <= L && lane <= n) ? dd_gf_mul(ex, lg, C, sv) : 0;
-        for (int off = 32; off >= 1; off >>= 1) d ^= __shfl_xor(d, off, 64);
-        d = __builtin_amdgcn_readfirstlane(d);
-        const int Bs = __shfl(B, (lane - m) & 63, 64);                  // B_(i-m)
-        if (d == 0) {
-            ++m;
-            continue;
-        }
-        const int coef = ex[lg[d] + 255 - lg[b]];
-        const int T = C;
-        C ^= (lane >= m && lane <= 2 * DD_RS_T) ? dd_gf_mul(ex, lg, coef, Bs) : 0;
-        if (2 * L <= n) {
-            L = n + 1 - L;
-            B = T;
-            b = d;
-            m = 1;
-        } else {
-            ++m;
-        }
-    }
-    const unsigned long long nz = __ballot(C != 0 && lane <= 2 * DD_RS_T);        // bit 0 is set: C_0 = 1
-    if (L <= DD_RS_T && 63 - __clzll((long long)nz) == L) {
-        int lam[DD_RS_T + 1], om[DD_RS_T];
-        for (int k = 0; k <= DD_RS_T; ++k) lam[k] = __builtin_amdgcn_readlane(C, k);
-        // Omega = S Lambda mod x^32, of degree < L <= 16: lane k < 16 forms Omega_k
-        int mine = 0;
-        for (int i = 0; i <= DD_RS_T; ++i) {
-            const int sv = __shfl(S, (lane - i) & 63, 64);
-            mine ^= (i <= lane && lane < DD_RS_T) ? dd_gf_mul(ex, lg, lam[i], sv) : 0;
-        }
-        for (int k = 0; k < DD_RS_T; ++k) om[k] = __builtin_amdgcn_readlane(mine, k);
-        int roots = 0;
-        bool bad = false;                                                        // a root with value 0, or at a shortened position
-        for (int q = 0; q < 4; ++q) {
-            const bool in = pos[q] < DD_RS_N;
-            const int lX = in ? (DD_RS_BETA * (254 - pos[q])) % 255 : 0;         // position i has locator X = beta^(254 - i)
-            const int lx = (255 - lX) % 255, lx2 = (2 * lx) % 255;               // X^-1 and its square
-            int v = lam[DD_RS_T];
-            for (int k = DD_RS_T - 1; k >= 0; --k) v = dd_gf_mul_log(ex, lg, v, lx) ^ lam[k];
-            const bool root = in && v == 0;
-            int num = om[DD_RS_T - 1];
-            for (int k = DD_RS_T - 2; k >= 0; --k) num = dd_gf_mul_log(ex, lg, num, lx) ^ om[k];
-            int den = lam[DD_RS_T - 1];                                          // Lambda'(x): the odd terms, one degree down
-            for (int k = DD_RS_T - 3; k >= 1; k -= 2) den = dd_gf_mul_log(ex, lg, den, lx2) ^ lam[k];
-            // the value X^(1 - 112) Omega(X^-1) / Lambda'(X^-1); -111 = 144 modulo 255
-            const int e = (num != 0 && den != 0) ? ex[(lg[num] + 255 - lg[den] + (lX * 144) % 255) % 255] : 0;
-            roots += __popcll(__ballot(root));
-            bad = bad || __ballot(root && (e == 0 || pos[q] < DD_FCF_RS_PAD)) != 0;
-            if (root) out[q] = got[q] ^ e;
-        }
-        bool good = roots == L && !bad;
-        if (good) {
-            // the corrected word's syndromes, from the wave's own row: the stores are ordered before the loads within the wave
-            for (int q = 0; q < 4; ++q)
-                if (pos[q] < DD_RS_N) row[1 + pos[q]] = (uint8_t)out[q];
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            good = __ballot(dd_rs_syndrome(ex, lg, row, lane) != 0) == 0;
-        }
-        if (good) nerr = L;
-    }
-    if (nerr < 0)
-        for (int q = 0; q < 4; ++q) out[q] = got[q];
-    return nerr;
-}
-
 // Frame blockIdx.x, codeword w = the wave: row[1 + i] = byte i of the (255,223) word, 0 for i < 95 and block[w + 2 (i - 95)] after.
-// As in k_lrpt_rs there is NO workgroup barrier below the staging barrier.
+// A root among the 95 would put a non-zero byte where the shortened code has none.  dd_rs_wave's rule holds below the staging barrier.
 __global__ void __launch_bounds__(128) k_fc_rs(const uint8_t* __restrict__ blocks, uint8_t* __restrict__ frames, int* __restrict__ errors) {
     __shared__ uint8_t ex[512];
     __shared__ uint8_t lg[256];
@@ -285,7 +168,7 @@ __global__ void __launch_bounds__(128) k_fc_rs(const uint8_t* __restrict__ block
         got[q] = pos[q] < DD_RS_N ? row[1 + pos[q]] : 0;
         out[q] = got[q];
     }
-    const int nerr = dd_fc_rs_wave(ex, lg, row, lane, pos, got, out);
+    const int nerr = dd_rs_wave(ex, lg, row, lane, pos, got, out, DD_FCF_RS_PAD);
     uint8_t* dst = frames + f * DD_FCF_FRAME + w;
     for (int q = 0; q < 4; ++q) {
         const int k = pos[q] - DD_FCF_RS_PAD;
@@ -327,7 +210,7 @@ extern "C" int dd_fc_viterbi(const int8_t* D, int64_t m, const int64_t* frames_h
         DD_REQUIRE(inv == 0 || inv == 1, "dd_fc_viterbi: polarity outside 0..1");
         DD_REQUIRE(p >= 0 && p <= m - DD_FCF_SPAN, "dd_fc_viterbi: frame outside D");
     }
-    return dd_lrpt_with_spans(frames_host, nframes, "dd_fc_viterbi", stream, [&](const int64_t* d) {
+    return dd_with_spans(frames_host, nframes, "dd_fc_viterbi", stream, [&](const int64_t* d) {
         hipLaunchKernelGGL(k_fc_viterbi, dim3((unsigned)nframes), dim3(64), 0, dd_stream(stream), D, d, blocks, corrected);
     });
 }

@@ -1,8 +1,9 @@
 // The LRPT modes of the Meteor-M N2-x satellites, from soft symbols (beyond the reference; DESIGN.md section 4.18 defines every
 // stage bit for bit, lrpt.py restates it in NumPy), included by dd_afsk.hip after dd_lrpt.h.  All arithmetic is integer.
 //
-//   k_lrpt_asm_t        -- k_lrpt_asm with the encoded marker's I and Q halves as arguments (the NRZ-M template)
-//   k_lrpt_finish_nrzm  -- k_lrpt_finish for a differential stream: the frame's bits are d[i] = v[i] ^ v[i-1] of the Viterbi bits
+// The marker search against the NRZ-M template and the frame finish of a differential stream are dd_lrpt.h's k_lrpt_asm_t and
+// k_lrpt_finish<true>; their entry points are here.
+//
 //   k_lrpt_deint_scores -- the 8-bit marker 0x27 against the hard bits at every symbol under the eight hypotheses, summed per
 //                          (segment, symbol mod 40, hypothesis)
 //   k_lrpt_deinterleave -- the gather through the convolutional interleaver: marker symbols dropped, one output pair per lane
@@ -15,89 +16,7 @@
 #define DD_LRPT_MARK_I 0x5u           // the marker 0x27 = 0 0 1 0 0 1 1 1: its even bits (I rail) and its odd bits (Q rail),
 #define DD_LRPT_MARK_Q 0x3u           // first symbol in bit 3
 
-// k_lrpt_asm's search against any 64-bit code word: ei, eq = the (c1, c2) halves of its 32 symbols, first symbol in bit 31.
-// (k_lrpt_asm itself keeps its compile-time word: its code object is the parent's.)
-__global__ void __launch_bounds__(256) k_lrpt_asm_t(const char2* __restrict__ soft, int64_t nsym, uint32_t ei, uint32_t eq, int min_score,
-                                                     int64_t cap, int64_t* __restrict__ cand, unsigned long long* __restrict__ count) {
-    __shared__ uint8_t sg[256 + 31];
-    const int64_t p0 = (int64_t)blockIdx.x * 256;
-    for (int i = threadIdx.x; i < 256 + 31; i += 256) {
-        uint8_t v = 0;
-        if (p0 + i < nsym) {
-            const char2 s = soft[p0 + i];
-            v = (uint8_t)((s.x > 0) | ((s.y > 0) << 1) | ((s.x < 0) << 2) | ((s.y < 0) << 3));
-        }
-        sg[i] = v;
-    }
-    __syncthreads();
-    const int64_t p = p0 + threadIdx.x;
-    if (p + 32 > nsym) return;
-    uint32_t m[4] = {0, 0, 0, 0};             // per sign bit: the 32 symbols from p, the first in bit 31
-    for (int k = 0; k < 32; ++k) {
-        const uint32_t v = sg[threadIdx.x + k];
-        for (int q = 0; q < 4; ++q) m[q] = (m[q] << 1) | ((v >> q) & 1);
-    }
-    for (int h = 0; h < 8; ++h) {
-        const int r = h & 3;
-        const uint32_t x = r == 0 ? m[0] : (r == 1 ? m[3] : (r == 2 ? m[2] : m[1]));
-        const uint32_t y = r == 0 ? m[1] : (r == 1 ? m[0] : (r == 2 ? m[3] : m[2]));
-        const uint32_t hi = (h & 4) ? y : x, hq = (h & 4) ? x : y;
-        const int score = __popc(~(hi ^ ei) & DD_LRPT_SCORED) + __popc(~(hq ^ eq) & DD_LRPT_SCORED);
-        if (score >= min_score) {
-            const unsigned long long c = atomicAdd(count, 1ull);
-            if ((int64_t)c < cap) {
-                cand[3 * c] = p;
-                cand[3 * c + 1] = h;
-                cand[3 * c + 2] = score;
-            }
-        }
-    }
-}
-
-// one workgroup per frame, as k_lrpt_finish: fr = the 1024 Viterbi bytes v, dd = the differentially decoded bytes (bit 0 of the frame
-// set to 0: its neighbour lies in another decode span).  The re-encode count is taken from v, everything else from d.
-__global__ void __launch_bounds__(256) k_lrpt_finish_nrzm(const uint8_t* __restrict__ bits, const char2* __restrict__ soft,
-                                                           const int64_t* __restrict__ spans, const DDLrptPn pn,
-                                                           uint8_t* __restrict__ bodies, int* __restrict__ info) {
-    __shared__ uint8_t fr[DD_LRPT_FRAME / 8];
-    __shared__ uint8_t dd[DD_LRPT_FRAME / 8];
-    __shared__ int diff;
-    const int tid = threadIdx.x;
-    const int64_t f = blockIdx.x;
-    const int64_t p = spans[2 * f];
-    const int h = (int)spans[2 * f + 1];
-    for (int i = tid; i < DD_LRPT_FRAME / 8; i += 256) fr[i] = bits[f * (DD_LRPT_FRAME / 8) + i];
-    if (tid == 0) diff = 0;
-    __syncthreads();
-    for (int i = tid; i < DD_LRPT_FRAME / 8; i += 256) {
-        const uint32_t v = fr[i];
-        const uint32_t before = i ? (uint32_t)(fr[i - 1] & 1) << 7 : (v & 0x80u);      // v[8i - 1]; for i = 0 the bit itself: d[0] = 0
-        dd[i] = (uint8_t)(v ^ ((v >> 1) | before));
-    }
-    int mine = 0;
-    for (int t = 6 + tid; t < DD_LRPT_FRAME; t += 256) {
-        int r = 0;
-        for (int j = 0; j < 7; ++j) {
-            const int u = t - 6 + j;
-            r |= ((fr[u >> 3] >> (7 - (u & 7))) & 1) << j;
-        }
-        const char2 s = soft[p + t];
-        int a, b;
-        dd_lrpt_hyp(s.x, s.y, h, a, b);
-        mine += ((__popc(r & DD_LRPT_G1) & 1) != (a > 0)) + ((__popc(r & DD_LRPT_G2) & 1) != (b > 0));
-    }
-    atomicAdd(&diff, mine);
-    __syncthreads();
-    for (int i = tid; i < DD_LRPT_BODY; i += 256) bodies[f * DD_LRPT_BODY + i] = dd[4 + i] ^ pn.b[i % 255];
-    if (tid == 0) {
-        const uint32_t head = ((uint32_t)dd[0] << 24) | ((uint32_t)dd[1] << 16) | ((uint32_t)dd[2] << 8) | dd[3];
-        info[3 * f] = __popc((head ^ DD_LRPT_ASM) & 0x7FFFFFFFu);     // bits 1..31
-        info[3 * f + 1] = diff;
-        info[3 * f + 2] = (dd[5] ^ pn.b[1]) & 0x3F;
-    }
-}
-
-// One symbol q per lane; the workgroup's 256 + 3 symbols are staged as k_lrpt_asm's four sign bits.  A lane whose marker fits
+// One symbol q per lane; the workgroup's 256 + 3 symbols are staged as four sign bits each.  A lane whose marker fits
 // (q + 4 <= nsym) scores its 8 hard bits under each hypothesis and adds the score into [q / (40 seg)][q % 40][h].  The lanes of the
 // workgroup's first segment add into the 320 LDS bins, flushed with one global atomic per non-zero bin; a lane of a later segment
 // (seg < 7: a segment shorter than the workgroup) adds to global memory itself.  Integer adds: the result does not depend on order.
@@ -107,31 +26,19 @@ __global__ void __launch_bounds__(256) k_lrpt_deint_scores(const char2* __restri
     __shared__ int bins[DD_LRPT_PERIOD * 8];
     const int tid = threadIdx.x;
     const int64_t p0 = (int64_t)blockIdx.x * 256;
-    for (int i = tid; i < 256 + DD_LRPT_MARK_SYMS - 1; i += 256) {
-        uint8_t v = 0;
-        if (p0 + i < nsym) {
-            const char2 s = soft[p0 + i];
-            v = (uint8_t)((s.x > 0) | ((s.y > 0) << 1) | ((s.x < 0) << 2) | ((s.y < 0) << 3));
-        }
-        sg[i] = v;
-    }
+    dd_lrpt_stage_signs(soft, nsym, p0, 256 + DD_LRPT_MARK_SYMS - 1, sg);
     for (int i = tid; i < DD_LRPT_PERIOD * 8; i += 256) bins[i] = 0;
     __syncthreads();
     const int64_t seg0 = p0 / seglen;
     const int64_t q = p0 + tid;
     if (q + DD_LRPT_MARK_SYMS <= nsym) {
-        uint32_t m[4] = {0, 0, 0, 0};         // per sign bit: the 4 symbols from q, the first in bit 3
-        for (int k = 0; k < DD_LRPT_MARK_SYMS; ++k) {
-            const uint32_t v = sg[tid + k];
-            for (int b = 0; b < 4; ++b) m[b] = (m[b] << 1) | ((v >> b) & 1);
-        }
+        uint32_t m[4];                        // per sign bit: the 4 symbols from q, the first in bit 3
+        dd_lrpt_sign_masks(sg + tid, DD_LRPT_MARK_SYMS, m);
         const int64_t sgm = q / seglen;
         const int slot = (int)(q % DD_LRPT_PERIOD) * 8;
         for (int h = 0; h < 8; ++h) {
-            const int r = h & 3;
-            const uint32_t x = r == 0 ? m[0] : (r == 1 ? m[3] : (r == 2 ? m[2] : m[1]));
-            const uint32_t y = r == 0 ? m[1] : (r == 1 ? m[0] : (r == 2 ? m[3] : m[2]));
-            const uint32_t hi = (h & 4) ? y : x, hq = (h & 4) ? x : y;
+            uint32_t hi, hq;
+            dd_lrpt_hyp_hard(m, h, hi, hq);
             const int score = __popc(~(hi ^ DD_LRPT_MARK_I) & 0xFu) + __popc(~(hq ^ DD_LRPT_MARK_Q) & 0xFu);
             if (sgm == seg0) atomicAdd(&bins[slot + h], score);
             else if (score) atomicAdd(&scores[sgm * (DD_LRPT_PERIOD * 8) + slot + h], score);
@@ -187,34 +94,12 @@ extern "C" int dd_lrpt_restagger(const int8_t* soft, int64_t nsym, int s, int8_t
 
 extern "C" int dd_lrpt_asm_search_t(const int8_t* soft, int64_t nsym, unsigned long long encoded, int min_score, int64_t cap, int64_t* cand,
                                     unsigned long long* count, void* stream) {
-    DD_REQUIRE(nsym >= 0 && cap >= 0 && count != nullptr, "dd_lrpt_asm_search_t: sizes");
-    DD_HIP_CHECK(hipMemsetAsync(count, 0, sizeof(unsigned long long), dd_stream(stream)));
-    if (nsym < 32) return DD_OK;
-    DD_REQUIRE(soft != nullptr && (cap == 0 || cand != nullptr), "dd_lrpt_asm_search_t: null buffer");
-    uint32_t ei = 0, eq = 0;
-    for (int k = 0; k < 32; ++k) {
-        ei = (ei << 1) | (uint32_t)((encoded >> (63 - 2 * k)) & 1);
-        eq = (eq << 1) | (uint32_t)((encoded >> (62 - 2 * k)) & 1);
-    }
-    hipLaunchKernelGGL(k_lrpt_asm_t, dim3((unsigned)((nsym - 31 + 255) / 256)), dim3(256), 0, dd_stream(stream), (const char2*)soft, nsym,
-                       ei, eq, min_score, cap, cand, count);
-    DD_LAUNCH_CHECK();
-    return DD_OK;
+    return dd_lrpt_asm_run("dd_lrpt_asm_search_t", soft, nsym, encoded, min_score, cap, cand, count, stream);
 }
 
 extern "C" int dd_lrpt_finish_nrzm(const uint8_t* bits_packed, const int8_t* soft, int64_t nsym, const int64_t* spans_host, int64_t nspans,
                                    uint8_t* bodies, int32_t* info, void* stream) {
-    DD_REQUIRE(nsym >= 0 && nspans >= 0 && nspans <= 0x7fffffff, "dd_lrpt_finish_nrzm: sizes");
-    if (nspans == 0) return DD_OK;
-    DD_REQUIRE(bits_packed != nullptr && soft != nullptr && spans_host != nullptr && bodies != nullptr && info != nullptr,
-               "dd_lrpt_finish_nrzm: null buffer");
-    const int rc = dd_lrpt_check_spans(spans_host, nspans, DD_LRPT_FRAME, nsym, "dd_lrpt_finish_nrzm");
-    if (rc != DD_OK) return rc;
-    const DDLrptPn pn = dd_lrpt_pn();
-    return dd_lrpt_with_spans(spans_host, nspans, "dd_lrpt_finish_nrzm", stream, [&](const int64_t* d) {
-        hipLaunchKernelGGL(k_lrpt_finish_nrzm, dim3((unsigned)nspans), dim3(256), 0, dd_stream(stream), bits_packed, (const char2*)soft, d,
-                           pn, bodies, info);
-    });
+    return dd_lrpt_finish_run("dd_lrpt_finish_nrzm", true, bits_packed, soft, nsym, spans_host, nspans, bodies, info, stream);
 }
 
 extern "C" int dd_lrpt_deint_scores(const int8_t* soft, int64_t nsym, int64_t seg, int32_t* scores, void* stream) {

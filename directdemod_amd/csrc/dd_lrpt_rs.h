@@ -1,9 +1,11 @@
 // Meteor-M2 LRPT: Reed-Solomon (255,223) correction of a frame's four interleaved codewords (DESIGN.md section 4.15 defines the
 // field, the code and the decoder's result; lrpt.py restates them in NumPy), included by dd_afsk.hip after dd_lrpt.h.
 //
-//   k_lrpt_rs  -- one workgroup per frame, one wave per codeword: syndromes, the all-zero exit, Berlekamp-Massey with a lane per
-//                 locator coefficient, a search of the 255 positions with a lane per position, Forney's value in the same lane,
-//                 and the corrected word's syndromes before anything is written
+//   dd_rs_wave -- one wave decodes one codeword: syndromes, the all-zero exit, Berlekamp-Massey with a lane per locator
+//                 coefficient, a search of the 255 positions with a lane per position, Forney's value in the same lane, and the
+//                 corrected word's syndromes before anything is written; k_fc_rs (dd_funcube_frames.h) decodes its shortened
+//                 words through it too
+//   k_lrpt_rs  -- one workgroup per frame, one wave per codeword
 #pragma once
 
 #define DD_RS_N 255
@@ -56,8 +58,89 @@ __device__ __forceinline__ int dd_rs_syndrome(const uint8_t* ex, const uint8_t* 
     return lane < 32 ? (dd_gf_mul_log(ex, lg, hi, (lr * 128) % 255) ^ lo) : 0;
 }
 
-// Frame blockIdx.x.  After the staging barrier the four waves share nothing but the read-only tables: a clean codeword leaves at
-// the all-zero test while a damaged one runs on, so there is NO workgroup barrier below the first -- only wave-level operations.
+// One wave, one codeword: row[0] = 0 and row[1 + i] = byte i of the wave's own 256-byte LDS row; pos[q] = lane + 64 q are the lane's
+// positions, got[q] the bytes received there (0 at position 255) and out[] enters equal to got[].  Returns the bytes changed (0..16)
+// with the corrected bytes in out[], or -1 with out[] = got[].  A root at a position below first_valid rejects the word: a shortened
+// code has no non-zero byte there.
+// The waves of a workgroup share nothing but the read-only tables, and a clean codeword leaves at the all-zero test while a damaged
+// one runs on: there is NO workgroup barrier in here, nor in a caller below its staging barrier -- only wave-level operations.
+__device__ __forceinline__ int dd_rs_wave(const uint8_t* ex, const uint8_t* lg, uint8_t* row, int lane, const int (&pos)[4],
+                                          const int (&got)[4], int (&out)[4], int first_valid) {
+    const int S = dd_rs_syndrome(ex, lg, row, lane);
+    if (__ballot(S != 0) == 0) return 0;
+    int nerr = -1;
+    // Berlekamp-Massey: lane i holds the coefficients C_i, B_i; the discrepancy and all that follows from it are wave-uniform
+    int C = lane == 0, B = C, L = 0, m = 1, b = 1;
+#pragma unroll                                                          // all 32: n becomes a constant in the lane tests and shuffles
+    for (int n = 0; n < 2 * DD_RS_T; ++n) {
+        const int sv = __shfl(S, (n - lane) & 63, 64);                  // S_(n-i)
+        int d = (lane <= L && lane <= n) ? dd_gf_mul(ex, lg, C, sv) : 0;
+        for (int off = 32; off >= 1; off >>= 1) d ^= __shfl_xor(d, off, 64);
+        d = __builtin_amdgcn_readfirstlane(d);
+        const int Bs = __shfl(B, (lane - m) & 63, 64);                  // B_(i-m)
+        if (d == 0) {
+            ++m;
+            continue;
+        }
+        const int coef = ex[lg[d] + 255 - lg[b]];
+        const int T = C;
+        C ^= (lane >= m && lane <= 2 * DD_RS_T) ? dd_gf_mul(ex, lg, coef, Bs) : 0;
+        if (2 * L <= n) {
+            L = n + 1 - L;
+            B = T;
+            b = d;
+            m = 1;
+        } else {
+            ++m;
+        }
+    }
+    const unsigned long long nz = __ballot(C != 0 && lane <= 2 * DD_RS_T);        // bit 0 is set: C_0 = 1
+    if (L <= DD_RS_T && 63 - __clzll((long long)nz) == L) {
+        int lam[DD_RS_T + 1], om[DD_RS_T];
+        for (int k = 0; k <= DD_RS_T; ++k) lam[k] = __builtin_amdgcn_readlane(C, k);
+        // Omega = S Lambda mod x^32, of degree < L <= 16: lane k < 16 forms Omega_k
+        int mine = 0;
+        for (int i = 0; i <= DD_RS_T; ++i) {
+            const int sv = __shfl(S, (lane - i) & 63, 64);
+            mine ^= (i <= lane && lane < DD_RS_T) ? dd_gf_mul(ex, lg, lam[i], sv) : 0;
+        }
+        for (int k = 0; k < DD_RS_T; ++k) om[k] = __builtin_amdgcn_readlane(mine, k);
+        int roots = 0;
+        bool bad = false;                                                        // a root with value 0, or below first_valid
+        for (int q = 0; q < 4; ++q) {
+            const bool in = pos[q] < DD_RS_N;
+            const int lX = in ? (DD_RS_BETA * (254 - pos[q])) % 255 : 0;         // position i has locator X = beta^(254 - i)
+            const int lx = (255 - lX) % 255, lx2 = (2 * lx) % 255;               // X^-1 and its square
+            int v = lam[DD_RS_T];
+            for (int k = DD_RS_T - 1; k >= 0; --k) v = dd_gf_mul_log(ex, lg, v, lx) ^ lam[k];
+            const bool root = in && v == 0;
+            int num = om[DD_RS_T - 1];
+            for (int k = DD_RS_T - 2; k >= 0; --k) num = dd_gf_mul_log(ex, lg, num, lx) ^ om[k];
+            int den = lam[DD_RS_T - 1];                                          // Lambda'(x): the odd terms, one degree down
+            for (int k = DD_RS_T - 3; k >= 1; k -= 2) den = dd_gf_mul_log(ex, lg, den, lx2) ^ lam[k];
+            // the value X^(1 - 112) Omega(X^-1) / Lambda'(X^-1); -111 = 144 modulo 255
+            const int e = (num != 0 && den != 0) ? ex[(lg[num] + 255 - lg[den] + (lX * 144) % 255) % 255] : 0;
+            roots += __popcll(__ballot(root));
+            bad = bad || __ballot(root && (e == 0 || pos[q] < first_valid)) != 0;
+            if (root) out[q] = got[q] ^ e;
+        }
+        bool good = roots == L && !bad;
+        if (good) {
+            // the corrected word's syndromes, from the wave's own row: the stores are ordered before the loads within the wave
+            for (int q = 0; q < 4; ++q)
+                if (pos[q] < DD_RS_N) row[1 + pos[q]] = (uint8_t)out[q];
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            good = __ballot(dd_rs_syndrome(ex, lg, row, lane) != 0) == 0;
+        }
+        if (good) nerr = L;
+    }
+    if (nerr < 0)
+        for (int q = 0; q < 4; ++q) out[q] = got[q];
+    return nerr;
+}
+
+// Frame blockIdx.x, codeword w = the wave: body byte i is byte i / 4 of codeword i % 4
 __global__ void __launch_bounds__(256) k_lrpt_rs(const uint8_t* __restrict__ bodies, uint8_t* __restrict__ fixed, int* __restrict__ errors) {
     __shared__ uint8_t ex[512];
     __shared__ uint8_t lg[256];
@@ -72,84 +155,13 @@ __global__ void __launch_bounds__(256) k_lrpt_rs(const uint8_t* __restrict__ bod
     __syncthreads();
 
     uint8_t* row = cw[w];
-    int pos[4], got[4], out[4];                         // lane's positions lane + 64 q, the received bytes, what leaves
+    int pos[4], got[4], out[4];
     for (int q = 0; q < 4; ++q) {
         pos[q] = lane + 64 * q;
         got[q] = pos[q] < DD_RS_N ? row[1 + pos[q]] : 0;
         out[q] = got[q];
     }
-    const int S = dd_rs_syndrome(ex, lg, row, lane);
-    int nerr = 0;
-    if (__ballot(S != 0) != 0) {
-        nerr = -1;
-        // Berlekamp-Massey: lane i holds the coefficients C_i, B_i; the discrepancy and all that follows from it are wave-uniform
-        int C = lane == 0, B = C, L = 0, m = 1, b = 1;
-        for (int n = 0; n < 2 * DD_RS_T; ++n) {
-            const int sv = __shfl(S, (n - lane) & 63, 64);                  // S_(n-i)
-            int d = (lane <= L && lane <= n) ? dd_gf_mul(ex, lg, C, sv) : 0;
-            for (int off = 32; off >= 1; off >>= 1) d ^= __shfl_xor(d, off, 64);
-            d = __builtin_amdgcn_readfirstlane(d);
-            const int Bs = __shfl(B, (lane - m) & 63, 64);                  // B_(i-m)
-            if (d == 0) {
-                ++m;
-                continue;
-            }
-            const int coef = ex[lg[d] + 255 - lg[b]];
-            const int T = C;
-            C ^= (lane >= m && lane <= 2 * DD_RS_T) ? dd_gf_mul(ex, lg, coef, Bs) : 0;
-            if (2 * L <= n) {
-                L = n + 1 - L;
-                B = T;
-                b = d;
-                m = 1;
-            } else {
-                ++m;
-            }
-        }
-        const unsigned long long nz = __ballot(C != 0 && lane <= 2 * DD_RS_T);        // bit 0 is set: C_0 = 1
-        if (L <= DD_RS_T && 63 - __clzll((long long)nz) == L) {
-            int lam[DD_RS_T + 1], om[DD_RS_T];
-            for (int k = 0; k <= DD_RS_T; ++k) lam[k] = __builtin_amdgcn_readlane(C, k);
-            // Omega = S Lambda mod x^32, of degree < L <= 16: lane k < 16 forms Omega_k
-            int mine = 0;
-            for (int i = 0; i <= DD_RS_T; ++i) {
-                const int sv = __shfl(S, (lane - i) & 63, 64);
-                mine ^= (i <= lane && lane < DD_RS_T) ? dd_gf_mul(ex, lg, lam[i], sv) : 0;
-            }
-            for (int k = 0; k < DD_RS_T; ++k) om[k] = __builtin_amdgcn_readlane(mine, k);
-            int roots = 0;
-            bool zero = false;
-            for (int q = 0; q < 4; ++q) {
-                const bool in = pos[q] < DD_RS_N;
-                const int lX = in ? (DD_RS_BETA * (254 - pos[q])) % 255 : 0;             // position i has locator X = beta^(254 - i)
-                const int lx = (255 - lX) % 255, lx2 = (2 * lx) % 255;                   // X^-1 and its square
-                int v = lam[DD_RS_T];
-                for (int k = DD_RS_T - 1; k >= 0; --k) v = dd_gf_mul_log(ex, lg, v, lx) ^ lam[k];
-                const bool root = in && v == 0;
-                int num = om[DD_RS_T - 1];
-                for (int k = DD_RS_T - 2; k >= 0; --k) num = dd_gf_mul_log(ex, lg, num, lx) ^ om[k];
-                int den = lam[DD_RS_T - 1];                                              // Lambda'(x): the odd terms, one degree down
-                for (int k = DD_RS_T - 3; k >= 1; k -= 2) den = dd_gf_mul_log(ex, lg, den, lx2) ^ lam[k];
-                // the value X^(1 - 112) Omega(X^-1) / Lambda'(X^-1); -111 = 144 modulo 255
-                const int e = (num != 0 && den != 0) ? ex[(lg[num] + 255 - lg[den] + (lX * 144) % 255) % 255] : 0;
-                roots += __popcll(__ballot(root));
-                zero = zero || __ballot(root && e == 0) != 0;
-                if (root) out[q] = got[q] ^ e;
-            }
-            bool good = roots == L && !zero;
-            if (good) {
-                // the corrected word's syndromes, from the wave's own row: the stores are ordered before the loads within the wave
-                for (int q = 0; q < 4; ++q)
-                    if (pos[q] < DD_RS_N) row[1 + pos[q]] = (uint8_t)out[q];
-                __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                good = __ballot(dd_rs_syndrome(ex, lg, row, lane) != 0) == 0;
-            }
-            if (good) nerr = L;
-        }
-        if (nerr < 0)
-            for (int q = 0; q < 4; ++q) out[q] = got[q];
-    }
+    const int nerr = dd_rs_wave(ex, lg, row, lane, pos, got, out, 0);
     uint8_t* dst = fixed + f * DD_LRPT_BODY + w;
     for (int q = 0; q < 4; ++q)
         if (pos[q] < DD_RS_N) dst[4 * pos[q]] = (uint8_t)out[q];
