@@ -197,6 +197,9 @@ SIGNATURES = {
     "dd_sstv_runs": (_int, [_p, _i64, _int, _i64, _i64, _p, _i64, _pi64, _p]),
     "dd_sstv_pixels": (_int, [_p, _i64, _p, _i64, _int, C.c_double, C.c_double, _p, _pi64, _p]),
     "dd_sstv_color": (_int, [_p, _i64, _int, _p, _p]),
+    "dd_adsb_candidates": (_int, [_p, _i64, _i64, _int, _p, _i64, _pi64, _p]),
+    "dd_adsb_demod": (_int, [_p, _i64, _i64, _int, _p, _i64, _p, _p, _p, _p]),
+    "dd_debug_adsb_chips": (_int, [_p, _i64, _i64, _int, _p, _i64, _p, _p]),
     "dd_lrpt_rs": (_int, [_p, _i64, _p, _p, _p]),
     "dd_lrpt_jpeg": (_int, [_p, _p, _p, _p, _i64, _i64, _p, _p, _p]),
     "dd_funcube_mix_ramp": (_int, [_p, _p, _i64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _p, _p]),

@@ -91,6 +91,9 @@ extern "C" int dd_afsk_edges_f64(const double* binary_filter, int64_t n, int spb
 // Slow-scan television, PD modes: lag product, tone classes, windowed runs, pixels, colour
 #include "dd_sstv.h"
 
+// 1090 MHz Mode S / ADS-B squitters: preamble candidates, bit decisions, CRC and one-bit repair, all integer
+#include "dd_adsb.h"
+
 // Meteor-M2 QPSK sync detection (decode_meteorm2.py:229-324)
 #include "dd_meteor.h"
 

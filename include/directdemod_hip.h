@@ -568,6 +568,25 @@ int dd_sstv_pixels(const void* d, int64_t n, const double* t0, int64_t nseg, int
                    int64_t* empty_host, void* stream);
 int dd_sstv_color(const uint8_t* levels, int64_t npairs, int W, uint8_t* rgb, void* stream);
 
+/* ---- 1090 MHz Mode S / ADS-B squitters (beyond the reference; DESIGN.md section 4.22 defines every stage) -------------------------
+ * All integer; adsb.py restates every entry in NumPy.  iq = n raw uint8 (I, Q) pairs on the device, n < 2^28; rate = samples per
+ * second, 2 000 000 .. 20 000 000; phases = candidates per sample, 1, 2, 4 or 8.  Candidate k starts k / phases samples into the
+ * recording; its chip c covers rate / 2 000 000 samples from k / phases + c rate / 2 000 000 on; a chip's energy is the sum of
+ * overlap * ((2 I - 255)^2 + (2 Q - 255)^2) with the overlaps in units of gcd(2 000 000 / phases, rate) / 2 000 000 sample.  The
+ * candidates are the k >= 0 whose 240 chips end inside the recording.
+ * dd_adsb_candidates -- the candidates that pass the preamble test (E0 > E1 < E2 > E3, E6 < E7 > E8 < E9 > E10, and 6 E[q] <
+ *     E0 + E2 + E7 + E9 for q = 4, 5, 11, 12, 13, 14; all strict) in ascending order: list[min(*count_host, cap)], *count_host =
+ *     how many passed.  More than cap: DD_ERR_INVALID with the count filled and nothing written past cap.
+ * dd_adsb_demod -- per listed candidate c < m: bit b = E[16 + 2 b] > E[17 + 2 b], DF = bits 0..4, L = 112 for DF >= 16 else 56,
+ *     rem = the remainder of the L-bit word by 0x1FFF409, score = the sum over b < L of |E[16 + 2 b] - E[17 + 2 b]|; for L = 112
+ *     and DF 17 or 18, a rem equal to the remainder of one lone bit at a position >= 5 gives fixed = that position and flips the
+ *     bit, else fixed = -1.  frames[14 c ..] = the word, zero beyond L; meta[4 c ..] = L, DF, rem, fixed; score[c].  list, frames,
+ *     meta and score are device arrays.  A k that is no candidate of the recording gives zeros and fixed = -1. */
+int dd_adsb_candidates(const void* iq, int64_t n, int64_t rate, int phases, int64_t* list, int64_t cap, int64_t* count_host,
+                       void* stream);
+int dd_adsb_demod(const void* iq, int64_t n, int64_t rate, int phases, const int64_t* list, int64_t m, uint8_t* frames,
+                  int32_t* meta, int64_t* score, void* stream);
+
 /* ---- Funcube BPSK sync detection (decode_funcube.py:148-306) ------------------------------------------------------------
  * dd_funcube_mix_ramp -- dd_meteor_mix with the frequency formed per sample: th = ((w * f[k]) * k) * inv_fs, w = -2 pi,
  *     f[k] = f0 + k * delta (np.arange's fill) clipped to target from above when target > f0, from below otherwise.

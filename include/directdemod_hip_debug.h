@@ -101,6 +101,11 @@ int  dd_debug_sync_prefilter(const double* x_dev, int64_t n, int nwin, const dou
 int  dd_debug_sync_tail(const double* hay_dev, const double* env_dev, int64_t n, int nwin, const double* needle_host, int needle_len,
                         int n_needles, const int* needle_of_window_host, int64_t* peak_host, double* height_host, double* tsync_host,
                         void* stream);
+/* dd_debug_adsb_chips -- the 240 chip energies E_k[0 .. 240) of every listed candidate (the arguments of dd_adsb_demod in
+ *   directdemod_hip.h): energies[240 c ..] for c < m, a device array; a k that is no candidate of the recording gives zeros.  Lets a
+ *   test place a disagreement of dd_adsb_candidates or dd_adsb_demod at one chip. */
+int  dd_debug_adsb_chips(const void* iq, int64_t n, int64_t rate, int phases, const int64_t* list, int64_t m, int64_t* energies,
+                         void* stream);
 
 #ifdef __cplusplus
 }
