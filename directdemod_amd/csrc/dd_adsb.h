@@ -5,7 +5,7 @@
 //
 //   k_adsb_preamble   -- a workgroup stages the power of 256 samples of starts and the preamble's reach in LDS, one thread per
 //                        sample walks its Q candidates' 15 chips, a mask byte per sample and a count per workgroup come out
-//   k_adsb_list       -- the masks' set bits as an ordered candidate list below the capacity (the counts scanned by k_sstv_scan_tops)
+//   k_adsb_list       -- the masks' set bits (those of a keep mask: dd_ais.h lists bit 0 alone) as an ordered candidate list below the capacity (the counts scanned by k_sstv_scan_tops)
 //   k_adsb_demod      -- one wave per listed candidate: 112 bit decisions by ballot, remainder, score, one-bit repair
 //   k_adsb_chips      -- diagnostic: one wave per listed candidate, all 240 chip energies
 #pragma once
@@ -77,12 +77,12 @@ __global__ void __launch_bounds__(DD_ADSB_TILE) k_adsb_preamble(const uint8_t* _
     if (tid == 255) bsum[blockIdx.x] = total;
 }
 
-// list[boff[block] + rank] = k for every set mask bit whose place is below cap: ordered, nothing written past cap
-__global__ void __launch_bounds__(DD_ADSB_TILE) k_adsb_list(const uint8_t* __restrict__ mask, int64_t n, int Q, const int* __restrict__ boff,
-                                                            int64_t* __restrict__ list, int64_t cap) {
+// list[boff[block] + rank] = k for every set mask bit among `keep` whose place is below cap: ordered, nothing written past cap
+__global__ void __launch_bounds__(DD_ADSB_TILE) k_adsb_list(const uint8_t* __restrict__ mask, int64_t n, int Q, uint32_t keep,
+                                                            const int* __restrict__ boff, int64_t* __restrict__ list, int64_t cap) {
     __shared__ int sh[256];
     const int64_t at = (int64_t)blockIdx.x * DD_ADSB_TILE + threadIdx.x;
-    uint32_t m = at < n ? mask[at] : 0u;
+    uint32_t m = at < n ? mask[at] & keep : 0u;
     const int c = __popc(m);
     int64_t place = (int64_t)boff[blockIdx.x] + dd_sstv_scan256(c, sh) - c;
     while (m) {
@@ -255,8 +255,8 @@ extern "C" int dd_adsb_candidates(const void* iq, int64_t n, int64_t rate, int p
     *count_host = total;
     const int64_t kept = total < cap ? total : cap;
     if (kept > 0) {
-        hipLaunchKernelGGL(k_adsb_list, dim3((unsigned)nb), dim3(DD_ADSB_TILE), 0, s, (const uint8_t*)mask, n, phases, (const int*)bsum, list,
-                           kept);
+        hipLaunchKernelGGL(k_adsb_list, dim3((unsigned)nb), dim3(DD_ADSB_TILE), 0, s, (const uint8_t*)mask, n, phases, 0xFFu, (const int*)bsum,
+                           list, kept);
         DD_LAUNCH_CHECK();
     }
     DD_REQUIRE(total <= cap, "dd_adsb_candidates: candidate list too small");

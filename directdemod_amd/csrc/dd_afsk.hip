@@ -94,6 +94,9 @@ extern "C" int dd_afsk_edges_f64(const double* binary_filter, int64_t n, int spb
 // 1090 MHz Mode S / ADS-B squitters: preamble candidates, bit decisions, CRC and one-bit repair, all integer
 #include "dd_adsb.h"
 
+// AIS, 9600 baud GMSK bursts: preamble candidates, HDLC by masks and prefix counts, CRC-16, integer behind the quantiser
+#include "dd_ais.h"
+
 // Meteor-M2 QPSK sync detection (decode_meteorm2.py:229-324)
 #include "dd_meteor.h"
 

@@ -91,13 +91,13 @@ class decode_afsk1200:
         return list(self.__frames)
 
     # ------------------------------------------------------------------ the device pipeline
-    def _audio(self):
-        """decode_afsk1200.py:67-94: chunk loop offsetFreq -> blackmanHarris(151) -> bwLim(bw) -> extend; demod_fm over the whole"""
+    def _baseband(self, taps=151):
+        """decode_afsk1200.py:67-90: chunk loop offsetFreq -> blackmanHarris(151) -> bwLim(bw) -> extend (decode_ais asks for a
+        shorter window at low sample rates)"""
         src = self.__sigsrc
         sig = comm.commSignal(src.sampFreq)
         ck = chunker.chunker(src)
-        bh = filters.blackmanHarris(151)
-        fm = demod_fm.demod_fm()
+        bh = filters.blackmanHarris(taps)
         read = src.read
         if self.__use_raw and hasattr(src, "read_device_raw") and src.read_device_raw(0, 1) is not None:
             read = src.read_device_raw
@@ -107,7 +107,12 @@ class decode_afsk1200:
             c.filter(bh)
             c.bwLim(self.__bw)
             sig.extend(c)
-        sig.funcApply(fm.demod)
+        return sig
+
+    def _audio(self):
+        """decode_afsk1200.py:67-94: the chunk loop, then demod_fm over the whole"""
+        sig = self._baseband()
+        sig.funcApply(demod_fm.demod_fm().demod)
         return sig
 
     def _decode(self):

@@ -307,6 +307,19 @@ class gaussian(filter):
         super(gaussian, self).__init__(np.exp(-k ** 2 / (2.0 * sigma * sigma)), [1], storeState, zeroPhase, initOut)
 
 
+class lowpass(filter):
+    '''EXTENSION (no counterpart in the reference): a Hamming-windowed sinc low-pass of cut-off `cutoff` Hz at `Fs` S/s with unit sum
+    and 2 int(Fs / 2400) + 1 taps.  decode_ais's channel filter at the audio rate (41 taps at 48 kS/s).'''
+
+    def __init__(self, Fs, cutoff, storeState=True, zeroPhase=False, initOut=None):
+        if not 0 < cutoff < Fs / 2.0:
+            raise ValueError("The cut-off must lie between 0 and Fs/2")
+        n = 2 * int(Fs / 2400.0) + 1
+        m = np.arange(n) - (n - 1) // 2
+        h = np.sinc(2.0 * cutoff / Fs * m) * _cosine_sum(n, [0.54, 0.46])
+        super(lowpass, self).__init__(h / h.sum(), [1], storeState, zeroPhase, initOut)
+
+
 class butter(filter):
     '''Butterworth filter (filters.py:232-273).  IIR: a float64 transposed direct form II
     recurrence on the device -- one lane per component for short (audio-rate) inputs, the

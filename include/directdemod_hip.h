@@ -587,6 +587,30 @@ int dd_adsb_candidates(const void* iq, int64_t n, int64_t rate, int phases, int6
 int dd_adsb_demod(const void* iq, int64_t n, int64_t rate, int phases, const int64_t* list, int64_t m, uint8_t* frames,
                   int32_t* meta, int64_t* score, void* stream);
 
+/* ---- AIS, 9600 baud GMSK bursts carrying HDLC frames (beyond the reference; DESIGN.md section 4.23 defines every stage) -----------
+ * ais.py restates every entry in NumPy.  audio = n float64 discriminator outputs (radians per sample) on the device, n < 2^31;
+ * sps = samples per bit, 4 .. 16; w = samples summed per bit value, odd, 1 .. 15.  q[i] = rint(audio[i] * (2^20 / pi)) as an integer
+ * (0 for a NaN and beyond +-2^21), 0 outside the audio; everything behind it is integer.  v(t, k) = the sum of the w samples q
+ * around sample floor(t + (k + 0.5) sps), the product and the sum rounded one by one in float64.  S(t) = v(t, 0) + .. + v(t, 15);
+ * the level of bit k is + when 16 v(t, k) > S(t), strictly.  The template is (- - + +) x 4, seven -, one +: the last 16 training bits
+ * and the start flag after NRZI.  The starts are the t >= 0 with floor(23.5 sps) + w / 2 < n - t.
+ * dd_ais_candidates -- the starts whose 24 levels equal the template, or its negation, in all but at most `slack` places (0 .. 11),
+ *     in ascending order: list[min(*count_host, cap)], *count_host = how many passed.  More than cap: DD_ERR_INVALID with the count
+ *     filled and nothing written past cap.
+ * dd_ais_demod -- per listed start c < m: 1280 levels at k = 24 .., bit i = 1 where level i repeats level i - 1 (NRZI; level -1 is
+ *     template bit 23); e = the start of the first run of six 1s; status 1 (no end flag) without one or when bit e + 6 lies past the
+ *     1280, 2 (abort) when bit e + 6 is 1; the data are the bits before e - 1 less every 0 that follows five 1s; status 3 (stuffing
+ *     violation) when five 1s end at e - 2, 4 (bad length) unless the count is a multiple of 8 and at least 40, 5 (bad CRC) unless
+ *     the CRC-16 register (reflected 0x8408, preset 0xFFFF) over all of them ends at 0xF0B8, else 0 (accepted).
+ *     frames[160 c ..] = the data bits, the first in bit 0 of byte 0 (AIS sends a byte's lowest bit first: these are the message's
+ *     bytes and its FCS), zero beyond the count and for status 1 and 2; meta[4 c ..] = status, bit count, CRC register (status 0 and
+ *     5, else 0), polarity (1 when the levels are nearer the negated template); score[c] = the sum over the template of
+ *     |16 v - S|.  list, frames, meta and score are device arrays.  A start outside [0, n) gives status 1 and zeros. */
+int dd_ais_candidates(const double* audio, int64_t n, double sps, int w, int slack, int64_t* list, int64_t cap, int64_t* count_host,
+                      void* stream);
+int dd_ais_demod(const double* audio, int64_t n, double sps, int w, const int64_t* list, int64_t m, uint8_t* frames, int32_t* meta,
+                 int64_t* score, void* stream);
+
 /* ---- Funcube BPSK sync detection (decode_funcube.py:148-306) ------------------------------------------------------------
  * dd_funcube_mix_ramp -- dd_meteor_mix with the frequency formed per sample: th = ((w * f[k]) * k) * inv_fs, w = -2 pi,
  *     f[k] = f0 + k * delta (np.arange's fill) clipped to target from above when target > f0, from below otherwise.
