@@ -97,6 +97,9 @@ extern "C" int dd_afsk_edges_f64(const double* binary_filter, int64_t n, int spb
 // AIS, 9600 baud GMSK bursts: preamble candidates, HDLC by masks and prefix counts, CRC-16, integer behind the quantiser
 #include "dd_ais.h"
 
+// POCSAG paging, 2-FSK at 512 / 1200 / 2400 baud: sync codeword candidates from an LDS prefix sum, BCH(31,21) two-bit repair per wave
+#include "dd_pocsag.h"
+
 // Meteor-M2 QPSK sync detection (decode_meteorm2.py:229-324)
 #include "dd_meteor.h"
 

@@ -611,6 +611,26 @@ int dd_ais_candidates(const double* audio, int64_t n, double sps, int w, int sla
 int dd_ais_demod(const double* audio, int64_t n, double sps, int w, const int64_t* list, int64_t m, uint8_t* frames, int32_t* meta,
                  int64_t* score, void* stream);
 
+/* ---- POCSAG paging, 2-FSK at 512 / 1200 / 2400 baud (beyond the reference; DESIGN.md section 4.24 defines every stage) ------------
+ * pocsag.py restates every entry in NumPy.  audio, n, q and v(t, k) as for AIS above, with sps = samples per bit, 4 .. 128, and w
+ * odd, 1 .. 77.  S(t) = v(t, 0) + .. + v(t, 31); bit k of the start t is 0 when 32 v(t, k) > S(t), strictly (the higher frequency
+ * is a 0), else 1.  A codeword holds its first-sent bit in bit 31.  The starts are the t >= 0 with floor(31.5 sps) + w / 2 < n - t.
+ * dd_pocsag_candidates -- the starts whose 32 bits equal the frame sync codeword 0x7CD215D8, or its inverse, in all but at most
+ *     `slack` places (0 .. 8), in ascending order: list[min(*count_host, cap)], *count_host = how many passed.  More than cap:
+ *     DD_ERR_INVALID with the count filled and nothing written past cap.
+ * dd_pocsag_batches -- per listed start c < m: the 544 bits k = 0 .. 543 against S(t) of the first 32, inverted when more than 16
+ *     of those differ from the sync codeword (polarity 1).  Codewords 1 .. 16: the syndrome of bits 31 .. 1 modulo x^10 + x^9 + x^8 +
+ *     x^6 + x^5 + x^3 + 1 (0x769); 0: no error there; that of one bit: the bit is flipped; that of two bits: both are flipped; else
+ *     uncorrectable.  Odd parity over the 32 bits after that flips bit 0 and counts as one more error.  A codeword with more than
+ *     `fix` (0 .. 2) errors is uncorrectable.  words[17 c ..] = codeword 0 as received and the others corrected, or as received where
+ *     uncorrectable; errs[17 c ..] = the sync codeword's wrong places, then the errors repaired per codeword, 255 = uncorrectable;
+ *     meta[4 c ..] = status, polarity, how many of the 16 were accepted, errs[17 c]; score[c] = the sum over the sync codeword of
+ *     |32 v - S|.  list, words, errs, meta and score are device arrays.  A start outside [0, n) gives status 1 and zeros. */
+int dd_pocsag_candidates(const double* audio, int64_t n, double sps, int w, int slack, int64_t* list, int64_t cap,
+                         int64_t* count_host, void* stream);
+int dd_pocsag_batches(const double* audio, int64_t n, double sps, int w, int fix, const int64_t* list, int64_t m, uint32_t* words,
+                      uint8_t* errs, int32_t* meta, int64_t* score, void* stream);
+
 /* ---- Funcube BPSK sync detection (decode_funcube.py:148-306) ------------------------------------------------------------
  * dd_funcube_mix_ramp -- dd_meteor_mix with the frequency formed per sample: th = ((w * f[k]) * k) * inv_fs, w = -2 pi,
  *     f[k] = f0 + k * delta (np.arange's fill) clipped to target from above when target > f0, from below otherwise.

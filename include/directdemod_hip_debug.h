@@ -106,6 +106,9 @@ int  dd_debug_sync_tail(const double* hay_dev, const double* env_dev, int64_t n,
  *   test place a disagreement of dd_adsb_candidates or dd_adsb_demod at one chip. */
 int  dd_debug_adsb_chips(const void* iq, int64_t n, int64_t rate, int phases, const int64_t* list, int64_t m, int64_t* energies,
                          void* stream);
+/* dd_debug_pocsag_masks -- the mask byte of every sample that dd_pocsag_candidates lists from (its arguments): mask[n] on the device,
+ *   1 = the sync codeword within `slack` places, 3 = its inverse, 0 otherwise and past the last start. */
+int  dd_debug_pocsag_masks(const double* audio, int64_t n, double sps, int w, int slack, uint8_t* mask, void* stream);
 
 #ifdef __cplusplus
 }
