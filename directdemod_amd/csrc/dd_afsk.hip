@@ -100,6 +100,9 @@ extern "C" int dd_afsk_edges_f64(const double* binary_filter, int64_t n, int spb
 // POCSAG paging, 2-FSK at 512 / 1200 / 2400 baud: sync codeword candidates from an LDS prefix sum, BCH(31,21) two-bit repair per wave
 #include "dd_pocsag.h"
 
+// ACARS, 2400 baud MSK over AM: template candidates from the same LDS prefix sum, parity-guided repair under the CRC-16 per wave
+#include "dd_acars.h"
+
 // Meteor-M2 QPSK sync detection (decode_meteorm2.py:229-324)
 #include "dd_meteor.h"
 

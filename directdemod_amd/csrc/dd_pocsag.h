@@ -60,6 +60,25 @@ __device__ __forceinline__ uint32_t dd_pocsag_scan256(uint32_t v, uint32_t* sh) 
     return v;
 }
 
+// ps[0 .. span) of a workgroup of 256, staged and synchronised, in place into its exclusive wrap-around prefix sum: ps[j] = the sum
+// of the former ps[0 .. j) mod 2^32; synchronised on return.  tops holds 4 values.
+__device__ __forceinline__ void dd_pocsag_prefix256(uint32_t* ps, int span, uint32_t* tops) {
+    const int tid = threadIdx.x;
+    // thread t owns entries [t c, t c + c): c is odd, so a wave's 64 words of one step fall into distinct banks, 32 per lane group
+    const int c = ((span + DD_POCSAG_TILE - 1) / DD_POCSAG_TILE) | 1;
+    const int lo = tid * c < span ? tid * c : span;
+    const int hi = lo + c < span ? lo + c : span;
+    uint32_t own = 0;
+    for (int j = lo; j < hi; ++j) own += ps[j];
+    uint32_t run = dd_pocsag_scan256(own, tops) - own;
+    for (int j = lo; j < hi; ++j) {
+        const uint32_t q = ps[j];
+        ps[j] = run;
+        run += q;
+    }
+    __syncthreads();
+}
+
 __global__ void __launch_bounds__(DD_POCSAG_TILE) k_pocsag_sync(const double* __restrict__ x, int64_t n, const DDPocsagGrid gd,
                                                                 uint8_t* __restrict__ mask, int* __restrict__ bsum) {
     __shared__ uint32_t ps[DD_POCSAG_SPAN];          // first q, then ps[j] = the sum of q over samples first .. first + j - 1 (mod 2^32)
@@ -73,19 +92,7 @@ __global__ void __launch_bounds__(DD_POCSAG_TILE) k_pocsag_sync(const double* __
         ps[j] = (i >= 0 && i < n) ? (uint32_t)dd_ais_q(x[i]) : 0u;
     }
     __syncthreads();
-    // thread t owns entries [t c, t c + c): c is odd, so a wave's 64 words of one step fall into distinct banks, 32 per lane group
-    const int c = ((gd.span + DD_POCSAG_TILE - 1) / DD_POCSAG_TILE) | 1;
-    const int lo = tid * c < gd.span ? tid * c : gd.span;
-    const int hi = lo + c < gd.span ? lo + c : gd.span;
-    uint32_t own = 0;
-    for (int j = lo; j < hi; ++j) own += ps[j];
-    uint32_t run = dd_pocsag_scan256(own, tops) - own;
-    for (int j = lo; j < hi; ++j) {
-        const uint32_t q = ps[j];
-        ps[j] = run;
-        run += q;
-    }
-    __syncthreads();
+    dd_pocsag_prefix256(ps, gd.span, tops);
     const int64_t t = base + tid;
     uint32_t m = 0;
     if (t < gd.nstart) {
@@ -232,17 +239,19 @@ static int dd_pocsag_grid(int64_t n, double sps, int w, int slack, int fix, DDPo
     return 1;
 }
 
-// the masks of every sample into scratch or into mask_out, the list below cap
-static int dd_pocsag_run(const double* audio, int64_t n, const DDPocsagGrid& gd, uint8_t* mask_out, int64_t* list, int64_t cap,
-                         int64_t* count_host, hipStream_t s) {
-    const int64_t nb = (gd.nstart + DD_POCSAG_TILE - 1) / DD_POCSAG_TILE;
+// the masks of every sample into scratch or into mask_out, the list below cap; sync(mask, bsum, nb) launches the kernel that tests
+// the nstart starts, 256 per workgroup, and leaves a mask byte per sample and the passes of each workgroup
+template <class Sync>
+static int dd_pocsag_run(int64_t n, int64_t nstart, uint8_t* mask_out, int64_t* list, int64_t cap, int64_t* count_host, hipStream_t s,
+                         Sync sync) {
+    const int64_t nb = (nstart + DD_POCSAG_TILE - 1) / DD_POCSAG_TILE;
     const size_t bM = mask_out ? 0 : dd_sstv_up16((size_t)n), bB = dd_sstv_up16(((size_t)nb + 1) * 4);
     DDScratchLock scr;
     int rc = scr.get(bM + bB, s);
     if (rc != DD_OK) return rc;
     uint8_t* mask = mask_out ? mask_out : (uint8_t*)scr.ptr;
     int* bsum = (int*)(scr.ptr + bM);
-    hipLaunchKernelGGL(k_pocsag_sync, dim3((unsigned)nb), dim3(DD_POCSAG_TILE), 0, s, audio, n, gd, mask, bsum);
+    sync(mask, bsum, nb);
     DD_LAUNCH_CHECK();
     if (mask_out) {
         DD_HIP_CHECK(hipStreamSynchronize(s));                            // (the scratch is given back on return)
@@ -263,6 +272,12 @@ static int dd_pocsag_run(const double* audio, int64_t n, const DDPocsagGrid& gd,
     return DD_OK;
 }
 
+static auto dd_pocsag_sync_launch(const double* audio, int64_t n, const DDPocsagGrid& gd, hipStream_t s) {
+    return [=](uint8_t* mask, int* bsum, int64_t nb) {
+        hipLaunchKernelGGL(k_pocsag_sync, dim3((unsigned)nb), dim3(DD_POCSAG_TILE), 0, s, audio, n, gd, mask, bsum);
+    };
+}
+
 extern "C" int dd_pocsag_candidates(const double* audio, int64_t n, double sps, int w, int slack, int64_t* list, int64_t cap,
                                     int64_t* count_host, void* stream) {
     DDPocsagGrid gd;
@@ -273,7 +288,8 @@ extern "C" int dd_pocsag_candidates(const double* audio, int64_t n, double sps, 
     if (n == 0) return DD_OK;
     DD_REQUIRE(audio != nullptr && (cap == 0 || list != nullptr), "dd_pocsag_candidates: null buffer");
     if (gd.nstart == 0) return DD_OK;
-    int rc = dd_pocsag_run(audio, n, gd, nullptr, list, cap, count_host, dd_stream(stream));
+    hipStream_t s = dd_stream(stream);
+    int rc = dd_pocsag_run(n, gd.nstart, nullptr, list, cap, count_host, s, dd_pocsag_sync_launch(audio, n, gd, s));
     if (rc != DD_OK) return rc;
     DD_REQUIRE(*count_host <= cap, "dd_pocsag_candidates: candidate list too small");
     return DD_OK;
@@ -301,5 +317,5 @@ extern "C" int dd_debug_pocsag_masks(const double* audio, int64_t n, double sps,
     hipStream_t s = dd_stream(stream);
     DD_HIP_CHECK(hipMemsetAsync(mask, 0, (size_t)n, s));
     if (gd.nstart == 0) return DD_OK;
-    return dd_pocsag_run(audio, n, gd, mask, nullptr, 0, nullptr, s);
+    return dd_pocsag_run(n, gd.nstart, mask, nullptr, 0, nullptr, s, dd_pocsag_sync_launch(audio, n, gd, s));
 }

@@ -631,6 +631,31 @@ int dd_pocsag_candidates(const double* audio, int64_t n, double sps, int w, int 
 int dd_pocsag_batches(const double* audio, int64_t n, double sps, int w, int fix, const int64_t* list, int64_t m, uint32_t* words,
                       uint8_t* errs, int32_t* meta, int64_t* score, void* stream);
 
+/* ---- ACARS on VHF, 2400 baud MSK on 1200 / 2400 Hz over AM (beyond the reference; DESIGN.md section 4.25 defines every stage) -----
+ * acars.py restates every entry in NumPy.  audio = n float64 samples of the AM envelope on the device, n < 2^31; sps = samples per
+ * bit, 8 .. 64; w = samples summed on either side of a bit's end, 1 .. 32.  q[i] = rint(audio[i] * 2^12) as an integer (0 for a NaN
+ * and beyond +-2^21), 0 outside the audio; everything behind it is integer.  B(t, k) = floor(t + (k + 1) sps), the product and the
+ * sum rounded one by one in float64; v(t, k) = (q[B] + .. + q[B + w - 1]) - (q[B - w] + .. + q[B - 1]); bit k of the start t is 1
+ * when v(t, k) > 0, strictly.  The template is 0x54686880, * SYN SYN SOH with each character's lowest bit first and the first-sent
+ * bit in bit 31.  The starts are the t >= 0 with t + floor(32 sps) + w <= n.
+ * dd_acars_candidates -- the starts whose 32 bits equal the template, or its inverse, in all but at most `slack` places (0 .. 5), in
+ *     ascending order: list[min(*count_host, cap)], *count_host = how many passed.  More than cap: DD_ERR_INVALID with the count
+ *     filled and nothing written past cap.
+ * dd_acars_blocks -- per listed start c < m: the 1920 bits k = 32 .. 1951, all inverted when more than 16 of the first 32 differ from
+ *     the template (polarity 1); bit p = k - 32 is bit p mod 8 of character p / 8.  e = the least character index from 12 on that holds
+ *     0x83 or 0x97 with e + 2 <= 239; without one status 2 (no end).  s = the CRC-16 register (reflected 0x8408, preset 0) over
+ *     characters 0 .. e + 2; c = the characters among 0 .. e with an even number of ones.  s = 0: accepted.  Else, with fix >= 1 and
+ *     c = 1, the one bit of that character whose flip clears s is flipped; with fix >= 1 and c = 0 the one such bit of characters
+ *     e + 1 and e + 2; with fix >= 2 and c = 2 the one pair of a bit of the first such character and a bit of the second, when exactly
+ *     one pair clears s; anything else is status 3 (bad block check).  bytes[240 c ..] = the characters, repaired where accepted;
+ *     meta[8 c ..] = status (0 accepted), polarity, the template's wrong places, e (-1 without), c, bits repaired, whether character
+ *     e + 3 is 0x7F, s as received; score[c] = the sum over the template of |v|.  list, bytes, meta and score are device arrays.
+ *     A start outside [0, n) gives status 1, e = -1 and zeros. */
+int dd_acars_candidates(const double* audio, int64_t n, double sps, int w, int slack, int64_t* list, int64_t cap, int64_t* count_host,
+                        void* stream);
+int dd_acars_blocks(const double* audio, int64_t n, double sps, int w, int fix, const int64_t* list, int64_t m, uint8_t* bytes,
+                    int32_t* meta, int64_t* score, void* stream);
+
 /* ---- Funcube BPSK sync detection (decode_funcube.py:148-306) ------------------------------------------------------------
  * dd_funcube_mix_ramp -- dd_meteor_mix with the frequency formed per sample: th = ((w * f[k]) * k) * inv_fs, w = -2 pi,
  *     f[k] = f0 + k * delta (np.arange's fill) clipped to target from above when target > f0, from below otherwise.

@@ -109,6 +109,9 @@ int  dd_debug_adsb_chips(const void* iq, int64_t n, int64_t rate, int phases, co
 /* dd_debug_pocsag_masks -- the mask byte of every sample that dd_pocsag_candidates lists from (its arguments): mask[n] on the device,
  *   1 = the sync codeword within `slack` places, 3 = its inverse, 0 otherwise and past the last start. */
 int  dd_debug_pocsag_masks(const double* audio, int64_t n, double sps, int w, int slack, uint8_t* mask, void* stream);
+/* dd_debug_acars_masks -- the mask byte of every sample that dd_acars_candidates lists from (its arguments): mask[n] on the device,
+ *   1 = the template * SYN SYN SOH within `slack` places, 3 = its inverse, 0 otherwise and past the last start. */
+int  dd_debug_acars_masks(const double* audio, int64_t n, double sps, int w, int slack, uint8_t* mask, void* stream);
 
 #ifdef __cplusplus
 }
