@@ -211,6 +211,11 @@ SIGNATURES = {
     "dd_acars_candidates": (_int, [_p, _i64, C.c_double, _int, _int, _p, _i64, _pi64, _p]),
     "dd_acars_blocks": (_int, [_p, _i64, C.c_double, _int, _int, _p, _i64, _p, _p, _p, _p]),
     "dd_debug_acars_masks": (_int, [_p, _i64, C.c_double, _int, _int, _p, _p]),
+    # RS41 radiosonde frames (dd_rs41.h)
+    "dd_rs41_candidates": (_int, [_p, _i64, C.c_double, _int, _int, _p, _i64, _pi64, _p]),
+    "dd_rs41_frames": (_int, [_p, _i64, C.c_double, _int, _p, _i64, _p, _p, _p, _p]),
+    "dd_debug_rs41_masks": (_int, [_p, _i64, C.c_double, _int, _int, _p, _p]),
+    "dd_debug_rs41_rs": (_int, [_p, _i64, _int, _p, _p, _p]),
     "dd_lrpt_rs": (_int, [_p, _i64, _p, _p, _p]),
     "dd_lrpt_jpeg": (_int, [_p, _p, _p, _p, _i64, _i64, _p, _p, _p]),
     "dd_funcube_mix_ramp": (_int, [_p, _p, _i64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _p, _p]),

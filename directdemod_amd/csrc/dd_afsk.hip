@@ -118,6 +118,10 @@ extern "C" int dd_afsk_edges_f64(const double* binary_filter, int64_t n, int spb
 // Reed-Solomon (255,223) correction of the frame bodies
 #include "dd_lrpt_rs.h"
 
+// RS41 radiosonde telemetry, 2-GFSK at 4800 baud: header candidates from POCSAG's LDS prefix sum against an unbalanced template's class
+// midpoint, de-whitening and two RS(255,231) codewords per wave through the same Reed-Solomon wave
+#include "dd_rs41.h"
+
 // the image packets' JPEG-like payload: Huffman decoding, dequantisation, inverse transform
 #include "dd_lrpt_jpeg.h"
 

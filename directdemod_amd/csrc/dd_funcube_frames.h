@@ -168,7 +168,7 @@ __global__ void __launch_bounds__(128) k_fc_rs(const uint8_t* __restrict__ block
         got[q] = pos[q] < DD_RS_N ? row[1 + pos[q]] : 0;
         out[q] = got[q];
     }
-    const int nerr = dd_rs_wave(ex, lg, row, lane, pos, got, out, DD_FCF_RS_PAD);
+    const int nerr = dd_rs_wave<DD_RS_T, DD_RS_BETA, DD_RS_ROOT0>(ex, lg, row, lane, pos, got, out, DD_FCF_RS_PAD);
     uint8_t* dst = frames + f * DD_FCF_FRAME + w;
     for (int q = 0; q < 4; ++q) {
         const int k = pos[q] - DD_FCF_RS_PAD;

@@ -656,6 +656,29 @@ int dd_acars_candidates(const double* audio, int64_t n, double sps, int w, int s
 int dd_acars_blocks(const double* audio, int64_t n, double sps, int w, int fix, const int64_t* list, int64_t m, uint8_t* bytes,
                     int32_t* meta, int64_t* score, void* stream);
 
+/* ---- Vaisala RS41 radiosonde telemetry, 2-GFSK at 4800 baud (beyond the reference; DESIGN.md section 4.26 defines every stage) ------
+ * rs41.py restates every entry in NumPy.  audio, n, q and v(t, k) as for AIS above, with sps = samples per bit, 4 .. 64, and w odd,
+ * 1 .. 39.  The header on the air is 10 B6 CA 11 22 96 12 F8, each byte's lowest bit first: 25 ones and 39 zeros among the places
+ * k = 0 .. 63.  S1(t) = the sum of v(t, k) over the one-places, S0(t) over the zero-places; a bit k of the start t is high when
+ * 1950 v(t, k) > 39 S1(t) + 25 S0(t) and low when 1950 v(t, k) < 39 S1(t) + 25 S0(t), both strictly.  Polarity 0 reads high as 1 and
+ * anything else as 0; polarity 1 reads low as 1 and anything else as 0.  The starts are the t >= 0 with floor(63.5 sps) + w / 2 < n - t.
+ * dd_rs41_candidates -- the starts whose 64 bits equal the header in all but at most `slack` places (0 .. 11) in polarity 0 or, failing
+ *     that, in polarity 1, in ascending order: list[min(*count_host, cap)], *count_host = how many passed.  More than cap:
+ *     DD_ERR_INVALID with the count filled and nothing written past cap.
+ * dd_rs41_frames -- per listed start c < m: the polarity is 1 when the header has fewer wrong places in polarity 1 than in polarity 0;
+ *     byte i of the frame is bits 8 i .. 8 i + 7, the first-sent in bit 0, XOR MASK[i mod 64] (section 4.26).  The frame is 518 bytes
+ *     long when byte 56 as received is nearer in Hamming distance to F0 than to 0F and floor(t + 4143.5 sps) + w / 2 < n, else 320.
+ *     Codeword j (0, 1): c_p = frame[8 + 24 j + p] for p < 24 and frame[56 + 2 (p - 24) + j] from there on while the frame lasts, 0
+ *     behind it; RS(255,231) over GF(2)[x]/0x11D, alpha = 2, roots alpha^0 .. alpha^23: the codeword within 12 bytes that changes no
+ *     byte behind the frame's end, or none.  fixed[518 c ..] = the frame with the decodable codewords corrected, recv[518 c ..] = the
+ *     frame as received, both zero past the length; meta[6 c ..] = status, polarity, length, the header's wrong places, the bytes
+ *     changed in codeword 0 and in codeword 1 (-1: none within reach).  list, fixed, recv and meta are device arrays.  A start outside
+ *     [0, n), or with floor(t + 2559.5 sps) + w / 2 >= n, gives status 1 and zeros. */
+int dd_rs41_candidates(const double* audio, int64_t n, double sps, int w, int slack, int64_t* list, int64_t cap, int64_t* count_host,
+                       void* stream);
+int dd_rs41_frames(const double* audio, int64_t n, double sps, int w, const int64_t* list, int64_t m, uint8_t* fixed, uint8_t* recv,
+                   int32_t* meta, void* stream);
+
 /* ---- Funcube BPSK sync detection (decode_funcube.py:148-306) ------------------------------------------------------------
  * dd_funcube_mix_ramp -- dd_meteor_mix with the frequency formed per sample: th = ((w * f[k]) * k) * inv_fs, w = -2 pi,
  *     f[k] = f0 + k * delta (np.arange's fill) clipped to target from above when target > f0, from below otherwise.

@@ -112,6 +112,14 @@ int  dd_debug_pocsag_masks(const double* audio, int64_t n, double sps, int w, in
 /* dd_debug_acars_masks -- the mask byte of every sample that dd_acars_candidates lists from (its arguments): mask[n] on the device,
  *   1 = the template * SYN SYN SOH within `slack` places, 3 = its inverse, 0 otherwise and past the last start. */
 int  dd_debug_acars_masks(const double* audio, int64_t n, double sps, int w, int slack, uint8_t* mask, void* stream);
+/* dd_debug_rs41_masks -- the mask byte of every sample that dd_rs41_candidates lists from (its arguments): mask[n] on the device,
+ *   1 = the RS41 header within `slack` places, 3 = the header of the negated audio, 0 otherwise and past the last start. */
+int  dd_debug_rs41_masks(const double* audio, int64_t n, double sps, int w, int slack, uint8_t* mask, void* stream);
+/* dd_debug_rs41_rs -- the Reed-Solomon wave as dd_rs41_frames instantiates it, RS(255,231) over GF(2)[x]/0x11D with roots alpha^0 ..
+ *   alpha^23, over m words of 255 bytes (byte i the coefficient of x^(254 - i)): fixed[255 c ..] = the word within 12 bytes of word c
+ *   with errors[c] = the bytes changed, or the word itself with -1 where there is none or where it would change a byte below
+ *   first_valid (0 .. 255).  words, fixed and errors are device arrays.  Lets the decoder be tested without audio. */
+int  dd_debug_rs41_rs(const uint8_t* words, int64_t m, int first_valid, uint8_t* fixed, int32_t* errors, void* stream);
 
 #ifdef __cplusplus
 }
