@@ -216,6 +216,13 @@ SIGNATURES = {
     "dd_rs41_frames": (_int, [_p, _i64, C.c_double, _int, _p, _i64, _p, _p, _p, _p]),
     "dd_debug_rs41_masks": (_int, [_p, _i64, C.c_double, _int, _int, _p, _p]),
     "dd_debug_rs41_rs": (_int, [_p, _i64, _int, _p, _p, _p]),
+    # RDS groups (dd_rds.h)
+    "dd_rds_baseband": (_int, [_p, _i64, _int, _u64, _u64, _p, _p, _p]),
+    "dd_rds_candidates": (_int, [_p, _i64, C.c_double, _int, _p, _i64, _pi64, _p]),
+    "dd_rds_groups": (_int, [_p, _i64, C.c_double, _int, _p, _i64, _p, _p, _p]),
+    "dd_debug_rds_masks": (_int, [_p, _i64, C.c_double, _int, _p, _p]),
+    "dd_debug_rds_halfbit": (_int, [_p, _i64, C.c_double, _p, _p]),
+    "dd_debug_rds_repair": (_int, [_p, _p, _i64, _int, _p, _p, _p]),
     "dd_lrpt_rs": (_int, [_p, _i64, _p, _p, _p]),
     "dd_lrpt_jpeg": (_int, [_p, _p, _p, _p, _i64, _i64, _p, _p, _p]),
     "dd_funcube_mix_ramp": (_int, [_p, _p, _i64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _p, _p]),

@@ -122,6 +122,10 @@ extern "C" int dd_afsk_edges_f64(const double* binary_filter, int64_t n, int spb
 // midpoint, de-whitening and two RS(255,231) codewords per wave through the same Reed-Solomon wave
 #include "dd_rs41.h"
 
+// RDS on broadcast FM, 1187.5 bit/s on the multiplex's 57 kHz subcarrier: a table-phasor block-sum baseband, half-bit differences from
+// the same LDS prefix sum, every sample tested as a group start by four block remainders, burst repair per wave
+#include "dd_rds.h"
+
 // the image packets' JPEG-like payload: Huffman decoding, dequantisation, inverse transform
 #include "dd_lrpt_jpeg.h"
 

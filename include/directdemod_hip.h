@@ -679,6 +679,32 @@ int dd_rs41_candidates(const double* audio, int64_t n, double sps, int w, int sl
 int dd_rs41_frames(const double* audio, int64_t n, double sps, int w, const int64_t* list, int64_t m, uint8_t* fixed, uint8_t* recv,
                    int32_t* meta, void* stream);
 
+/* ---- RDS on broadcast FM, 1187.5 bit/s differential biphase on 57 kHz (beyond the reference) ---------------
+ * rds.py restates every entry in NumPy.  mpx is the FM discriminator's float64 output in radians per sample at R S/s;
+ * q = rint(mpx * 2^15 / pi), 0 for a NaN and beyond +-2^15.
+ * dd_rds_baseband -- b[2 o], b[2 o + 1] = (the sum over i < D of q[o D + i] * table[phase(n0 + o D + i)]) >> 10 (arithmetic, of the
+ *     int64 sum) for o < n / D; a tail shorter than D is dropped.  phase(j) = bits 31 .. 22 of (j * step) mod 2^32, step =
+ *     rint(57000 * 2^32 / R); table = 1024 int32 pairs rint(2^14 exp(-2 pi i (j + 1/2) / 1024)), 1 <= D <= 32.  |b| <= 2^24.
+ * With sps = baseband samples per bit, 12 .. 32, h = floor(sps / 2) and m pairs of b: z[p] = the sum of b[p .. p + h - 1] less the sum
+ * of b[p - h .. p - 1] for h <= p <= m - h, else 0; p_k(t) = floor((t + k sps) + 0.5), each operation rounded to float64; bit k of the
+ * start t is 1 iff Re(z[p_k] conj(z[p_(k-1)])) < 0 (int64), k = 0 .. 103, first-sent first into four blocks of 26 bits.  A block is
+ * clean for an offset word iff block mod 0x5B9 equals it: A 0FC, B 198, C 168, C' 350, D 1B4.  A start fits when 0 <= t < m,
+ * p_-1 >= 0 and p_103 <= m - h.
+ * dd_rds_candidates -- the starts that fit with at least `clean` (2 .. 4) clean blocks, the four tested against A, B, C or C', D, in
+ *     ascending order: list[min(*count_host, cap)], *count_host = how many passed.  More than cap: DD_ERR_INVALID with the count
+ *     filled and nothing written past cap.
+ * dd_rds_groups -- per listed start c < count: a block that is not clean is repaired when exactly one burst of at most `fix` bits
+ *     (0 .. 5, a burst begins and ends in a wrong bit) makes it clean.  The third block is held against C' when the second, after
+ *     its repair, has bit 11 of its information word set, against C when not; if the second is not decodable, against whichever of
+ *     the two it is clean for, and C if neither.  words[4 c ..] = the four 16-bit information words (as received where not
+ *     decodable); meta[8 c ..] = four statuses (0 clean, n bits repaired, -1 not decodable), the third offset word (0 C, 1 C'), the
+ *     metric = the sum over the bits of min(|Re| >> 20, 2^24) <= 104 * 2^24, 0, the blocks decoded.  A start that does not fit gives
+ *     zeros, statuses of -1 and meta[8 c + 6] = 1.  b, list, words and meta are device arrays. */
+int dd_rds_baseband(const double* mpx, int64_t n, int D, uint64_t n0, uint64_t step, const int32_t* table, int32_t* b, void* stream);
+int dd_rds_candidates(const int32_t* b, int64_t m, double sps, int clean, int64_t* list, int64_t cap, int64_t* count_host, void* stream);
+int dd_rds_groups(const int32_t* b, int64_t m, double sps, int fix, const int64_t* list, int64_t count, uint16_t* words, int32_t* meta,
+                  void* stream);
+
 /* ---- Funcube BPSK sync detection (decode_funcube.py:148-306) ------------------------------------------------------------
  * dd_funcube_mix_ramp -- dd_meteor_mix with the frequency formed per sample: th = ((w * f[k]) * k) * inv_fs, w = -2 pi,
  *     f[k] = f0 + k * delta (np.arange's fill) clipped to target from above when target > f0, from below otherwise.

@@ -120,6 +120,17 @@ int  dd_debug_rs41_masks(const double* audio, int64_t n, double sps, int w, int 
  *   with errors[c] = the bytes changed, or the word itself with -1 where there is none or where it would change a byte below
  *   first_valid (0 .. 255).  words, fixed and errors are device arrays.  Lets the decoder be tested without audio. */
 int  dd_debug_rs41_rs(const uint8_t* words, int64_t m, int first_valid, uint8_t* fixed, int32_t* errors, void* stream);
+/* dd_debug_rds_masks -- the mask byte of every start that dd_rds_candidates lists from (its arguments): mask[m] on the device,
+ *   score << 1 | (score >= clean) with score = the blocks whose remainder is their offset word's, 0 where the group does not fit. */
+int  dd_debug_rds_masks(const int32_t* b, int64_t m, double sps, int clean, uint8_t* mask, void* stream);
+/* dd_debug_rds_halfbit -- the half-bit differences the RDS kernels decide bits from: z[2 p], z[2 p + 1] = the sum of b[p .. p + h - 1]
+ *   less the sum of b[p - h .. p - 1], h = floor(sps / 2), for h <= p <= m - h and 0 elsewhere; b and z are device arrays of m pairs. */
+int  dd_debug_rds_halfbit(const int32_t* b, int64_t m, double sps, int32_t* z, void* stream);
+/* dd_debug_rds_repair -- the block repair of dd_rds_groups over loose words: word c of 26 bits against offset word offs[c] (0 A, 1 B,
+ *   2 C, 3 C', 4 D) gives status[c] = 0 when it is clean, n when the one burst of at most `fix` bits (0 .. 5) that makes it clean has
+ *   n ones, with fixed[c] the block without that burst, and -1 with fixed[c] = the word where there is none.  Device arrays. */
+int  dd_debug_rds_repair(const uint32_t* words, const int32_t* offs, int64_t count, int fix, uint32_t* fixed, int32_t* status,
+                         void* stream);
 
 #ifdef __cplusplus
 }
