@@ -14,13 +14,12 @@ upwards after a 1 (polarity 0), so v > 0 reads 1; the carrier's level cancels in
 The format is taken from public descriptions of ARINC 618 VHF ACARS; it was not checked against an off-air recording.
 INTEGRATION.md lists the limits.
 """
-import ctypes as C
 import math
-import time
 
 import numpy as np
 
-from . import _hip
+from . import _burst
+from ._burst import Laps, need
 from ._hip import DevArray, check, lib
 
 BAUD = 2400
@@ -236,11 +235,6 @@ def blocks_host(audio, sps, w, fix, ts):
 
 
 # ------------------------------------------------------------------------------------------------------------------ the device stages
-def _need(a, what):
-    if not isinstance(a, DevArray) or a.dtype != _F64:
-        raise TypeError("%s: a float64 device array expected" % what)
-
-
 def capacity(n, sps):
     """the default list capacity: a clean block passes at about sps / 2 adjacent starts of the 300 sps samples the shortest block
     with its pre-key takes; some four times that share of the audio, and 1024"""
@@ -250,22 +244,16 @@ def capacity(n, sps):
 def candidates(audio, sps, w, slack=2, cap=None):
     """float64 device audio -> (the survivors as a device int64 array, how many) (dd_acars_candidates); a list that proves too
     small is asked for again at the true count"""
-    _need(audio, "acars.candidates")
+    need(audio, _F64, "acars.candidates")
     cap = capacity(audio.n, sps) if cap is None else int(cap)
-    count = C.c_int64(0)
-    while True:
-        lst = DevArray(max(cap, 1), np.int64)
-        rc = lib().dd_acars_candidates(audio.ptr, audio.n, float(sps), int(w), int(slack), lst.ptr, cap, C.byref(count), None)
-        if rc == _hip.DD_ERR_INVALID and count.value > cap:
-            cap = count.value
-            continue
-        check(rc, "dd_acars_candidates")
-        return lst, int(count.value)
+    def call(lst, cap, count):
+        return lib().dd_acars_candidates(audio.ptr, audio.n, float(sps), int(w), int(slack), lst, cap, count, None)
+    return _burst.candidates("dd_acars_candidates", cap, call)
 
 
 def blocks(audio, sps, w, fix, lst, m):
     """the first m starts of the device list -> the dict of blocks_host, on the host (dd_acars_blocks)"""
-    _need(audio, "acars.blocks")
+    need(audio, _F64, "acars.blocks")
     if not isinstance(lst, DevArray):
         lst = DevArray.from_host(np.ascontiguousarray(lst, dtype=np.int64))
     det = _empty_det(m)
@@ -282,27 +270,20 @@ def blocks(audio, sps, w, fix, lst, m):
 
 def masks_device(audio, sps, w, slack=2):
     """the mask byte of every sample, uint8[n] on the host, 0 past the last start (dd_debug_acars_masks, a diagnostic)"""
-    _need(audio, "acars.masks_device")
-    mask = DevArray(max(audio.n, 1), np.uint8)
-    check(lib().dd_debug_acars_masks(audio.ptr, audio.n, float(sps), int(w), int(slack), mask.ptr, None), "dd_debug_acars_masks")
-    return mask.to_host()[:audio.n]
+    need(audio, _F64, "acars.masks_device")
+    return _burst.masks("dd_debug_acars_masks", audio.n,
+                        lambda mask: lib().dd_debug_acars_masks(audio.ptr, audio.n, float(sps), int(w), int(slack), mask, None))
 
 
-class HostOps:
+class HostOps(Laps):
     """the stages of `decode` in NumPy"""
 
     def detect(self, audio, sps, w, slack, fix):
         return blocks_host(audio, sps, w, fix, candidates_host(audio, sps, w, slack))
 
-    def lap(self, name):
-        pass
 
-
-class DeviceOps:
+class DeviceOps(Laps):
     """the stages of `decode` on the device; `laps` collects seconds per stage, with a synchronisation after each"""
-
-    def __init__(self, laps=None):
-        self.laps = laps
 
     def detect(self, audio, sps, w, slack, fix):
         lst, m = candidates(audio, sps, w, slack)
@@ -310,13 +291,6 @@ class DeviceOps:
         det = blocks(audio, sps, w, fix, lst, m)
         self.lap("blocks")
         return det
-
-    def lap(self, name):
-        if self.laps is not None:
-            _hip.sync()
-            now = time.perf_counter()
-            self.laps[name] = self.laps.get(name, 0.0) + now - self.laps["_t"]
-            self.laps["_t"] = now
 
 
 # ------------------------------------------------------------------------------------------------------------------ the host logic

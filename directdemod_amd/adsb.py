@@ -8,12 +8,12 @@ Positions are integers in units of 1/U sample (U = 2 000 000 chips per second): 
 starts at k U / Q and its chip c covers R units from there on.  Divided by g = gcd(U / Q, R) these are u = U / g, xq = U / (Q g)
 and r = R / g; a chip energy is the sum of overlap * power, an exact integer below 2^63.
 """
-import ctypes as C
 import math
 
 import numpy as np
 
 from . import _hip
+from . import _burst
 from ._hip import DevArray, check, lib
 
 U = 2000000                           # chips per second
@@ -193,15 +193,9 @@ def candidates(iq, rate, Q, cap=None):
     _need(iq, "adsb.candidates")
     rate, Q = check_rate(rate, Q)
     cap = 1024 + n_candidates(iq.n, rate, Q) // 128 if cap is None else int(cap)
-    count = C.c_int64(0)
-    while True:
-        lst = DevArray(max(cap, 1), np.int64)
-        rc = lib().dd_adsb_candidates(iq.ptr, iq.n, rate, Q, lst.ptr, cap, C.byref(count), None)
-        if rc == _hip.DD_ERR_INVALID and count.value > cap:
-            cap = count.value
-            continue
-        check(rc, "dd_adsb_candidates")
-        return lst, int(count.value)
+    def call(lst, cap, count):
+        return lib().dd_adsb_candidates(iq.ptr, iq.n, rate, Q, lst, cap, count, None)
+    return _burst.candidates("dd_adsb_candidates", cap, call)
 
 
 def demod(iq, rate, Q, lst, m):

@@ -11,13 +11,12 @@ samples q around it, samples outside the audio counting 0.
 
 The format is taken from public descriptions of AIS (ITU-R M.1371, the AIVDM sentence descriptions); INTEGRATION.md lists the limits.
 """
-import ctypes as C
 import math
-import time
 
 import numpy as np
 
-from . import _hip
+from . import _burst
+from ._burst import Laps, need
 from ._hip import DevArray, check, lib
 
 BAUD = 9600
@@ -29,7 +28,7 @@ TRAINING = 16                         # of which S sums the first
 RAW_BITS = 1280                       # raw bits behind the start flag that dd_ais_demod reads
 FRAME_BYTES = 160
 TILE = 256                            # DD_AIS_TILE
-SCALE = 1048576.0 / math.pi           # DD_AIS_SCALE
+SCALE = 1048576.0 / math.pi           # DD_FM_SCALE (dd_candidates.h)
 CLIP = 2097152.0
 PLUS = np.array([(0x80CCCC >> k) & 1 for k in range(TEMPLATE)], dtype=bool)      # (- - + +) x 4, seven -, one +
 OK, NO_END, ABORT, STUFFING, LENGTH, CRC = range(6)
@@ -219,30 +218,19 @@ def demod_host(audio, sps, w, ts):
 
 
 # ------------------------------------------------------------------------------------------------------------------ the device stages
-def _need(a, what):
-    if not isinstance(a, DevArray) or a.dtype != _F64:
-        raise TypeError("%s: a float64 device array expected" % what)
-
-
 def candidates(audio, sps, w, slack=0, cap=None):
     """float64 device audio -> (the survivors as a device int64 array, how many) (dd_ais_candidates); a list that proves too small
     is asked for again at the true count"""
-    _need(audio, "ais.candidates")
+    need(audio, _F64, "ais.candidates")
     cap = 1024 + audio.n // 1024 if cap is None else int(cap)
-    count = C.c_int64(0)
-    while True:
-        lst = DevArray(max(cap, 1), np.int64)
-        rc = lib().dd_ais_candidates(audio.ptr, audio.n, float(sps), int(w), int(slack), lst.ptr, cap, C.byref(count), None)
-        if rc == _hip.DD_ERR_INVALID and count.value > cap:
-            cap = count.value
-            continue
-        check(rc, "dd_ais_candidates")
-        return lst, int(count.value)
+    def call(lst, cap, count):
+        return lib().dd_ais_candidates(audio.ptr, audio.n, float(sps), int(w), int(slack), lst, cap, count, None)
+    return _burst.candidates("dd_ais_candidates", cap, call)
 
 
 def demod(audio, sps, w, lst, m):
     """the first m starts of the device list -> the dict of demod_host, on the host (dd_ais_demod)"""
-    _need(audio, "ais.demod")
+    need(audio, _F64, "ais.demod")
     if not isinstance(lst, DevArray):
         lst = DevArray.from_host(np.ascontiguousarray(lst, dtype=np.int64))
     det = _empty_det(m)
@@ -256,22 +244,16 @@ def demod(audio, sps, w, lst, m):
     return det
 
 
-class HostOps:
+class HostOps(Laps):
     """the stages of `decode` in NumPy"""
 
     def detect(self, audio, sps, w, slack):
         ts = candidates_host(audio, sps, w, slack)
         return demod_host(audio, sps, w, ts)
 
-    def lap(self, name):
-        pass
 
-
-class DeviceOps:
+class DeviceOps(Laps):
     """the stages of `decode` on the device; `laps` collects seconds per stage, with a synchronisation after each"""
-
-    def __init__(self, laps=None):
-        self.laps = laps
 
     def detect(self, audio, sps, w, slack):
         lst, m = candidates(audio, sps, w, slack)
@@ -279,13 +261,6 @@ class DeviceOps:
         det = demod(audio, sps, w, lst, m)
         self.lap("demod")
         return det
-
-    def lap(self, name):
-        if self.laps is not None:
-            _hip.sync()
-            now = time.perf_counter()
-            self.laps[name] = self.laps.get(name, 0.0) + now - self.laps["_t"]
-            self.laps["_t"] = now
 
 
 # ------------------------------------------------------------------------------------------------------------------ the host logic

@@ -1,14 +1,14 @@
 // ACARS on VHF, 2400 baud MSK on 1200 / 2400 Hz over AM (beyond the reference; DESIGN.md section 4.25 defines every stage, acars.py
-// restates each kernel in NumPy), included by dd_afsk.hip after dd_pocsag.h, whose LDS prefix sum and list driver it uses, with
-// dd_adsb.h's list kernel and dd_sstv.h's block scan.  The audio is the float64 AM envelope; everything behind the quantiser is
-// integer, so sums in any order equal the restatement bit for bit.  The boundaries are float64 products and sums rounded one by one
+// restates each kernel in NumPy), included by dd_afsk.hip after dd_candidates.h, whose LDS prefix sum, tail, list kernel and driver it
+// uses; the quantiser's scale and clip and the bit-end positions are its own.  The audio is the float64 AM envelope; everything
+// behind the quantiser is integer, so sums in any order equal the restatement bit for bit.  The boundaries are float64 products and sums rounded one by one
 // (the unit is built without contraction).
 //
 //   k_acars_sync      -- a workgroup stages the quantised audio of 256 starts and the reach of 32 bits in LDS and turns it into its
-//                        exclusive prefix sum in place (dd_pocsag_prefix256; 32-bit wrap-around: |v| <= 2^27, so differences are
+//                        exclusive prefix sum in place (dd_stage_prefix256; 32-bit wrap-around: |v| <= 2^27, so differences are
 //                        exact); one thread per start decides the 32 bits of * SYN SYN SOH, each the sum of the w samples behind a
 //                        bit's end less the w before it, three LDS reads per bit; a mask byte per sample, a count per workgroup
-//   k_adsb_list       -- (dd_adsb.h) the masks' pass bits as an ordered candidate list below the capacity
+//   k_cand_list       -- (dd_candidates.h) the masks' pass bits as an ordered candidate list below the capacity
 //   k_acars_block     -- one wave per listed start: 1920 bits by thirty ballots, each ballot word eight received characters; the end
 //                        by a lane per character, the block check as a wave XOR of lone-bit registers, repair of one bit or of one
 //                        bit in each of two characters guided by the characters' parity
@@ -70,12 +70,7 @@ __global__ void __launch_bounds__(DD_ACARS_TILE) k_acars_sync(const double* __re
     const int tid = threadIdx.x;
     const int64_t base = (int64_t)blockIdx.x * DD_ACARS_TILE;
     const int64_t first = base - gd.w;               // the tile's first sample; 0 outside the audio
-    for (int j = tid; j < gd.span; j += DD_ACARS_TILE) {
-        const int64_t i = first + j;
-        ps[j] = (i >= 0 && i < n) ? (uint32_t)dd_acars_q(x[i]) : 0u;
-    }
-    __syncthreads();
-    dd_pocsag_prefix256(ps, gd.span, tops);
+    dd_stage_prefix256([&](int64_t i) { return dd_acars_q(x[i]); }, n, first, gd.span, ps, tops);
     const int64_t t = base + tid;
     uint32_t m = 0;
     if (t < gd.nstart) {
@@ -90,9 +85,7 @@ __global__ void __launch_bounds__(DD_ACARS_TILE) k_acars_sync(const double* __re
         const int mis = __popc(d ^ DD_ACARS_TEMPLATE);
         m = mis <= gd.slack ? 1u : (32 - mis <= gd.slack ? 3u : 0u);
     }
-    if (t < n) mask[t] = (uint8_t)m;
-    const int total = dd_sstv_scan256((int)(m & 1u), sh);
-    if (tid == 255) bsum[blockIdx.x] = total;
+    dd_cand_tail(mask, t, n, m, (int)(m & 1u), sh, bsum);
 }
 
 // the bytes of word j that lie at or before byte e, as a mask over the word's 64 bits
@@ -256,19 +249,12 @@ static auto dd_acars_sync_launch(const double* audio, int64_t n, const DDAcarsGr
 
 extern "C" int dd_acars_candidates(const double* audio, int64_t n, double sps, int w, int slack, int64_t* list, int64_t cap,
                                    int64_t* count_host, void* stream) {
-    DDAcarsGrid gd;
-    DD_REQUIRE(cap >= 0 && dd_acars_grid(n, sps, w, slack, 0, &gd),
-               "dd_acars_candidates: need 0 <= n < 2^31, 8 <= sps <= 64, 1 <= w <= 32, 0 <= slack <= 5 and cap >= 0");
-    DD_REQUIRE(count_host != nullptr, "dd_acars_candidates: count");
-    *count_host = 0;
-    if (n == 0) return DD_OK;
-    DD_REQUIRE(audio != nullptr && (cap == 0 || list != nullptr), "dd_acars_candidates: null buffer");
-    if (gd.nstart == 0) return DD_OK;
+    DDAcarsGrid gd = {};
+    const bool served = cap >= 0 && dd_acars_grid(n, sps, w, slack, 0, &gd);
     hipStream_t s = dd_stream(stream);
-    int rc = dd_pocsag_run(n, gd.nstart, nullptr, list, cap, count_host, s, dd_acars_sync_launch(audio, n, gd, s));
-    if (rc != DD_OK) return rc;
-    DD_REQUIRE(*count_host <= cap, "dd_acars_candidates: candidate list too small");
-    return DD_OK;
+    return dd_cand_entry("dd_acars_candidates", served,
+                         "dd_acars_candidates: need 0 <= n < 2^31, 8 <= sps <= 64, 1 <= w <= 32, 0 <= slack <= 5 and cap >= 0", audio, n,
+                         gd.nstart, 1, 1u, list, cap, count_host, s, dd_acars_sync_launch(audio, n, gd, s));
 }
 
 extern "C" int dd_acars_blocks(const double* audio, int64_t n, double sps, int w, int fix, const int64_t* list, int64_t m,
@@ -285,13 +271,10 @@ extern "C" int dd_acars_blocks(const double* audio, int64_t n, double sps, int w
 }
 
 extern "C" int dd_debug_acars_masks(const double* audio, int64_t n, double sps, int w, int slack, uint8_t* mask, void* stream) {
-    DDAcarsGrid gd;
-    DD_REQUIRE(dd_acars_grid(n, sps, w, slack, 0, &gd),
-               "dd_debug_acars_masks: need 0 <= n < 2^31, 8 <= sps <= 64, 1 <= w <= 32 and 0 <= slack <= 5");
-    if (n == 0) return DD_OK;
-    DD_REQUIRE(audio != nullptr && mask != nullptr, "dd_debug_acars_masks: null buffer");
+    DDAcarsGrid gd = {};
+    const bool served = dd_acars_grid(n, sps, w, slack, 0, &gd);
     hipStream_t s = dd_stream(stream);
-    DD_HIP_CHECK(hipMemsetAsync(mask, 0, (size_t)n, s));
-    if (gd.nstart == 0) return DD_OK;
-    return dd_pocsag_run(n, gd.nstart, mask, nullptr, 0, nullptr, s, dd_acars_sync_launch(audio, n, gd, s));
+    return dd_cand_masks_entry("dd_debug_acars_masks", served,
+                               "dd_debug_acars_masks: need 0 <= n < 2^31, 8 <= sps <= 64, 1 <= w <= 32 and 0 <= slack <= 5", audio, n, gd.nstart,
+                               mask, s, dd_acars_sync_launch(audio, n, gd, s));
 }

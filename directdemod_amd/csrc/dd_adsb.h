@@ -1,11 +1,11 @@
 // 1090 MHz Mode S / ADS-B squitters (beyond the reference; DESIGN.md section 4.22 defines every stage, adsb.py restates each kernel in
-// NumPy), included by dd_afsk.hip after dd_sstv.h, whose block scan it uses.  All integer: positions in units of g = gcd(U / Q, R)
+// NumPy), included by dd_afsk.hip after dd_candidates.h, whose tail, list kernel and driver it uses.  All integer: positions in units of g = gcd(U / Q, R)
 // with u = U / g units per sample, xq = U / (Q g) per candidate step and r = R / g per chip; a chip energy is the sum of
 // overlap * power over the samples the chip touches, below 2^43, so sums in any order equal the restatement bit for bit.
 //
 //   k_adsb_preamble   -- a workgroup stages the power of 256 samples of starts and the preamble's reach in LDS, one thread per
 //                        sample walks its Q candidates' 15 chips, a mask byte per sample and a count per workgroup come out
-//   k_adsb_list       -- the masks' set bits (those of a keep mask: dd_ais.h lists bit 0 alone) as an ordered candidate list below the capacity (the counts scanned by k_sstv_scan_tops)
+//   k_cand_list       -- (dd_candidates.h) the masks' set bits, all Q of a byte, as an ordered candidate list below the capacity
 //   k_adsb_demod      -- one wave per listed candidate: 112 bit decisions by ballot, remainder, score, one-bit repair
 //   k_adsb_chips      -- diagnostic: one wave per listed candidate, all 240 chip energies
 #pragma once
@@ -72,25 +72,7 @@ __global__ void __launch_bounds__(DD_ADSB_TILE) k_adsb_preamble(const uint8_t* _
                         6 * e[4] < s && 6 * e[5] < s && 6 * e[11] < s && 6 * e[12] < s && 6 * e[13] < s && 6 * e[14] < s;
         m |= ok ? 1u << i : 0u;
     }
-    if (base + tid < n) mask[base + tid] = (uint8_t)m;
-    const int total = dd_sstv_scan256(__popc(m), sh);
-    if (tid == 255) bsum[blockIdx.x] = total;
-}
-
-// list[boff[block] + rank] = k for every set mask bit among `keep` whose place is below cap: ordered, nothing written past cap
-__global__ void __launch_bounds__(DD_ADSB_TILE) k_adsb_list(const uint8_t* __restrict__ mask, int64_t n, int Q, uint32_t keep,
-                                                            const int* __restrict__ boff, int64_t* __restrict__ list, int64_t cap) {
-    __shared__ int sh[256];
-    const int64_t at = (int64_t)blockIdx.x * DD_ADSB_TILE + threadIdx.x;
-    uint32_t m = at < n ? mask[at] & keep : 0u;
-    const int c = __popc(m);
-    int64_t place = (int64_t)boff[blockIdx.x] + dd_sstv_scan256(c, sh) - c;
-    while (m) {
-        const int i = __ffs(m) - 1;
-        m &= m - 1;
-        if (place < cap) list[place] = at * Q + i;
-        ++place;
-    }
+    dd_cand_tail(mask, base + tid, n, m, __popc(m), sh, bsum);
 }
 
 // where candidate k's chip c starts: sample j and f units into it (k xq = (k / Q) u + (k mod Q) xq)
@@ -228,39 +210,16 @@ static const DDAdsbTable& dd_adsb_table() {
 
 extern "C" int dd_adsb_candidates(const void* iq, int64_t n, int64_t rate, int phases, int64_t* list, int64_t cap, int64_t* count_host,
                                   void* stream) {
-    DDAdsbGrid gd;
-    DD_REQUIRE(cap >= 0 && dd_adsb_grid(n, rate, phases, &gd),
-               "dd_adsb_candidates: need 0 <= n < 2^28, 2 000 000 <= rate <= 20 000 000, phases of 1, 2, 4, 8 and cap >= 0");
-    DD_REQUIRE(count_host != nullptr, "dd_adsb_candidates: count");
-    *count_host = 0;
-    if (n == 0) return DD_OK;
-    DD_REQUIRE(iq != nullptr && (cap == 0 || list != nullptr), "dd_adsb_candidates: null buffer");
-    if (gd.ncand == 0) return DD_OK;
+    DDAdsbGrid gd = {};
+    const bool served = cap >= 0 && dd_adsb_grid(n, rate, phases, &gd);
     hipStream_t s = dd_stream(stream);
-    const int64_t starts = (gd.ncand + phases - 1) / phases;         // samples that hold a candidate's start
-    const int64_t nb = (starts + DD_ADSB_TILE - 1) / DD_ADSB_TILE;
-    const size_t bM = dd_sstv_up16((size_t)n), bB = dd_sstv_up16(((size_t)nb + 1) * 4);
-    DDScratchLock scr;
-    int rc = scr.get(bM + bB, s);
-    if (rc != DD_OK) return rc;
-    uint8_t* mask = (uint8_t*)scr.ptr;
-    int* bsum = (int*)(scr.ptr + bM);
-    hipLaunchKernelGGL(k_adsb_preamble, dim3((unsigned)nb), dim3(DD_ADSB_TILE), 0, s, (const uint8_t*)iq, n, gd, mask, bsum);
-    DD_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_sstv_scan_tops, dim3(1), dim3(256), 0, s, bsum, nb);
-    DD_LAUNCH_CHECK();
-    int total = 0;
-    DD_HIP_CHECK(hipMemcpyAsync(&total, bsum + nb, sizeof(int), hipMemcpyDeviceToHost, s));
-    DD_HIP_CHECK(hipStreamSynchronize(s));
-    *count_host = total;
-    const int64_t kept = total < cap ? total : cap;
-    if (kept > 0) {
-        hipLaunchKernelGGL(k_adsb_list, dim3((unsigned)nb), dim3(DD_ADSB_TILE), 0, s, (const uint8_t*)mask, n, phases, 0xFFu, (const int*)bsum,
-                           list, kept);
-        DD_LAUNCH_CHECK();
-    }
-    DD_REQUIRE(total <= cap, "dd_adsb_candidates: candidate list too small");
-    return DD_OK;
+    const int64_t starts = served ? (gd.ncand + phases - 1) / phases : 0;   // samples that hold a candidate's start
+    return dd_cand_entry("dd_adsb_candidates", served,
+                         "dd_adsb_candidates: need 0 <= n < 2^28, 2 000 000 <= rate <= 20 000 000, phases of 1, 2, 4, 8 and cap >= 0", iq, n,
+                         starts, phases, 0xFFu, list, cap, count_host, s, [=](uint8_t* mask, int* bsum, int64_t nb) {
+                             hipLaunchKernelGGL(k_adsb_preamble, dim3((unsigned)nb), dim3(DD_ADSB_TILE), 0, s, (const uint8_t*)iq, n, gd, mask,
+                                                bsum);
+                         });
 }
 
 extern "C" int dd_adsb_demod(const void* iq, int64_t n, int64_t rate, int phases, const int64_t* list, int64_t m, uint8_t* frames,

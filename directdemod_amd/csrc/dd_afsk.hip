@@ -88,6 +88,9 @@ extern "C" int dd_afsk_edges_f64(const double* binary_filter, int64_t n, int spb
 // G3RUH 9600 baud FSK: bit timing on FM audio, descrambler, NRZI
 #include "dd_fsk.h"
 
+// what the burst decoders below share: block scans, the LDS prefix sum, the candidate list and its driver, the FM-audio quantiser
+#include "dd_candidates.h"
+
 // Slow-scan television, PD modes: lag product, tone classes, windowed runs, pixels, colour
 #include "dd_sstv.h"
 
@@ -118,7 +121,7 @@ extern "C" int dd_afsk_edges_f64(const double* binary_filter, int64_t n, int spb
 // Reed-Solomon (255,223) correction of the frame bodies
 #include "dd_lrpt_rs.h"
 
-// RS41 radiosonde telemetry, 2-GFSK at 4800 baud: header candidates from POCSAG's LDS prefix sum against an unbalanced template's class
+// RS41 radiosonde telemetry, 2-GFSK at 4800 baud: header candidates from the same LDS prefix sum against an unbalanced template's class
 // midpoint, de-whitening and two RS(255,231) codewords per wave through the same Reed-Solomon wave
 #include "dd_rs41.h"
 

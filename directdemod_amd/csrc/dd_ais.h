@@ -1,12 +1,12 @@
 // AIS, 9600 baud GMSK bursts carrying HDLC frames (beyond the reference; DESIGN.md section 4.23 defines every stage, ais.py restates
-// each kernel in NumPy), included by dd_afsk.hip after dd_adsb.h, whose list kernel and block scan it uses.  The audio is the FM
-// discriminator's float64 output in radians per sample.  One multiply and one rint make an integer of each sample; everything behind
-// that is integer, so sums in any order equal the restatement bit for bit.  The positions are float64 products and sums rounded one
+// each kernel in NumPy), included by dd_afsk.hip after dd_candidates.h, whose tail, list kernel and driver it uses.  The audio is
+// the FM discriminator's float64 output in radians per sample.  One multiply and one rint make an integer of each sample (dd_fm_q);
+// everything behind that is integer, so sums in any order equal the restatement bit for bit.  The positions are float64 products and sums rounded one
 // by one (the unit is built without contraction), as dd_sstv_pixels forms its pixel edges.
 //
 //   k_ais_preamble    -- a workgroup stages the quantised audio of 256 starts and the reach of 24 bits in LDS, one thread per start
 //                        decides the 24 template bits against the training bits' mean; a mask byte per sample, a count per workgroup
-//   k_adsb_list       -- (dd_adsb.h) the masks' pass bits as an ordered candidate list below the capacity
+//   k_cand_list       -- (dd_candidates.h) the masks' pass bits as an ordered candidate list below the capacity
 //   k_ais_demod       -- one wave per listed candidate: 1280 levels by ballot, NRZI, end flag, de-stuffing by masks and prefix counts,
 //                        the CRC as a wave XOR of lone-bit remainders
 #pragma once
@@ -19,8 +19,6 @@
 #define DD_AIS_WORDS 20
 #define DD_AIS_FRAME 160              // bytes per candidate of dd_ais_demod's frames
 #define DD_AIS_PLUS 0x80CCCCu         // the template's + levels: (- - + +) x 4, seven -, one +; bit k = template bit k
-#define DD_AIS_SCALE (1048576.0 / 3.14159265358979323846)
-#define DD_AIS_CLIP 2097152.0         // |q| <= 2^21: twice what a discriminator can give; beyond it and for a NaN q = 0
 
 enum { DD_AIS_OK = 0, DD_AIS_NO_END = 1, DD_AIS_ABORT = 2, DD_AIS_STUFFING = 3, DD_AIS_LENGTH = 4, DD_AIS_CRC = 5 };
 
@@ -46,16 +44,6 @@ constexpr DDAisTable dd_ais_make_table() {
 
 __constant__ const DDAisTable dd_ais_table = dd_ais_make_table();
 
-__device__ __forceinline__ int dd_ais_q(double x) {
-    const double r = rint(x * DD_AIS_SCALE);
-    return (r >= -DD_AIS_CLIP && r <= DD_AIS_CLIP) ? (int)r : 0;
-}
-
-// the middle sample of bit k of the start t
-__device__ __forceinline__ int64_t dd_ais_pos(int64_t t, int k, double sps) {
-    return (int64_t)floor((double)t + ((double)k + 0.5) * sps);
-}
-
 __global__ void __launch_bounds__(DD_AIS_TILE) k_ais_preamble(const double* __restrict__ x, int64_t n, const DDAisGrid gd,
                                                                uint8_t* __restrict__ mask, int* __restrict__ bsum) {
     __shared__ int qs[DD_AIS_MARGIN + DD_AIS_TILE + DD_AIS_REACH];   // qs[j] = q of sample base - margin + j, 0 outside the audio
@@ -64,7 +52,7 @@ __global__ void __launch_bounds__(DD_AIS_TILE) k_ais_preamble(const double* __re
     const int64_t base = (int64_t)blockIdx.x * DD_AIS_TILE;
     for (int j = tid; j < DD_AIS_MARGIN + DD_AIS_TILE + DD_AIS_REACH; j += DD_AIS_TILE) {
         const int64_t i = base - DD_AIS_MARGIN + j;
-        qs[j] = (i >= 0 && i < n) ? dd_ais_q(x[i]) : 0;
+        qs[j] = (i >= 0 && i < n) ? dd_fm_q(x[i]) : 0;
     }
     __syncthreads();
     const int64_t t = base + tid;
@@ -74,7 +62,7 @@ __global__ void __launch_bounds__(DD_AIS_TILE) k_ais_preamble(const double* __re
         int S = 0;
 #pragma unroll
         for (int k = 0; k < DD_AIS_TEMPLATE; ++k) {
-            const int at = (int)(dd_ais_pos(t, k, gd.sps) - base) + DD_AIS_MARGIN;
+            const int at = (int)(dd_bit_mid(t, k, gd.sps) - base) + DD_AIS_MARGIN;
             int s = 0;
             for (int j = -gd.h; j <= gd.h; ++j) s += qs[at + j];
             v[k] = s;
@@ -86,9 +74,7 @@ __global__ void __launch_bounds__(DD_AIS_TILE) k_ais_preamble(const double* __re
         const int mis = __popc(d ^ DD_AIS_PLUS);
         m = mis <= gd.slack ? 1u : (DD_AIS_TEMPLATE - mis <= gd.slack ? 3u : 0u);
     }
-    if (t < n) mask[t] = (uint8_t)m;
-    const int total = dd_sstv_scan256((int)(m & 1u), sh);
-    if (tid == 255) bsum[blockIdx.x] = total;
+    dd_cand_tail(mask, t, n, m, (int)(m & 1u), sh, bsum);
 }
 
 // frames[160 c]: the de-stuffed bits, the first in bit 0 of byte 0 (AIS sends every byte lowest bit first, so these are the
@@ -113,15 +99,7 @@ __global__ void __launch_bounds__(64) k_ais_demod(const double* __restrict__ x, 
         }
         return;
     }
-    const auto value = [&](int k) {
-        const int64_t at = dd_ais_pos(t, k, gd.sps);
-        int s = 0;
-        for (int j = -gd.h; j <= gd.h; ++j) {
-            const int64_t i = at + j;
-            if (i >= 0 && i < n) s += dd_ais_q(x[i]);
-        }
-        return s;
-    };
+    const auto value = [&](int k) { return dd_window_sum(x, n, dd_bit_mid(t, k, gd.sps), gd.h); };
     // the template: S, the decisions' distance from the template, the score
     const int vt = lane < DD_AIS_TEMPLATE ? value(lane) : 0;
     int S = lane < 16 ? vt : 0;
@@ -218,38 +196,14 @@ static int dd_ais_grid(int64_t n, double sps, int w, int slack, DDAisGrid* gd) {
 
 extern "C" int dd_ais_candidates(const double* audio, int64_t n, double sps, int w, int slack, int64_t* list, int64_t cap,
                                  int64_t* count_host, void* stream) {
-    DDAisGrid gd;
-    DD_REQUIRE(cap >= 0 && dd_ais_grid(n, sps, w, slack, &gd),
-               "dd_ais_candidates: need 0 <= n < 2^31, 4 <= sps <= 16, an odd w from 1 to 15, 0 <= slack <= 11 and cap >= 0");
-    DD_REQUIRE(count_host != nullptr, "dd_ais_candidates: count");
-    *count_host = 0;
-    if (n == 0) return DD_OK;
-    DD_REQUIRE(audio != nullptr && (cap == 0 || list != nullptr), "dd_ais_candidates: null buffer");
-    if (gd.nstart == 0) return DD_OK;
+    DDAisGrid gd = {};
+    const bool served = cap >= 0 && dd_ais_grid(n, sps, w, slack, &gd);
     hipStream_t s = dd_stream(stream);
-    const int64_t nb = (gd.nstart + DD_AIS_TILE - 1) / DD_AIS_TILE;
-    const size_t bM = dd_sstv_up16((size_t)n), bB = dd_sstv_up16(((size_t)nb + 1) * 4);
-    DDScratchLock scr;
-    int rc = scr.get(bM + bB, s);
-    if (rc != DD_OK) return rc;
-    uint8_t* mask = (uint8_t*)scr.ptr;
-    int* bsum = (int*)(scr.ptr + bM);
-    hipLaunchKernelGGL(k_ais_preamble, dim3((unsigned)nb), dim3(DD_AIS_TILE), 0, s, audio, n, gd, mask, bsum);
-    DD_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_sstv_scan_tops, dim3(1), dim3(256), 0, s, bsum, nb);
-    DD_LAUNCH_CHECK();
-    int total = 0;
-    DD_HIP_CHECK(hipMemcpyAsync(&total, bsum + nb, sizeof(int), hipMemcpyDeviceToHost, s));
-    DD_HIP_CHECK(hipStreamSynchronize(s));
-    *count_host = total;
-    const int64_t kept = total < cap ? total : cap;
-    if (kept > 0) {
-        hipLaunchKernelGGL(k_adsb_list, dim3((unsigned)nb), dim3(DD_ADSB_TILE), 0, s, (const uint8_t*)mask, n, 1, 1u, (const int*)bsum, list,
-                           kept);
-        DD_LAUNCH_CHECK();
-    }
-    DD_REQUIRE(total <= cap, "dd_ais_candidates: candidate list too small");
-    return DD_OK;
+    return dd_cand_entry("dd_ais_candidates", served,
+                         "dd_ais_candidates: need 0 <= n < 2^31, 4 <= sps <= 16, an odd w from 1 to 15, 0 <= slack <= 11 and cap >= 0", audio, n,
+                         gd.nstart, 1, 1u, list, cap, count_host, s, [=](uint8_t* mask, int* bsum, int64_t nb) {
+                             hipLaunchKernelGGL(k_ais_preamble, dim3((unsigned)nb), dim3(DD_AIS_TILE), 0, s, audio, n, gd, mask, bsum);
+                         });
 }
 
 extern "C" int dd_ais_demod(const double* audio, int64_t n, double sps, int w, const int64_t* list, int64_t m, uint8_t* frames,

@@ -1,13 +1,13 @@
 // POCSAG paging, 2-FSK at 512, 1200 or 2400 baud (beyond the reference; DESIGN.md section 4.24 defines every stage, pocsag.py restates
-// each kernel in NumPy), included by dd_afsk.hip after dd_ais.h, whose quantiser and positions it uses, with dd_adsb.h's list kernel
-// and dd_sstv.h's block scan.  The audio is the FM discriminator's float64 output in radians per sample; everything behind the
-// quantiser is integer, so sums in any order equal the restatement bit for bit.
+// each kernel in NumPy), included by dd_afsk.hip after dd_candidates.h, whose quantiser, positions, LDS prefix sum, tail, list kernel
+// and driver it uses.  The audio is the FM discriminator's float64 output in radians per sample; everything behind the quantiser is
+// integer, so sums in any order equal the restatement bit for bit.
 //
 //   k_pocsag_sync     -- a workgroup stages the quantised audio of 256 starts and the reach of 32 bits in LDS and turns it into its
-//                        exclusive prefix sum in place (32-bit wrap-around: a window's sum is below 2^28, so differences are exact);
+//                        exclusive prefix sum in place (dd_stage_prefix256; 32-bit wrap-around: a window's sum is below 2^28, so differences are exact);
 //                        one thread per start decides the 32 bits of the frame sync codeword against their own mean, two LDS reads
 //                        per bit; a mask byte per sample, a count per workgroup
-//   k_adsb_list       -- (dd_adsb.h) the masks' pass bits as an ordered candidate list below the capacity
+//   k_cand_list       -- (dd_candidates.h) the masks' pass bits as an ordered candidate list below the capacity
 //   k_pocsag_batch    -- one wave per listed start: 544 bits by nine ballots, polarity from the sync codeword, BCH(31,21) + parity
 //                        correction of up to two bits per codeword by a syndrome search across the lanes, two codewords per ballot
 #pragma once
@@ -19,7 +19,6 @@
 #define DD_POCSAG_BITS 544
 #define DD_POCSAG_FSC 0x7CD215D8u     // the frame sync codeword, the first-sent bit in bit 31
 #define DD_POCSAG_GEN 0x769u          // x^10 + x^9 + x^8 + x^6 + x^5 + x^3 + 1 over bits 31 .. 1
-#define DD_POCSAG_SPAN 4368           // prefix entries of a tile at most: 257 + floor(31.5 * 128) + 2 * 38 + 1 = 4366
 
 enum { DD_POCSAG_OK = 0, DD_POCSAG_OUTSIDE = 1 };
 
@@ -47,52 +46,15 @@ constexpr DDPocsagTable dd_pocsag_make_table() {
 
 __constant__ const DDPocsagTable dd_pocsag_table = dd_pocsag_make_table();
 
-// inclusive wrap-around scan of one value per thread over a workgroup of 256; sh holds 4 values
-__device__ __forceinline__ uint32_t dd_pocsag_scan256(uint32_t v, uint32_t* sh) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t a = __shfl_up(v, o);
-        if (lane >= o) v += a;
-    }
-    if (lane == 63) sh[wave] = v;
-    __syncthreads();
-    for (int k = 0; k < wave; ++k) v += sh[k];
-    return v;
-}
-
-// ps[0 .. span) of a workgroup of 256, staged and synchronised, in place into its exclusive wrap-around prefix sum: ps[j] = the sum
-// of the former ps[0 .. j) mod 2^32; synchronised on return.  tops holds 4 values.
-__device__ __forceinline__ void dd_pocsag_prefix256(uint32_t* ps, int span, uint32_t* tops) {
-    const int tid = threadIdx.x;
-    // thread t owns entries [t c, t c + c): c is odd, so a wave's 64 words of one step fall into distinct banks, 32 per lane group
-    const int c = ((span + DD_POCSAG_TILE - 1) / DD_POCSAG_TILE) | 1;
-    const int lo = tid * c < span ? tid * c : span;
-    const int hi = lo + c < span ? lo + c : span;
-    uint32_t own = 0;
-    for (int j = lo; j < hi; ++j) own += ps[j];
-    uint32_t run = dd_pocsag_scan256(own, tops) - own;
-    for (int j = lo; j < hi; ++j) {
-        const uint32_t q = ps[j];
-        ps[j] = run;
-        run += q;
-    }
-    __syncthreads();
-}
-
 __global__ void __launch_bounds__(DD_POCSAG_TILE) k_pocsag_sync(const double* __restrict__ x, int64_t n, const DDPocsagGrid gd,
                                                                 uint8_t* __restrict__ mask, int* __restrict__ bsum) {
-    __shared__ uint32_t ps[DD_POCSAG_SPAN];          // first q, then ps[j] = the sum of q over samples first .. first + j - 1 (mod 2^32)
+    __shared__ uint32_t ps[DD_CAND_SPAN];            // first q, then ps[j] = the sum of q over samples first .. first + j - 1 (mod 2^32)
     __shared__ int sh[256];
     __shared__ uint32_t tops[4];
     const int tid = threadIdx.x;
     const int64_t base = (int64_t)blockIdx.x * DD_POCSAG_TILE;
     const int64_t first = base - gd.h;               // the tile's first sample; 0 outside the audio
-    for (int j = tid; j < gd.span; j += DD_POCSAG_TILE) {
-        const int64_t i = first + j;
-        ps[j] = (i >= 0 && i < n) ? (uint32_t)dd_ais_q(x[i]) : 0u;
-    }
-    __syncthreads();
-    dd_pocsag_prefix256(ps, gd.span, tops);
+    dd_stage_prefix256([&](int64_t i) { return dd_fm_q(x[i]); }, n, first, gd.span, ps, tops);
     const int64_t t = base + tid;
     uint32_t m = 0;
     if (t < gd.nstart) {
@@ -100,7 +62,7 @@ __global__ void __launch_bounds__(DD_POCSAG_TILE) k_pocsag_sync(const double* __
         int64_t S = 0;
 #pragma unroll
         for (int k = 0; k < 32; ++k) {
-            const int at = (int)(dd_ais_pos(t, k, gd.sps) - first);      // h <= at, at + h + 1 < span (a rounding of the sum included)
+            const int at = (int)(dd_bit_mid(t, k, gd.sps) - first);      // h <= at, at + h + 1 < span (a rounding of the sum included)
             v[k] = (int)(ps[at + gd.h + 1] - ps[at - gd.h]);
             S += v[k];
         }
@@ -110,9 +72,7 @@ __global__ void __launch_bounds__(DD_POCSAG_TILE) k_pocsag_sync(const double* __
         const int mis = __popc(~d ^ DD_POCSAG_FSC);                      // a level above the mean is a 0
         m = mis <= gd.slack ? 1u : (32 - mis <= gd.slack ? 3u : 0u);
     }
-    if (t < n) mask[t] = (uint8_t)m;
-    const int total = dd_sstv_scan256((int)(m & 1u), sh);
-    if (tid == 255) bsum[blockIdx.x] = total;
+    dd_cand_tail(mask, t, n, m, (int)(m & 1u), sh, bsum);
 }
 
 // words[17 c]: the batch's codewords in the polarity found, the first-sent bit in bit 31; codeword 0 as received, 1 .. 16 corrected
@@ -139,15 +99,7 @@ __global__ void __launch_bounds__(64) k_pocsag_batch(const double* __restrict__ 
         }
         return;
     }
-    const auto value = [&](int k) {
-        const int64_t at = dd_ais_pos(t, k, gd.sps);
-        int s = 0;
-        for (int j = -gd.h; j <= gd.h; ++j) {
-            const int64_t i = at + j;
-            if (i >= 0 && i < n) s += dd_ais_q(x[i]);
-        }
-        return s;
-    };
+    const auto value = [&](int k) { return dd_window_sum(x, n, dd_bit_mid(t, k, gd.sps), gd.h); };
     // the sync codeword (lanes 0 .. 31): S, the polarity, the score
     const int v0 = value(lane);
     int64_t S = lane < 32 ? v0 : 0;
@@ -239,39 +191,6 @@ static int dd_pocsag_grid(int64_t n, double sps, int w, int slack, int fix, DDPo
     return 1;
 }
 
-// the masks of every sample into scratch or into mask_out, the list below cap; sync(mask, bsum, nb) launches the kernel that tests
-// the nstart starts, 256 per workgroup, and leaves a mask byte per sample and the passes of each workgroup
-template <class Sync>
-static int dd_pocsag_run(int64_t n, int64_t nstart, uint8_t* mask_out, int64_t* list, int64_t cap, int64_t* count_host, hipStream_t s,
-                         Sync sync) {
-    const int64_t nb = (nstart + DD_POCSAG_TILE - 1) / DD_POCSAG_TILE;
-    const size_t bM = mask_out ? 0 : dd_sstv_up16((size_t)n), bB = dd_sstv_up16(((size_t)nb + 1) * 4);
-    DDScratchLock scr;
-    int rc = scr.get(bM + bB, s);
-    if (rc != DD_OK) return rc;
-    uint8_t* mask = mask_out ? mask_out : (uint8_t*)scr.ptr;
-    int* bsum = (int*)(scr.ptr + bM);
-    sync(mask, bsum, nb);
-    DD_LAUNCH_CHECK();
-    if (mask_out) {
-        DD_HIP_CHECK(hipStreamSynchronize(s));                            // (the scratch is given back on return)
-        return DD_OK;
-    }
-    hipLaunchKernelGGL(k_sstv_scan_tops, dim3(1), dim3(256), 0, s, bsum, nb);
-    DD_LAUNCH_CHECK();
-    int total = 0;
-    DD_HIP_CHECK(hipMemcpyAsync(&total, bsum + nb, sizeof(int), hipMemcpyDeviceToHost, s));
-    DD_HIP_CHECK(hipStreamSynchronize(s));
-    *count_host = total;
-    const int64_t kept = total < cap ? total : cap;
-    if (kept > 0) {
-        hipLaunchKernelGGL(k_adsb_list, dim3((unsigned)nb), dim3(DD_ADSB_TILE), 0, s, (const uint8_t*)mask, n, 1, 1u, (const int*)bsum, list,
-                           kept);
-        DD_LAUNCH_CHECK();
-    }
-    return DD_OK;
-}
-
 static auto dd_pocsag_sync_launch(const double* audio, int64_t n, const DDPocsagGrid& gd, hipStream_t s) {
     return [=](uint8_t* mask, int* bsum, int64_t nb) {
         hipLaunchKernelGGL(k_pocsag_sync, dim3((unsigned)nb), dim3(DD_POCSAG_TILE), 0, s, audio, n, gd, mask, bsum);
@@ -280,19 +199,12 @@ static auto dd_pocsag_sync_launch(const double* audio, int64_t n, const DDPocsag
 
 extern "C" int dd_pocsag_candidates(const double* audio, int64_t n, double sps, int w, int slack, int64_t* list, int64_t cap,
                                     int64_t* count_host, void* stream) {
-    DDPocsagGrid gd;
-    DD_REQUIRE(cap >= 0 && dd_pocsag_grid(n, sps, w, slack, 0, &gd),
-               "dd_pocsag_candidates: need 0 <= n < 2^31, 4 <= sps <= 128, an odd w from 1 to 77, 0 <= slack <= 8 and cap >= 0");
-    DD_REQUIRE(count_host != nullptr, "dd_pocsag_candidates: count");
-    *count_host = 0;
-    if (n == 0) return DD_OK;
-    DD_REQUIRE(audio != nullptr && (cap == 0 || list != nullptr), "dd_pocsag_candidates: null buffer");
-    if (gd.nstart == 0) return DD_OK;
+    DDPocsagGrid gd = {};
+    const bool served = cap >= 0 && dd_pocsag_grid(n, sps, w, slack, 0, &gd);
     hipStream_t s = dd_stream(stream);
-    int rc = dd_pocsag_run(n, gd.nstart, nullptr, list, cap, count_host, s, dd_pocsag_sync_launch(audio, n, gd, s));
-    if (rc != DD_OK) return rc;
-    DD_REQUIRE(*count_host <= cap, "dd_pocsag_candidates: candidate list too small");
-    return DD_OK;
+    return dd_cand_entry("dd_pocsag_candidates", served,
+                         "dd_pocsag_candidates: need 0 <= n < 2^31, 4 <= sps <= 128, an odd w from 1 to 77, 0 <= slack <= 8 and cap >= 0", audio,
+                         n, gd.nstart, 1, 1u, list, cap, count_host, s, dd_pocsag_sync_launch(audio, n, gd, s));
 }
 
 extern "C" int dd_pocsag_batches(const double* audio, int64_t n, double sps, int w, int fix, const int64_t* list, int64_t m,
@@ -309,13 +221,10 @@ extern "C" int dd_pocsag_batches(const double* audio, int64_t n, double sps, int
 }
 
 extern "C" int dd_debug_pocsag_masks(const double* audio, int64_t n, double sps, int w, int slack, uint8_t* mask, void* stream) {
-    DDPocsagGrid gd;
-    DD_REQUIRE(dd_pocsag_grid(n, sps, w, slack, 0, &gd),
-               "dd_debug_pocsag_masks: need 0 <= n < 2^31, 4 <= sps <= 128, an odd w from 1 to 77 and 0 <= slack <= 8");
-    if (n == 0) return DD_OK;
-    DD_REQUIRE(audio != nullptr && mask != nullptr, "dd_debug_pocsag_masks: null buffer");
+    DDPocsagGrid gd = {};
+    const bool served = dd_pocsag_grid(n, sps, w, slack, 0, &gd);
     hipStream_t s = dd_stream(stream);
-    DD_HIP_CHECK(hipMemsetAsync(mask, 0, (size_t)n, s));
-    if (gd.nstart == 0) return DD_OK;
-    return dd_pocsag_run(n, gd.nstart, mask, nullptr, 0, nullptr, s, dd_pocsag_sync_launch(audio, n, gd, s));
+    return dd_cand_masks_entry("dd_debug_pocsag_masks", served,
+                               "dd_debug_pocsag_masks: need 0 <= n < 2^31, 4 <= sps <= 128, an odd w from 1 to 77 and 0 <= slack <= 8", audio, n,
+                               gd.nstart, mask, s, dd_pocsag_sync_launch(audio, n, gd, s));
 }

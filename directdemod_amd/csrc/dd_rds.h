@@ -1,17 +1,17 @@
 // RDS on broadcast FM, 1187.5 bit/s differential biphase on a 57 kHz subcarrier of the multiplex (beyond the reference; DESIGN.md
-// section 4.27 defines every stage, rds.py restates each kernel in NumPy), included by dd_afsk.hip after dd_rs41.h; it uses
-// dd_pocsag.h's LDS prefix sum and list driver with dd_adsb.h's list kernel and dd_sstv.h's block scan.  The multiplex is the FM
+// section 4.27 defines every stage, rds.py restates each kernel in NumPy), included by dd_afsk.hip after dd_candidates.h, whose LDS
+// prefix sum, tail, list kernel and driver it uses; the quantiser and the positions are its own.  The multiplex is the FM
 // discriminator's float64 output in radians per sample; everything behind the quantiser is integer, so sums in any order equal the
 // restatement bit for bit.  Positions are float64 products and sums rounded one by one (the unit is built without contraction).
 //
 //   k_rds_baseband    -- a workgroup stages the quantised multiplex of 256 outputs in LDS beside the 1024-entry phasor table; a thread
 //                        per output sums D products q * table[phase] in int64 and stores the sum >> 10 as an int32 pair
 //   k_rds_sync        -- a workgroup stages the baseband of 256 starts and the reach of 105 bit boundaries in LDS and turns both
-//                        components into exclusive prefix sums in place (dd_pocsag_prefix256; 32-bit wrap-around: |z| < 2^30, so
+//                        components into exclusive prefix sums in place (dd_prefix256; 32-bit wrap-around: |z| < 2^30, so
 //                        differences are exact); one thread per start takes the 105 half-bit differences, three LDS reads per
 //                        component, decides 104 bits by the sign of Re(z[p_k] conj(z[p_k-1])) and runs them through the
 //                        remainder register of four 26-bit blocks; a mask byte per start, a count per workgroup
-//   k_adsb_list       -- (dd_adsb.h) the masks' pass bits as an ordered candidate list below the capacity
+//   k_cand_list       -- (dd_candidates.h) the masks' pass bits as an ordered candidate list below the capacity
 //   k_rds_groups      -- one wave per listed start: 104 bits by two ballots, the four remainders as wave XORs of lone-bit
 //                        remainders, burst repair searched a lane per position and pattern
 //   k_rds_halfbit, k_rds_repair -- (diagnostics) the half-bit differences of every sample; the repair of loose 26-bit words
@@ -103,15 +103,15 @@ __global__ void __launch_bounds__(DD_RDS_TILE) k_rds_baseband(const double* __re
 // pr, pi[0 .. span) = the exclusive wrap-around prefix sums of the two components of b[first .. first + span), 0 outside the data
 __device__ __forceinline__ void dd_rds_stage(const int2* __restrict__ b, int64_t m, int64_t first, int span, uint32_t* pr, uint32_t* pi,
                                              uint32_t* tops) {
-    for (int j = threadIdx.x; j < span; j += DD_RDS_TILE) {
+    for (int j = threadIdx.x; j < span; j += DD_RDS_TILE) {                 // (one read serves both components: not dd_stage_prefix256)
         const int64_t i = first + j;
         const int2 v = (i >= 0 && i < m) ? b[i] : make_int2(0, 0);
         pr[j] = (uint32_t)v.x;
         pi[j] = (uint32_t)v.y;
     }
     __syncthreads();
-    dd_pocsag_prefix256(pr, span, tops);
-    dd_pocsag_prefix256(pi, span, tops);
+    dd_prefix256(pr, span, tops);
+    dd_prefix256(pi, span, tops);
 }
 
 // z[p] = the sum of b[p .. p + h - 1] less the sum of b[p - h .. p - 1] from the prefix sums, at = p - first; 0 below p = h
@@ -153,9 +153,7 @@ __global__ void __launch_bounds__(DD_RDS_TILE) k_rds_sync(const int2* __restrict
         }
     }
     const uint32_t pass = score >= (uint32_t)gd.clean ? 1u : 0u;
-    if (t < gd.m) mask[t] = (uint8_t)(score << 1 | pass);
-    const int total = dd_sstv_scan256((int)pass, sh);
-    if (tid == 255) bsum[blockIdx.x] = total;
+    dd_cand_tail(mask, t, gd.m, score << 1 | pass, (int)pass, sh, bsum);
 }
 
 // z[2 p], z[2 p + 1] for every sample p (a diagnostic): 0 below h and beyond m - h
@@ -319,18 +317,11 @@ static auto dd_rds_sync_launch(const int32_t* b, const DDRdsGrid& gd, hipStream_
 
 extern "C" int dd_rds_candidates(const int32_t* b, int64_t m, double sps, int clean, int64_t* list, int64_t cap, int64_t* count_host,
                                  void* stream) {
-    DDRdsGrid gd;
-    DD_REQUIRE(cap >= 0 && dd_rds_grid(m, sps, clean, 0, &gd),
-               "dd_rds_candidates: need 0 <= m < 2^31, 12 <= sps <= 32, 2 <= clean <= 4 and cap >= 0");
-    DD_REQUIRE(count_host != nullptr, "dd_rds_candidates: count");
-    *count_host = 0;
-    if (m == 0) return DD_OK;
-    DD_REQUIRE(b != nullptr && (cap == 0 || list != nullptr), "dd_rds_candidates: null buffer");
+    DDRdsGrid gd = {};
+    const bool served = cap >= 0 && dd_rds_grid(m, sps, clean, 0, &gd);
     hipStream_t s = dd_stream(stream);
-    int rc = dd_pocsag_run(m, m, nullptr, list, cap, count_host, s, dd_rds_sync_launch(b, gd, s));
-    if (rc != DD_OK) return rc;
-    DD_REQUIRE(*count_host <= cap, "dd_rds_candidates: candidate list too small");
-    return DD_OK;
+    return dd_cand_entry("dd_rds_candidates", served, "dd_rds_candidates: need 0 <= m < 2^31, 12 <= sps <= 32, 2 <= clean <= 4 and cap >= 0", b,
+                         m, m, 1, 1u, list, cap, count_host, s, dd_rds_sync_launch(b, gd, s));
 }
 
 extern "C" int dd_rds_groups(const int32_t* b, int64_t m, double sps, int fix, const int64_t* list, int64_t count, uint16_t* words,
@@ -346,12 +337,11 @@ extern "C" int dd_rds_groups(const int32_t* b, int64_t m, double sps, int fix, c
 }
 
 extern "C" int dd_debug_rds_masks(const int32_t* b, int64_t m, double sps, int clean, uint8_t* mask, void* stream) {
-    DDRdsGrid gd;
-    DD_REQUIRE(dd_rds_grid(m, sps, clean, 0, &gd), "dd_debug_rds_masks: need 0 <= m < 2^31, 12 <= sps <= 32 and 2 <= clean <= 4");
-    if (m == 0) return DD_OK;
-    DD_REQUIRE(b != nullptr && mask != nullptr, "dd_debug_rds_masks: null buffer");
+    DDRdsGrid gd = {};
+    const bool served = dd_rds_grid(m, sps, clean, 0, &gd);
     hipStream_t s = dd_stream(stream);
-    return dd_pocsag_run(m, m, mask, nullptr, 0, nullptr, s, dd_rds_sync_launch(b, gd, s));
+    return dd_cand_masks_entry("dd_debug_rds_masks", served, "dd_debug_rds_masks: need 0 <= m < 2^31, 12 <= sps <= 32 and 2 <= clean <= 4", b, m, m,
+                               mask, s, dd_rds_sync_launch(b, gd, s));
 }
 
 extern "C" int dd_debug_rds_halfbit(const int32_t* b, int64_t m, double sps, int32_t* z, void* stream) {

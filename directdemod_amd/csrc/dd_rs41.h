@@ -1,20 +1,20 @@
 // Vaisala RS41 radiosonde telemetry, 2-GFSK at 4800 baud (beyond the reference; DESIGN.md section 4.26 defines every stage, rs41.py
-// restates each kernel in NumPy), included by dd_afsk.hip after dd_pocsag.h, whose LDS prefix sum and list driver it uses with dd_ais.h's
-// quantiser and positions, and after dd_lrpt_rs.h, whose wave decodes the two RS(255,231) codewords.  The audio is the FM
+// restates each kernel in NumPy), included by dd_afsk.hip after dd_candidates.h, whose quantiser, positions, LDS prefix sum, tail, list
+// kernel and driver it uses, and after dd_lrpt_rs.h, whose wave decodes the two RS(255,231) codewords.  The audio is the FM
 // discriminator's float64 output in radians per sample; everything behind the quantiser is integer, so sums in any order equal the
 // restatement bit for bit.
 //
 //   k_rs41_sync       -- a workgroup stages the quantised audio of 256 starts and the reach of 64 bits in LDS and turns it into its
-//                        exclusive prefix sum in place (dd_pocsag_prefix256; a window's sum is below 2^27, so differences are exact);
+//                        exclusive prefix sum in place (dd_stage_prefix256; a window's sum is below 2^27, so differences are exact);
 //                        one thread per start decides the 64 bits of the header against the midpoint of its two classes' means, two
 //                        LDS reads per bit; a mask byte per sample, a count per workgroup
-//   k_adsb_list       -- (dd_adsb.h) the masks' pass bits as an ordered candidate list below the capacity
+//   k_cand_list       -- (dd_candidates.h) the masks' pass bits as an ordered candidate list below the capacity
 //   k_rs41_frame      -- one wave per listed start: the header's midpoint and polarity, 40 or 65 ballots of 8 bytes each, the
 //                        whitening mask, the length from byte 56, the two codewords through dd_rs_wave<12, 1, 0>
 //   k_rs41_rs_words   -- (a diagnostic) one wave per 255-byte word through dd_rs_wave<12, 1, 0>
 #pragma once
 
-#define DD_RS41_TILE DD_POCSAG_TILE   // starts per workgroup (mirrored by rs41.TILE)
+#define DD_RS41_TILE 256              // starts per workgroup (mirrored by rs41.TILE)
 #define DD_RS41_W_MAX 39              // samples summed per bit value at most: the odd number nearest 0.6 * 64
 #define DD_RS41_SLACK_MAX 11          // the header slid into the preamble is 24 or more places from itself and its inverse: 11 + 11 < 24
 #define DD_RS41_HDR 0xF812962211CAB610ull   // the header on the air, first-sent bit k in bit k: 25 ones, 39 zeros
@@ -26,7 +26,7 @@
 #define DD_RS41_T 12                  // RS(255,231) over 0x11D, roots alpha^0 .. alpha^23
 #define DD_RS41_META 6
 
-static_assert(DD_RS41_TILE + 63 * 64 + 32 + DD_RS41_W_MAX + 2 <= DD_POCSAG_SPAN, "a tile's span fits POCSAG's LDS array");
+static_assert(DD_RS41_TILE + 63 * 64 + 32 + DD_RS41_W_MAX + 2 <= DD_CAND_SPAN, "a tile's span fits the LDS array");
 
 enum { DD_RS41_OK = 0, DD_RS41_OUTSIDE = 1 };
 
@@ -47,18 +47,13 @@ __constant__ const uint8_t dd_rs41_mask[64] = {
 // low when strictly below.  Polarity 0 reads high as 1; polarity 1 is the same test of the negated audio, which reads low as 1.
 __global__ void __launch_bounds__(DD_RS41_TILE) k_rs41_sync(const double* __restrict__ x, int64_t n, const DDRs41Grid gd,
                                                             uint8_t* __restrict__ mask, int* __restrict__ bsum) {
-    __shared__ uint32_t ps[DD_POCSAG_SPAN];          // first q, then ps[j] = the sum of q over samples first .. first + j - 1 (mod 2^32)
+    __shared__ uint32_t ps[DD_CAND_SPAN];            // first q, then ps[j] = the sum of q over samples first .. first + j - 1 (mod 2^32)
     __shared__ int sh[256];
     __shared__ uint32_t tops[4];
     const int tid = threadIdx.x;
     const int64_t base = (int64_t)blockIdx.x * DD_RS41_TILE;
     const int64_t first = base - gd.h;               // the tile's first sample; 0 outside the audio
-    for (int j = tid; j < gd.span; j += DD_RS41_TILE) {
-        const int64_t i = first + j;
-        ps[j] = (i >= 0 && i < n) ? (uint32_t)dd_ais_q(x[i]) : 0u;
-    }
-    __syncthreads();
-    dd_pocsag_prefix256(ps, gd.span, tops);
+    dd_stage_prefix256([&](int64_t i) { return dd_fm_q(x[i]); }, n, first, gd.span, ps, tops);
     const int64_t t = base + tid;
     uint32_t m = 0;
     if (t < gd.nstart) {
@@ -66,7 +61,7 @@ __global__ void __launch_bounds__(DD_RS41_TILE) k_rs41_sync(const double* __rest
         int64_t S1 = 0, S0 = 0;
 #pragma unroll
         for (int k = 0; k < 64; ++k) {
-            const int at = (int)(dd_ais_pos(t, k, gd.sps) - first);      // h <= at, at + h + 1 < span (a rounding of the sum included)
+            const int at = (int)(dd_bit_mid(t, k, gd.sps) - first);      // h <= at, at + h + 1 < span (a rounding of the sum included)
             v[k] = (int)(ps[at + gd.h + 1] - ps[at - gd.h]);
             if ((DD_RS41_HDR >> k) & 1ull) S1 += v[k];
             else S0 += v[k];
@@ -81,9 +76,7 @@ __global__ void __launch_bounds__(DD_RS41_TILE) k_rs41_sync(const double* __rest
         }
         m = __popcll(hi ^ DD_RS41_HDR) <= gd.slack ? 1u : (__popcll(lo ^ DD_RS41_HDR) <= gd.slack ? 3u : 0u);
     }
-    if (t < n) mask[t] = (uint8_t)m;
-    const int total = dd_sstv_scan256((int)(m & 1u), sh);
-    if (tid == 255) bsum[blockIdx.x] = total;
+    dd_cand_tail(mask, t, n, m, (int)(m & 1u), sh, bsum);
 }
 
 // the wave's LDS stores before, its LDS loads behind: one wave is the whole workgroup, so no barrier is needed (dd_rs_wave's rule)
@@ -108,7 +101,7 @@ __global__ void __launch_bounds__(64) k_rs41_frame(const double* __restrict__ x,
     uint8_t* fo = fixed + (int64_t)blockIdx.x * DD_RS41_EXT;
     uint8_t* ro = recv + (int64_t)blockIdx.x * DD_RS41_EXT;
     int* mt = meta + (int64_t)blockIdx.x * DD_RS41_META;
-    const auto fits = [&](int bytes) { return dd_ais_pos(t, 8 * bytes - 1, gd.sps) + gd.h < n; };
+    const auto fits = [&](int bytes) { return dd_bit_mid(t, 8 * bytes - 1, gd.sps) + gd.h < n; };
     if (t < 0 || t >= n || !fits(DD_RS41_STD)) {                          // (uniform over the wave)
         for (int i = lane; i < DD_RS41_EXT; i += 64) fo[i] = ro[i] = 0;
         if (lane < DD_RS41_META) mt[lane] = lane == 0 ? DD_RS41_OUTSIDE : 0;
@@ -118,15 +111,7 @@ __global__ void __launch_bounds__(64) k_rs41_frame(const double* __restrict__ x,
     for (int i = lane; i < 256; i += 64) lg[i] = dd_rs_tables_11d.lg[i];
     for (int i = lane; i < 8 * 65; i += 64) rx[i] = 0;
     dd_rs41_wave_sync();
-    const auto value = [&](int k) {
-        const int64_t at = dd_ais_pos(t, k, gd.sps);
-        int s = 0;
-        for (int j = -gd.h; j <= gd.h; ++j) {
-            const int64_t i = at + j;
-            if (i >= 0 && i < n) s += dd_ais_q(x[i]);
-        }
-        return s;
-    };
+    const auto value = [&](int k) { return dd_window_sum(x, n, dd_bit_mid(t, k, gd.sps), gd.h); };
     // the header (a lane per place): the midpoint, the polarity
     const int v0 = value(lane);
     const bool one = (DD_RS41_HDR >> lane) & 1ull;
@@ -245,19 +230,12 @@ static auto dd_rs41_sync_launch(const double* audio, int64_t n, const DDRs41Grid
 
 extern "C" int dd_rs41_candidates(const double* audio, int64_t n, double sps, int w, int slack, int64_t* list, int64_t cap,
                                   int64_t* count_host, void* stream) {
-    DDRs41Grid gd;
-    DD_REQUIRE(cap >= 0 && dd_rs41_grid(n, sps, w, slack, &gd),
-               "dd_rs41_candidates: need 0 <= n < 2^31, 4 <= sps <= 64, an odd w from 1 to 39, 0 <= slack <= 11 and cap >= 0");
-    DD_REQUIRE(count_host != nullptr, "dd_rs41_candidates: count");
-    *count_host = 0;
-    if (n == 0) return DD_OK;
-    DD_REQUIRE(audio != nullptr && (cap == 0 || list != nullptr), "dd_rs41_candidates: null buffer");
-    if (gd.nstart == 0) return DD_OK;
+    DDRs41Grid gd = {};
+    const bool served = cap >= 0 && dd_rs41_grid(n, sps, w, slack, &gd);
     hipStream_t s = dd_stream(stream);
-    int rc = dd_pocsag_run(n, gd.nstart, nullptr, list, cap, count_host, s, dd_rs41_sync_launch(audio, n, gd, s));
-    if (rc != DD_OK) return rc;
-    DD_REQUIRE(*count_host <= cap, "dd_rs41_candidates: candidate list too small");
-    return DD_OK;
+    return dd_cand_entry("dd_rs41_candidates", served,
+                         "dd_rs41_candidates: need 0 <= n < 2^31, 4 <= sps <= 64, an odd w from 1 to 39, 0 <= slack <= 11 and cap >= 0", audio, n,
+                         gd.nstart, 1, 1u, list, cap, count_host, s, dd_rs41_sync_launch(audio, n, gd, s));
 }
 
 extern "C" int dd_rs41_frames(const double* audio, int64_t n, double sps, int w, const int64_t* list, int64_t m, uint8_t* fixed,
@@ -274,15 +252,12 @@ extern "C" int dd_rs41_frames(const double* audio, int64_t n, double sps, int w,
 }
 
 extern "C" int dd_debug_rs41_masks(const double* audio, int64_t n, double sps, int w, int slack, uint8_t* mask, void* stream) {
-    DDRs41Grid gd;
-    DD_REQUIRE(dd_rs41_grid(n, sps, w, slack, &gd),
-               "dd_debug_rs41_masks: need 0 <= n < 2^31, 4 <= sps <= 64, an odd w from 1 to 39 and 0 <= slack <= 11");
-    if (n == 0) return DD_OK;
-    DD_REQUIRE(audio != nullptr && mask != nullptr, "dd_debug_rs41_masks: null buffer");
+    DDRs41Grid gd = {};
+    const bool served = dd_rs41_grid(n, sps, w, slack, &gd);
     hipStream_t s = dd_stream(stream);
-    DD_HIP_CHECK(hipMemsetAsync(mask, 0, (size_t)n, s));
-    if (gd.nstart == 0) return DD_OK;
-    return dd_pocsag_run(n, gd.nstart, mask, nullptr, 0, nullptr, s, dd_rs41_sync_launch(audio, n, gd, s));
+    return dd_cand_masks_entry("dd_debug_rs41_masks", served,
+                               "dd_debug_rs41_masks: need 0 <= n < 2^31, 4 <= sps <= 64, an odd w from 1 to 39 and 0 <= slack <= 11", audio, n,
+                               gd.nstart, mask, s, dd_rs41_sync_launch(audio, n, gd, s));
 }
 
 extern "C" int dd_debug_rs41_rs(const uint8_t* words, int64_t m, int first_valid, uint8_t* fixed, int32_t* errors, void* stream) {

@@ -5,7 +5,8 @@
 //
 //   k_sstv_lag        -- one thread per output: z[n] = sum_k h[k] x[n-k] (complex taps, k ascending), d[n] = z[n] conj(z[n-1])
 //   k_sstv_classes    -- one thread per sample: the tone class of d[n] by cross-product signs against six band-edge phasors
-//   k_sstv_scan_*     -- P[i] = how many of v[0..i) equal a value: block sums, their scan, the blocks' own scans
+//   k_sstv_scan_*     -- P[i] = how many of v[0..i) equal a value: block sums, their scan (dd_candidates.h's k_scan_tops), the blocks'
+//                        own scans
 //   k_sstv_run_*      -- maximal runs of window counts >= a threshold, one wave per run for the first index of its maximum
 //   k_sstv_pixels     -- one wave per segment, one lane per pixel: sum of d over the pixel, polynomial arctangent, level
 //   k_sstv_color      -- one thread per pixel column of a line pair: Y0, Cr, Cb, Y1 -> two RGB rows, integer arithmetic
@@ -69,20 +70,6 @@ __global__ void __launch_bounds__(256) k_sstv_classes(const double2* __restrict_
     cls[i] = (int8_t)c;
 }
 
-// inclusive scan of one int per thread over a workgroup of 256; sh holds 256 ints
-__device__ __forceinline__ int dd_sstv_scan256(int v, int* sh) {
-    const int t = threadIdx.x;
-    sh[t] = v;
-    __syncthreads();
-    for (int o = 1; o < 256; o <<= 1) {
-        const int a = t >= o ? sh[t - o] : 0;
-        __syncthreads();
-        sh[t] += a;
-        __syncthreads();
-    }
-    return sh[t];
-}
-
 // bsum[b] = how many of v[1024 b .. 1024 b + 1024) equal target
 __global__ void __launch_bounds__(256) k_sstv_scan_blocks(const int8_t* __restrict__ v, int64_t n, int target, int* __restrict__ bsum) {
     __shared__ int sh[256];
@@ -90,23 +77,8 @@ __global__ void __launch_bounds__(256) k_sstv_scan_blocks(const int8_t* __restri
     int c = 0;
 #pragma unroll
     for (int j = 0; j < 4; ++j) c += (at + j < n && v[at + j] == target) ? 1 : 0;
-    const int s = dd_sstv_scan256(c, sh);
+    const int s = dd_scan256(c, sh);
     if (threadIdx.x == 255) bsum[blockIdx.x] = s;
-}
-
-// bsum[nb] -> its exclusive scan in place, the total in bsum[nb]; one workgroup of 256
-__global__ void __launch_bounds__(256) k_sstv_scan_tops(int* __restrict__ bsum, int64_t nb) {
-    __shared__ int sh[256];
-    int carry = 0;
-    for (int64_t base = 0; base < nb; base += 256) {
-        const int64_t b = base + threadIdx.x;
-        const int v = b < nb ? bsum[b] : 0;
-        const int s = dd_sstv_scan256(v, sh);
-        if (b < nb) bsum[b] = carry + s - v;
-        carry += sh[255];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) bsum[nb] = carry;
 }
 
 // P[0] = 0, P[i + 1] = how many of v[0..i] equal target; boff = the scanned block sums
@@ -120,7 +92,7 @@ __global__ void __launch_bounds__(256) k_sstv_scan_write(const int8_t* __restric
         f[j] = (at + j < n && v[at + j] == target) ? 1 : 0;
         c += f[j];
     }
-    int run = boff[blockIdx.x] + dd_sstv_scan256(c, sh) - c;
+    int run = boff[blockIdx.x] + dd_scan256(c, sh) - c;
     if (blockIdx.x == 0 && threadIdx.x == 0) P[0] = 0;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -134,7 +106,7 @@ static int dd_sstv_scan(const int8_t* v, int64_t n, int target, int* bsum, int* 
     const int64_t nb = (n + DD_SSTV_SCAN - 1) / DD_SSTV_SCAN;
     hipLaunchKernelGGL(k_sstv_scan_blocks, dim3((unsigned)nb), dim3(256), 0, s, v, n, target, bsum);
     DD_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_sstv_scan_tops, dim3(1), dim3(256), 0, s, bsum, nb);
+    hipLaunchKernelGGL(k_scan_tops, dim3(1), dim3(256), 0, s, bsum, nb);
     DD_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_sstv_scan_write, dim3((unsigned)nb), dim3(256), 0, s, v, n, target, (const int*)bsum, P);
     DD_LAUNCH_CHECK();
@@ -304,8 +276,6 @@ extern "C" int dd_sstv_classes(const void* d, int64_t n, const double* edges_hos
     return DD_OK;
 }
 
-static inline size_t dd_sstv_up16(size_t b) { return (b + 15) & ~(size_t)15; }
-
 extern "C" int dd_sstv_runs(const int8_t* cls, int64_t n, int target, int64_t window, int64_t thresh, int64_t* pos, int64_t cap,
                             int64_t* count_host, void* stream) {
     DD_REQUIRE(n >= 0 && cap >= 0 && n <= 0x7FFFFFF0LL, "dd_sstv_runs: sizes");
@@ -317,8 +287,8 @@ extern "C" int dd_sstv_runs(const int8_t* cls, int64_t n, int target, int64_t wi
     DD_REQUIRE(cls != nullptr && (cap == 0 || pos != nullptr), "dd_sstv_runs: null buffer");
     hipStream_t s = dd_stream(stream);
     const int64_t m = n - window + 1;
-    const size_t bP = dd_sstv_up16(((size_t)n + 1) * 4), bQ = dd_sstv_up16(((size_t)m + 1) * 4), bM = dd_sstv_up16((size_t)m),
-                 bB = dd_sstv_up16(((size_t)n / DD_SSTV_SCAN + 2) * 4);
+    const size_t bP = dd_up16(((size_t)n + 1) * 4), bQ = dd_up16(((size_t)m + 1) * 4), bM = dd_up16((size_t)m),
+                 bB = dd_up16(((size_t)n / DD_SSTV_SCAN + 2) * 4);
     DDScratchLock scr;
     int rc = scr.get(bP + bQ + bM + bB, s);
     if (rc != DD_OK) return rc;

@@ -11,11 +11,10 @@ A block starts cold behind a short pre-key: nothing has to pull in, so every blo
 INTEGRATION.md lists the limits.
 """
 import logging
-import time
 
 import numpy as np
 
-from . import _hip, acars, ais, decode_afsk1200 as _afsk1200, filters
+from . import _channel, _hip, acars
 from .decode_ais import channel_names
 
 
@@ -39,24 +38,18 @@ class decode_acars:
     (source.read_device_raw)."""
 
     def __init__(self, sigsrc, offsets, bw=None, cut=None, slack=2, fix=2, use_device_raw=True):
-        self.__bw = 48000 if bw is None else bw
-        self.__cut = acars.CUT if cut is None else float(cut)
+        bw = 48000 if bw is None else bw
+        cut = acars.CUT if cut is None else float(cut)
         self.__offsets = [float(o) for o in np.atleast_1d(offsets)]
         self.__channels = channel_names(len(self.__offsets))
-        self.__fronts = []
+        self.__front = None
         self.__audios = None
         self.__slack, self.__fix = slack, fix
         acars.params(acars.BAUD * acars.SPS_MIN, None, slack, fix)           # ValueError for a slack or a fix out of range
         if sigsrc is not None:
-            fs = sigsrc.sampFreq
-            if self.__bw <= 0 or fs < self.__bw:
-                raise ValueError("decode_acars: a bandwidth of %r S/s cannot be cut from %r S/s" % (self.__bw, fs))
-            self.__rate = fs / int(fs / self.__bw)
-            _rates(self.__rate, fs)
-            if not 0 < self.__cut < self.__rate / 2.0:
-                raise ValueError("decode_acars: a cut-off of %r Hz does not fit an audio rate of %r S/s" % (self.__cut, self.__rate))
-            self.__taps = ais.window_taps(fs)
-            self.__fronts = [_afsk1200.decode_afsk1200(sigsrc, o, self.__bw, use_device_raw) for o in self.__offsets]
+            self.__front = _channel.Channels("decode_acars", sigsrc, self.__offsets, bw, cut, use_device_raw,
+                                             lambda rate: _rates(rate, sigsrc.sampFreq))
+            self.__rate = self.__front.rate
         self.__done = False
         self.__blocks = []
         self.__info = {}
@@ -128,30 +121,19 @@ class decode_acars:
         """the channels' envelopes as float64 device arrays (the front end runs once)"""
         _hip.require_gpu()
         if self.__audios is None:
-            self.__audios = []
-            for front in self.__fronts:
-                sig = front._baseband(self.__taps)
-                sig.filter(filters.lowpass(self.__rate, self.__cut, storeState=False))
-                self.__audios.append(_magnitude(sig.device_signal))
-        self.__audios = [a if isinstance(a, _hip.DevArray) else _hip.DevArray.from_host(a) for a in self.__audios]
-        for a in self.__audios:
-            if a.dtype != np.dtype(np.float64):
-                raise TypeError("float64 audio expected, got %s" % a.dtype)
+            self.__audios = self.__front.audios(lambda sig: _magnitude(sig.device_signal))
+        self.__audios = _channel.on_device(self.__audios)
         return self.__audios
 
     def _decode(self):
         if self.__done:
             return
         _hip.require_gpu()
-        laps = {"_t": time.perf_counter()}
-        ops = acars.DeviceOps(laps)
+        ops = acars.DeviceOps({})
         audios = self.audio()
         ops.lap("front_end")
         self.__blocks, self.__info, self.__cand = acars.decode(audios, self.__rate, self.__channels, self.__slack, self.__fix, ops=ops)
-        laps.pop("_t")
-        for name in ("candidates", "blocks", "host"):
-            laps.setdefault(name, 0.0)
-        self.timings = laps
+        self.timings = ops.finish("candidates", "blocks", "host")
         for b in self.__blocks:
             logging.info("%s (at %.4f s, %d bits repaired)", acars.line(b), b["t"], b["corrected"])
         self.__done = True

@@ -9,11 +9,11 @@ INTEGRATION.md lists the limits: recordings at exactly 2.0 MS/s lose frames whos
 strictly between 2.0 and 2.4 MS/s lose most frames.
 """
 import logging
-import time
 
 import numpy as np
 
 from . import _hip, adsb
+from ._burst import Laps
 
 
 class decode_adsb:
@@ -115,13 +115,7 @@ class decode_adsb:
             return
         _hip.require_gpu()
         laps = {}
-        mark = [time.perf_counter()]
-
-        def lap(name):
-            _hip.sync()
-            now = time.perf_counter()
-            laps[name] = laps.get(name, 0.0) + now - mark[0]
-            mark[0] = now
+        lap = Laps(laps).lap
         rate, Q = self.__rate, self.__Q
         n = self.__sigsrc.length if self.__raw is None else (self.__raw.n if isinstance(self.__raw, _hip.DevArray) else len(self.__raw))
         dets, passed = [], 0

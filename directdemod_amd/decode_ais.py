@@ -9,11 +9,10 @@ A burst is a single transmission of 26.7 ms with 24 training bits in front: noth
 recording cold is decoded like any other.  INTEGRATION.md lists the limits.
 """
 import logging
-import time
 
 import numpy as np
 
-from . import _hip, ais, comm, decode_afsk1200 as _afsk1200, demod_fm, filters
+from . import _channel, _hip, ais
 
 
 def channel_names(count):
@@ -28,23 +27,17 @@ class decode_ais:
     use_device_raw: read the recording as raw u8 pairs resident on the device when the source offers it (source.read_device_raw)."""
 
     def __init__(self, sigsrc, offsets=(-25000.0, 25000.0), bw=None, cut=None, slack=0, use_device_raw=True):
-        self.__bw = 48000 if bw is None else bw
-        self.__cut = ais.CUT if cut is None else float(cut)
+        bw = 48000 if bw is None else bw
+        cut = ais.CUT if cut is None else float(cut)
         self.__offsets = [float(o) for o in np.atleast_1d(offsets)]
         self.__channels = channel_names(len(self.__offsets))
-        self.__fronts = []
+        self.__front = None
         self.__audios = None
         self.__slack = slack
         if sigsrc is not None:
-            fs = sigsrc.sampFreq
-            if self.__bw <= 0 or fs < self.__bw:
-                raise ValueError("decode_ais: a bandwidth of %r S/s cannot be cut from %r S/s" % (self.__bw, fs))
-            self.__rate = fs / int(fs / self.__bw)
-            ais.params(self.__rate, None, slack)         # ValueError unless it gives 4 to 16 samples per bit
-            if not 0 < self.__cut < self.__rate / 2.0:
-                raise ValueError("decode_ais: a cut-off of %r Hz does not fit an audio rate of %r S/s" % (self.__cut, self.__rate))
-            self.__taps = ais.window_taps(fs)
-            self.__fronts = [_afsk1200.decode_afsk1200(sigsrc, o, self.__bw, use_device_raw) for o in self.__offsets]
+            self.__front = _channel.Channels("decode_ais", sigsrc, self.__offsets, bw, cut, use_device_raw,
+                                             lambda rate: ais.params(rate, None, slack))     # (4 to 16 samples per bit)
+            self.__rate = self.__front.rate
         self.__done = False
         self.__msgs = []
         self.__info = {}
@@ -121,29 +114,19 @@ class decode_ais:
         """the channels' FM-demodulated audio as float64 device arrays (the front end runs once)"""
         _hip.require_gpu()
         if self.__audios is None:
-            self.__audios = []
-            for front in self.__fronts:
-                sig = front._baseband(self.__taps)
-                sig.filter(filters.lowpass(self.__rate, self.__cut, storeState=False))
-                sig.funcApply(demod_fm.demod_fm().demod)
-                self.__audios.append(comm._convert(sig.device_signal, np.float64))
-        self.__audios = [a if isinstance(a, _hip.DevArray) else _hip.DevArray.from_host(a) for a in self.__audios]
-        for a in self.__audios:
-            if a.dtype != np.dtype(np.float64):
-                raise TypeError("float64 audio expected, got %s" % a.dtype)
+            self.__audios = self.__front.audios(_channel.fm_audio)
+        self.__audios = _channel.on_device(self.__audios)
         return self.__audios
 
     def _decode(self):
         if self.__done:
             return
         _hip.require_gpu()
-        laps = {"_t": time.perf_counter()}
-        ops = ais.DeviceOps(laps)
+        ops = ais.DeviceOps({})
         audios = self.audio()
         ops.lap("front_end")
         self.__msgs, self.__info, self.__cand = ais.decode(audios, self.__rate, self.__channels, self.__slack, ops=ops)
-        laps.pop("_t")
-        self.timings = laps
+        self.timings = ops.finish()
         for m in self.__msgs:
             logging.info("AIS %s at %.4f s: type %d, MMSI %09d, %d bits: %s", m["channel"], m["t"], m["type"], m["mmsi"], m["nbits"],
                          " ".join(m["nmea"]))

@@ -11,11 +11,11 @@ decode_lrpt's chain with stagger="auto": at two of the walk's four carrier-phase
 Nothing here has been verified against a recording of a satellite: every stage is defined in DESIGN.md and tested against its NumPy
 restatement on synthesised recordings.
 """
-import time
 
 import numpy as np
 
 from . import _hip, chunker, comm, constants, filters, lrpt, oqpsk
+from ._burst import Laps
 from .decode_lrpt import decode_lrpt
 
 
@@ -62,14 +62,7 @@ class decode_meteorm2x(decode_lrpt):
         _hip.require_gpu()
         src = self._sigsrc
         t = dict(front_end=0.0, walk=0.0)
-        t0 = time.perf_counter()
-
-        def lap(name):
-            nonlocal t0
-            _hip.sync()
-            now = time.perf_counter()
-            t[name] += now - t0
-            t0 = now
+        lap = Laps(t).lap
         ck = chunker.chunker(src, self._chunk_size)
         read = src.read
         if self._use_raw and hasattr(src, "read_device_raw") and src.length > 0 and src.read_device_raw(0, 1) is not None:

@@ -10,11 +10,10 @@ Every batch carries its own sync codeword: nothing has to pull in, so a recordin
 from its next batch on.  INTEGRATION.md lists the limits.
 """
 import logging
-import time
 
 import numpy as np
 
-from . import _hip, ais, comm, decode_afsk1200 as _afsk1200, demod_fm, filters, pocsag
+from . import _channel, _hip, pocsag
 
 
 class decode_pocsag:
@@ -27,8 +26,8 @@ class decode_pocsag:
 
     def __init__(self, sigsrc, offset, bw=None, bauds=pocsag.BAUDS, cut=None, slack=2, fix=2, follow=2, content="auto",
                  use_device_raw=True):
-        self.__bw = 48000 if bw is None else bw
-        self.__cut = pocsag.CUT if cut is None else float(cut)
+        bw = 48000 if bw is None else bw
+        cut = pocsag.CUT if cut is None else float(cut)
         self.__bauds = tuple(bauds)
         self.__opts = {"slack": slack, "fix": fix, "follow": follow, "content": content}
         self.__front = None
@@ -38,16 +37,11 @@ class decode_pocsag:
         if int(follow) != follow or follow < 0:
             raise ValueError("decode_pocsag: follow must be a count from 0 up, got %r" % (follow,))
         if sigsrc is not None:
-            fs = sigsrc.sampFreq
-            if self.__bw <= 0 or fs < self.__bw:
-                raise ValueError("decode_pocsag: a bandwidth of %r S/s cannot be cut from %r S/s" % (self.__bw, fs))
-            self.__rate = fs / int(fs / self.__bw)
-            for baud in self.__bauds:
-                pocsag.params(self.__rate, baud, None, slack, fix)   # ValueError unless it gives 4 to 128 samples per bit
-            if not 0 < self.__cut < self.__rate / 2.0:
-                raise ValueError("decode_pocsag: a cut-off of %r Hz does not fit an audio rate of %r S/s" % (self.__cut, self.__rate))
-            self.__taps = ais.window_taps(fs)
-            self.__front = _afsk1200.decode_afsk1200(sigsrc, float(offset), self.__bw, use_device_raw)
+            def check_rate(rate):                  # ValueError unless it gives 4 to 128 samples per bit
+                for baud in self.__bauds:
+                    pocsag.params(rate, baud, None, slack, fix)
+            self.__front = _channel.Channels("decode_pocsag", sigsrc, [offset], bw, cut, use_device_raw, check_rate)
+            self.__rate = self.__front.rate
         self.__done = False
         self.__pages = []
         self.__info = {}
@@ -125,29 +119,19 @@ class decode_pocsag:
         """the FM-demodulated audio as a float64 device array (the front end runs once)"""
         _hip.require_gpu()
         if self.__audio is None:
-            sig = self.__front._baseband(self.__taps)
-            sig.filter(filters.lowpass(self.__rate, self.__cut, storeState=False))
-            sig.funcApply(demod_fm.demod_fm().demod)
-            self.__audio = comm._convert(sig.device_signal, np.float64)
-        if not isinstance(self.__audio, _hip.DevArray):
-            self.__audio = _hip.DevArray.from_host(self.__audio)
-        if self.__audio.dtype != np.dtype(np.float64):
-            raise TypeError("float64 audio expected, got %s" % self.__audio.dtype)
+            self.__audio, = self.__front.audios(_channel.fm_audio)
+        self.__audio, = _channel.on_device([self.__audio])
         return self.__audio
 
     def _decode(self):
         if self.__done:
             return
         _hip.require_gpu()
-        laps = {"_t": time.perf_counter()}
-        ops = pocsag.DeviceOps(laps)
+        ops = pocsag.DeviceOps({})
         audio = self.audio()
         ops.lap("front_end")
         self.__pages, self.__info, self.__cand, self.__batches = pocsag.decode(audio, self.__rate, self.__bauds, ops=ops, **self.__opts)
-        laps.pop("_t")
-        for name in ("candidates", "batches", "host"):
-            laps.setdefault(name, 0.0)
-        self.timings = laps
+        self.timings = ops.finish("candidates", "batches", "host")
         for p in self.__pages:
             logging.info("%s (at %.4f s, %d bits repaired)", pocsag.line(p), p["t"], p["corrected"])
         self.__done = True

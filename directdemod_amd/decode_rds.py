@@ -11,7 +11,6 @@ the next one on.  The format is IEC 62106 / EN 50067 as publicly described and h
 INTEGRATION.md lists the limits.
 """
 import logging
-import time
 
 import numpy as np
 
@@ -129,15 +128,11 @@ class decode_rds:
         if self.__done:
             return
         _hip.require_gpu()
-        laps = {"_t": time.perf_counter()}
-        ops = rds.DeviceOps(laps)
+        ops = rds.DeviceOps({})
         mpx = self.audio()
         ops.lap("front_end")
         self.__groups, self.__info, self.__cand = rds.decode(mpx, self.__rate, ops=ops, **self.__opts)
-        laps.pop("_t")
-        for name in ("baseband", "candidates", "groups", "host"):
-            laps.setdefault(name, 0.0)
-        self.timings = laps
+        self.timings = ops.finish("baseband", "candidates", "groups", "host")
         for line in rds.text_lines(self.__groups):
             logging.info("%s", line)
         self.__done = True

@@ -10,11 +10,10 @@ Every frame carries its own header: nothing has to pull in, so a recording that 
 on.  The format is taken from public descriptions and has been met in synthesised recordings only; INTEGRATION.md lists the limits.
 """
 import logging
-import time
 
 import numpy as np
 
-from . import _hip, ais, comm, decode_afsk1200 as _afsk1200, demod_fm, filters, rs41
+from . import _channel, _hip, rs41
 
 _KEYS = ("t", "start", "status", "extended", "polarity", "frame_number", "serial", "battery", "gps_week", "gps_tow", "time", "lat", "lon",
          "alt", "speed", "heading", "climb", "sats", "meas_raw", "xdata", "blocks", "corrected", "header_errors", "followed")
@@ -48,23 +47,17 @@ class decode_rs41:
     when the source offers it (source.read_device_raw)."""
 
     def __init__(self, sigsrc, offset, bw=None, cut=None, slack=4, follow=2, use_device_raw=True):
-        self.__bw = 48000 if bw is None else bw
-        self.__cut = rs41.CUT if cut is None else float(cut)
+        bw = 48000 if bw is None else bw
+        cut = rs41.CUT if cut is None else float(cut)
         self.__opts = {"slack": slack, "follow": follow}
         self.__front = None
         self.__audio = None
         if int(follow) != follow or follow < 0:
             raise ValueError("decode_rs41: follow must be a count from 0 up, got %r" % (follow,))
         if sigsrc is not None:
-            fs = sigsrc.sampFreq
-            if self.__bw <= 0 or fs < self.__bw:
-                raise ValueError("decode_rs41: a bandwidth of %r S/s cannot be cut from %r S/s" % (self.__bw, fs))
-            self.__rate = fs / int(fs / self.__bw)
-            rs41.params(self.__rate, None, slack)            # ValueError unless it gives 4 to 64 samples per bit
-            if not 0 < self.__cut < self.__rate / 2.0:
-                raise ValueError("decode_rs41: a cut-off of %r Hz does not fit an audio rate of %r S/s" % (self.__cut, self.__rate))
-            self.__taps = ais.window_taps(fs)
-            self.__front = _afsk1200.decode_afsk1200(sigsrc, float(offset), self.__bw, use_device_raw)
+            self.__front = _channel.Channels("decode_rs41", sigsrc, [offset], bw, cut, use_device_raw,
+                                             lambda rate: rs41.params(rate, None, slack))    # (4 to 64 samples per bit)
+            self.__rate = self.__front.rate
         self.__done = False
         self.__frames = []
         self.__info = {}
@@ -140,29 +133,19 @@ class decode_rs41:
         """the FM-demodulated audio as a float64 device array (the front end runs once)"""
         _hip.require_gpu()
         if self.__audio is None:
-            sig = self.__front._baseband(self.__taps)
-            sig.filter(filters.lowpass(self.__rate, self.__cut, storeState=False))
-            sig.funcApply(demod_fm.demod_fm().demod)
-            self.__audio = comm._convert(sig.device_signal, np.float64)
-        if not isinstance(self.__audio, _hip.DevArray):
-            self.__audio = _hip.DevArray.from_host(self.__audio)
-        if self.__audio.dtype != np.dtype(np.float64):
-            raise TypeError("float64 audio expected, got %s" % self.__audio.dtype)
+            self.__audio, = self.__front.audios(_channel.fm_audio)
+        self.__audio, = _channel.on_device([self.__audio])
         return self.__audio
 
     def _decode(self):
         if self.__done:
             return
         _hip.require_gpu()
-        laps = {"_t": time.perf_counter()}
-        ops = rs41.DeviceOps(laps)
+        ops = rs41.DeviceOps({})
         audio = self.audio()
         ops.lap("front_end")
         self.__frames, self.__info, self.__cand = rs41.decode(audio, self.__rate, ops=ops, **self.__opts)
-        laps.pop("_t")
-        for name in ("candidates", "frames", "host"):
-            laps.setdefault(name, 0.0)
-        self.timings = laps
+        self.timings = ops.finish("candidates", "frames", "host")
         for f in self.__frames:
             logging.info("RS41 %s frame %s at %.4f s: %s, %s", f["serial"], f["frame_number"], f["t"], f["status"],
                          "no position" if f["lat"] is None else "%.5f %.5f %.1f m" % (f["lat"], f["lon"], f["alt"]))

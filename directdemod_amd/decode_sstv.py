@@ -11,7 +11,6 @@ The mode figures are taken from public descriptions of the PD modes; nothing her
 decoder (INTEGRATION.md lists the limits).
 """
 import logging
-import time
 
 import numpy as np
 
@@ -95,13 +94,11 @@ class decode_sstv:
         if self.__done:
             return
         _hip.require_gpu()
-        laps = {"_t": time.perf_counter()}
-        ops = sstv.DeviceOps(laps)
+        ops = sstv.DeviceOps({})
         audio = self.audio()
         ops.lap("front_end")
         self.__images, self.__info = sstv.decode(audio, self.__rate, self.__mode, ops)
-        del laps["_t"]
-        self.timings = laps
+        self.timings = ops.finish()
         for i in self.__info:
             logging.info("SSTV %s image at sample %d: %d rows, %d of %d syncs, slant %.0f ppm, %d empty pixels", i["mode"], i["start"],
                          i["rows"], i["syncs_matched"], i["syncs_expected"], i["slant_ppm"], i["empty_pixels"])

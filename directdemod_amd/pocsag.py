@@ -13,13 +13,12 @@ integer whose bit 31 is the first-sent bit.
 
 The format is taken from public descriptions of POCSAG (CCIR Radiopaging Code No. 1, ITU-R M.584); INTEGRATION.md lists the limits.
 """
-import ctypes as C
 import math
-import time
 
 import numpy as np
 
-from . import _hip
+from . import _burst
+from ._burst import Laps, need
 from ._hip import DevArray, check, lib
 from .ais import positions, quantise, values  # noqa: F401  (the same quantiser, positions and window sums)
 
@@ -204,11 +203,6 @@ def batches_host(audio, sps, w, fix, ts):
 
 
 # ------------------------------------------------------------------------------------------------------------------ the device stages
-def _need(a, what):
-    if not isinstance(a, DevArray) or a.dtype != _F64:
-        raise TypeError("%s: a float64 device array expected" % what)
-
-
 def capacity(n, sps):
     """the default list capacity: a clean batch passes at about sps adjacent starts of its 544 sps samples, a share of 1 / 544 of the
     audio when batch follows batch; four times that and 1024"""
@@ -218,22 +212,16 @@ def capacity(n, sps):
 def candidates(audio, sps, w, slack=2, cap=None):
     """float64 device audio -> (the survivors as a device int64 array, how many) (dd_pocsag_candidates); a list that proves too
     small is asked for again at the true count"""
-    _need(audio, "pocsag.candidates")
+    need(audio, _F64, "pocsag.candidates")
     cap = capacity(audio.n, sps) if cap is None else int(cap)
-    count = C.c_int64(0)
-    while True:
-        lst = DevArray(max(cap, 1), np.int64)
-        rc = lib().dd_pocsag_candidates(audio.ptr, audio.n, float(sps), int(w), int(slack), lst.ptr, cap, C.byref(count), None)
-        if rc == _hip.DD_ERR_INVALID and count.value > cap:
-            cap = count.value
-            continue
-        check(rc, "dd_pocsag_candidates")
-        return lst, int(count.value)
+    def call(lst, cap, count):
+        return lib().dd_pocsag_candidates(audio.ptr, audio.n, float(sps), int(w), int(slack), lst, cap, count, None)
+    return _burst.candidates("dd_pocsag_candidates", cap, call)
 
 
 def batches(audio, sps, w, fix, lst, m):
     """the first m starts of the device list -> the dict of batches_host, on the host (dd_pocsag_batches)"""
-    _need(audio, "pocsag.batches")
+    need(audio, _F64, "pocsag.batches")
     if not isinstance(lst, DevArray):
         lst = DevArray.from_host(np.ascontiguousarray(lst, dtype=np.int64))
     det = _empty_det(m)
@@ -250,13 +238,12 @@ def batches(audio, sps, w, fix, lst, m):
 
 def masks_device(audio, sps, w, slack=2):
     """the mask byte of every sample, uint8[n] on the host, 0 past the last start (dd_debug_pocsag_masks, a diagnostic)"""
-    _need(audio, "pocsag.masks_device")
-    mask = DevArray(max(audio.n, 1), np.uint8)
-    check(lib().dd_debug_pocsag_masks(audio.ptr, audio.n, float(sps), int(w), int(slack), mask.ptr, None), "dd_debug_pocsag_masks")
-    return mask.to_host()[:audio.n]
+    need(audio, _F64, "pocsag.masks_device")
+    return _burst.masks("dd_debug_pocsag_masks", audio.n,
+                        lambda mask: lib().dd_debug_pocsag_masks(audio.ptr, audio.n, float(sps), int(w), int(slack), mask, None))
 
 
-class HostOps:
+class HostOps(Laps):
     """the stages of `decode` in NumPy"""
 
     def detect(self, audio, sps, w, slack, fix):
@@ -265,15 +252,9 @@ class HostOps:
     def batches(self, audio, sps, w, fix, ts):
         return batches_host(audio, sps, w, fix, ts)
 
-    def lap(self, name):
-        pass
 
-
-class DeviceOps:
+class DeviceOps(Laps):
     """the stages of `decode` on the device; `laps` collects seconds per stage, with a synchronisation after each"""
-
-    def __init__(self, laps=None):
-        self.laps = laps
 
     def detect(self, audio, sps, w, slack, fix):
         lst, m = candidates(audio, sps, w, slack)
@@ -286,13 +267,6 @@ class DeviceOps:
         det = batches(audio, sps, w, fix, ts, len(ts))
         self.lap("batches")
         return det
-
-    def lap(self, name):
-        if self.laps is not None:
-            _hip.sync()
-            now = time.perf_counter()
-            self.laps[name] = self.laps.get(name, 0.0) + now - self.laps["_t"]
-            self.laps["_t"] = now
 
 
 # ------------------------------------------------------------------------------------------------------------------ the host logic

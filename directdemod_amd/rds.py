@@ -17,14 +17,13 @@ The format is IEC 62106 / EN 50067 as publicly described and has been met in syn
 limits.
 """
 import bisect
-import ctypes as C
 import functools
 import math
-import time
 
 import numpy as np
 
-from . import _hip
+from . import _burst
+from ._burst import Laps, need
 from ._hip import DevArray, check, lib
 
 BITRATE = 1187.5
@@ -288,11 +287,6 @@ def groups_host(b, sps, fix, ts):
 
 
 # ------------------------------------------------------------------------------------------------------------------ the device stages
-def _need(a, dtype, what):
-    if not isinstance(a, DevArray) or a.dtype != dtype:
-        raise TypeError("%s: a %s device array expected" % (what, dtype))
-
-
 @functools.lru_cache(maxsize=None)
 def table_device():
     """the phasor table on the device, int32[2048], uploaded once"""
@@ -301,7 +295,7 @@ def table_device():
 
 def baseband(mpx, d, step, n0=0):
     """float64 device multiplex -> the baseband as a device int32 array of n // d pairs (dd_rds_baseband)"""
-    _need(mpx, _F64, "rds.baseband")
+    need(mpx, _F64, "rds.baseband")
     nout = mpx.n // int(d)
     b = DevArray(max(2 * nout, 2), np.int32)
     check(lib().dd_rds_baseband(mpx.ptr, mpx.n, int(d), int(n0) & 0xFFFFFFFFFFFFFFFF, int(step), table_device().ptr, b.ptr, None),
@@ -317,22 +311,16 @@ def capacity(m):
 def candidates(b, m, sps, clean=3, cap=None):
     """device baseband of m pairs -> (the survivors as a device int64 array, how many) (dd_rds_candidates); a list that proves too
     small is asked for again at the true count"""
-    _need(b, _I32, "rds.candidates")
+    need(b, _I32, "rds.candidates")
     cap = capacity(m) if cap is None else int(cap)
-    count = C.c_int64(0)
-    while True:
-        lst = DevArray(max(cap, 1), np.int64)
-        rc = lib().dd_rds_candidates(b.ptr, int(m), float(sps), int(clean), lst.ptr, cap, C.byref(count), None)
-        if rc == _hip.DD_ERR_INVALID and count.value > cap:
-            cap = count.value
-            continue
-        check(rc, "dd_rds_candidates")
-        return lst, int(count.value)
+    def call(lst, cap, count):
+        return lib().dd_rds_candidates(b.ptr, int(m), float(sps), int(clean), lst, cap, count, None)
+    return _burst.candidates("dd_rds_candidates", cap, call)
 
 
 def groups(b, m, sps, fix, lst, count):
     """the first `count` starts of the device list -> the dict of groups_host, on the host (dd_rds_groups)"""
-    _need(b, _I32, "rds.groups")
+    need(b, _I32, "rds.groups")
     if not isinstance(lst, DevArray):
         lst = DevArray.from_host(np.ascontiguousarray(lst, dtype=np.int64)) if count else None
     det = _empty_det(count)
@@ -348,15 +336,14 @@ def groups(b, m, sps, fix, lst, count):
 
 def masks_device(b, m, sps, clean=3):
     """the mask byte of every start, uint8[m] on the host (dd_debug_rds_masks, a diagnostic)"""
-    _need(b, _I32, "rds.masks_device")
-    mask = DevArray(max(m, 1), np.uint8)
-    check(lib().dd_debug_rds_masks(b.ptr, int(m), float(sps), int(clean), mask.ptr, None), "dd_debug_rds_masks")
-    return mask.to_host()[:m]
+    need(b, _I32, "rds.masks_device")
+    return _burst.masks("dd_debug_rds_masks", m,
+                        lambda mask: lib().dd_debug_rds_masks(b.ptr, int(m), float(sps), int(clean), mask, None))
 
 
 def halfbit_device(b, m, sps):
     """z as int32[m, 2] on the host (dd_debug_rds_halfbit, a diagnostic)"""
-    _need(b, _I32, "rds.halfbit_device")
+    need(b, _I32, "rds.halfbit_device")
     z = DevArray(max(2 * m, 2), np.int32)
     check(lib().dd_debug_rds_halfbit(b.ptr, int(m), float(sps), z.ptr, None), "dd_debug_rds_halfbit")
     return z.to_host()[:2 * m].reshape(m, 2)
@@ -374,7 +361,7 @@ def repair_device(words, offs, fix):
     return fixed.to_host(), status.to_host()
 
 
-class HostOps:
+class HostOps(Laps):
     """the stages of `decode` in NumPy"""
 
     def baseband(self, mpx, d, step):
@@ -387,15 +374,9 @@ class HostOps:
     def groups(self, b, m, sps, fix, ts):
         return groups_host(b, sps, fix, ts)
 
-    def lap(self, name):
-        pass
 
-
-class DeviceOps:
+class DeviceOps(Laps):
     """the stages of `decode` on the device; `laps` collects seconds per stage, with a synchronisation after each"""
-
-    def __init__(self, laps=None):
-        self.laps = laps
 
     def baseband(self, mpx, d, step):
         b = baseband(mpx, d, step)
@@ -413,13 +394,6 @@ class DeviceOps:
         det = groups(b, m, sps, fix, ts, len(ts))
         self.lap("groups")
         return det
-
-    def lap(self, name):
-        if self.laps is not None:
-            _hip.sync()
-            now = time.perf_counter()
-            self.laps[name] = self.laps.get(name, 0.0) + now - self.laps["_t"]
-            self.laps["_t"] = now
 
 
 # ------------------------------------------------------------------------------------------------------------------ the parser

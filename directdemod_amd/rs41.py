@@ -15,15 +15,14 @@ means.  Polarity 0 reads high as 1, polarity 1 reads low as 1.  A byte holds its
 The format is taken from public descriptions of the RS41 and has been met in synthesised recordings only; INTEGRATION.md lists the
 limits.
 """
-import ctypes as C
 import datetime
 import functools
 import math
-import time
 
 import numpy as np
 
-from . import _hip
+from . import _burst
+from ._burst import Laps, need
 from ._hip import DevArray, check, lib
 from .ais import positions, quantise, values  # noqa: F401  (the same quantiser, positions and window sums)
 
@@ -363,11 +362,6 @@ def frames_host(audio, sps, w, ts):
 
 
 # ------------------------------------------------------------------------------------------------------------------ the device stages
-def _need(a, what):
-    if not isinstance(a, DevArray) or a.dtype != _F64:
-        raise TypeError("%s: a float64 device array expected" % what)
-
-
 def capacity(n, sps):
     """the default list capacity: a clean frame passes at about sps adjacent starts of its second; 1024 and a share of the audio"""
     return 1024 + int(n) // 512
@@ -376,22 +370,16 @@ def capacity(n, sps):
 def candidates(audio, sps, w, slack=4, cap=None):
     """float64 device audio -> (the survivors as a device int64 array, how many) (dd_rs41_candidates); a list that proves too small
     is asked for again at the true count"""
-    _need(audio, "rs41.candidates")
+    need(audio, _F64, "rs41.candidates")
     cap = capacity(audio.n, sps) if cap is None else int(cap)
-    count = C.c_int64(0)
-    while True:
-        lst = DevArray(max(cap, 1), np.int64)
-        rc = lib().dd_rs41_candidates(audio.ptr, audio.n, float(sps), int(w), int(slack), lst.ptr, cap, C.byref(count), None)
-        if rc == _hip.DD_ERR_INVALID and count.value > cap:
-            cap = count.value
-            continue
-        check(rc, "dd_rs41_candidates")
-        return lst, int(count.value)
+    def call(lst, cap, count):
+        return lib().dd_rs41_candidates(audio.ptr, audio.n, float(sps), int(w), int(slack), lst, cap, count, None)
+    return _burst.candidates("dd_rs41_candidates", cap, call)
 
 
 def frames(audio, sps, w, lst, m):
     """the first m starts of the device list -> the dict of frames_host, on the host (dd_rs41_frames)"""
-    _need(audio, "rs41.frames")
+    need(audio, _F64, "rs41.frames")
     if not isinstance(lst, DevArray):
         lst = DevArray.from_host(np.ascontiguousarray(lst, dtype=np.int64))
     det = _empty_det(m)
@@ -407,10 +395,9 @@ def frames(audio, sps, w, lst, m):
 
 def masks_device(audio, sps, w, slack=4):
     """the mask byte of every sample, uint8[n] on the host, 0 past the last start (dd_debug_rs41_masks, a diagnostic)"""
-    _need(audio, "rs41.masks_device")
-    mask = DevArray(max(audio.n, 1), np.uint8)
-    check(lib().dd_debug_rs41_masks(audio.ptr, audio.n, float(sps), int(w), int(slack), mask.ptr, None), "dd_debug_rs41_masks")
-    return mask.to_host()[:audio.n]
+    need(audio, _F64, "rs41.masks_device")
+    return _burst.masks("dd_debug_rs41_masks", audio.n,
+                        lambda mask: lib().dd_debug_rs41_masks(audio.ptr, audio.n, float(sps), int(w), int(slack), mask, None))
 
 
 def rs_device(words, first_valid=0):
@@ -424,7 +411,7 @@ def rs_device(words, first_valid=0):
     return fixed.to_host().reshape(m, RS_N), errors.to_host()
 
 
-class HostOps:
+class HostOps(Laps):
     """the stages of `decode` in NumPy"""
 
     def detect(self, audio, sps, w, slack):
@@ -433,15 +420,9 @@ class HostOps:
     def frames(self, audio, sps, w, ts):
         return frames_host(audio, sps, w, ts)
 
-    def lap(self, name):
-        pass
 
-
-class DeviceOps:
+class DeviceOps(Laps):
     """the stages of `decode` on the device; `laps` collects seconds per stage, with a synchronisation after each"""
-
-    def __init__(self, laps=None):
-        self.laps = laps
 
     def detect(self, audio, sps, w, slack):
         lst, m = candidates(audio, sps, w, slack)
@@ -454,13 +435,6 @@ class DeviceOps:
         det = frames(audio, sps, w, ts, len(ts))
         self.lap("frames")
         return det
-
-    def lap(self, name):
-        if self.laps is not None:
-            _hip.sync()
-            now = time.perf_counter()
-            self.laps[name] = self.laps.get(name, 0.0) + now - self.laps["_t"]
-            self.laps["_t"] = now
 
 
 # ------------------------------------------------------------------------------------------------------------------ the parser

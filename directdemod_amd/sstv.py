@@ -9,12 +9,12 @@ The mode figures come from public descriptions of the PD modes and have not been
 import ctypes as C
 import logging
 import math
-import time
 from collections import namedtuple
 
 import numpy as np
 
 from . import _hip
+from ._burst import Laps
 from ._hip import DevArray, check, lib
 
 Mode = namedtuple("Mode", "name vis width height pixel")           # pixel time in seconds
@@ -377,7 +377,7 @@ def match_grid(cands, start0, period0, k0, k1, tol=GRID_TOLERANCE):
     return ks, ps, start, period
 
 
-class HostOps:
+class HostOps(Laps):
     """the stages of `decode` in NumPy"""
 
     def lag(self, audio, hr, hi):
@@ -398,15 +398,9 @@ class HostOps:
     def color(self, levels, pairs, W):
         return color_host(np.asarray(levels).reshape(pairs, 4, W))
 
-    def lap(self, name):
-        pass
 
-
-class DeviceOps:
+class DeviceOps(Laps):
     """the stages of `decode` on the device; `laps` collects seconds per stage, with a synchronisation after each"""
-
-    def __init__(self, laps=None):
-        self.laps = laps
 
     def lag(self, audio, hr, hi):
         return lag(audio, hr, hi)
@@ -425,13 +419,6 @@ class DeviceOps:
 
     def color(self, levels, pairs, W):
         return color(levels, pairs, W)
-
-    def lap(self, name):
-        if self.laps is not None:
-            _hip.sync()
-            now = time.perf_counter()
-            self.laps[name] = self.laps.get(name, 0.0) + now - self.laps["_t"]
-            self.laps["_t"] = now
 
 
 def decode(audio, rate, mode=None, ops=None):

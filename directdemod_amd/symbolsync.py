@@ -6,11 +6,11 @@ two modules' MINSYNC and MAXSYNC stages, and the decode pass of the two decoder 
 """
 import ctypes as C
 import logging
-import time
 
 import numpy as np
 
 from . import _hip, chunker, comm
+from ._burst import Laps
 from ._hip import DevArray, check, lib
 
 
@@ -215,14 +215,7 @@ class SyncDecoder:
         _hip.require_gpu()
         src = self._sigsrc
         t = dict.fromkeys(tuple(self.STAGES) + ("walk", "lim"), 0.0)
-        t0 = time.perf_counter()
-
-        def lap(name):
-            nonlocal t0
-            _hip.sync()
-            now = time.perf_counter()
-            t[name] = t.get(name, 0.0) + now - t0
-            t0 = now
+        lap = Laps(t).lap
         ck = chunker.chunker(src)
         read = src.read
         if self._use_raw and hasattr(src, "read_device_raw") and src.length > 0 and src.read_device_raw(0, 1) is not None:
