@@ -223,6 +223,12 @@ SIGNATURES = {
     "dd_debug_rds_masks": (_int, [_p, _i64, C.c_double, _int, _p, _p]),
     "dd_debug_rds_halfbit": (_int, [_p, _i64, C.c_double, _p, _p]),
     "dd_debug_rds_repair": (_int, [_p, _p, _i64, _int, _p, _p, _p]),
+    # FM stereo audio (dd_fmstereo.h)
+    "dd_fms_pilot": (_int, [_p, _i64, _u64, _p, _p, _p]),
+    "dd_fms_carrier": (_int, [_p, _i64, _i64, _p, _p, _p, _p]),
+    "dd_fms_audio": (_int, [_p, _i64, _u64, _p, _p, _i64, _int, _p, _int, _int, _int, _p, _p]),
+    "dd_debug_fms_mix": (_int, [_p, _i64, _u64, _p, _p, _i64, _int, _p, _p]),
+    "dd_debug_fms_audio_route": (_int, [_p, _i64, _u64, _p, _p, _i64, _int, _p, _int, _int, _int, _int, _p, _p]),
     "dd_lrpt_rs": (_int, [_p, _i64, _p, _p, _p]),
     "dd_lrpt_jpeg": (_int, [_p, _p, _p, _p, _i64, _i64, _p, _p, _p]),
     "dd_funcube_mix_ramp": (_int, [_p, _p, _i64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _p, _p]),

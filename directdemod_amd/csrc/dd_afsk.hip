@@ -129,6 +129,10 @@ extern "C" int dd_afsk_edges_f64(const double* binary_filter, int64_t n, int spb
 // the same LDS prefix sum, every sample tested as a group start by four block remainders, burst repair per wave
 #include "dd_rds.h"
 
+// FM stereo audio from the same multiplex: 19 kHz pilot blocks, the 38 kHz correction per block, the mixer and a decimating FIR over
+// both channels, integer behind dd_rds.h's quantiser and table
+#include "dd_fmstereo.h"
+
 // the image packets' JPEG-like payload: Huffman decoding, dequantisation, inverse transform
 #include "dd_lrpt_jpeg.h"
 

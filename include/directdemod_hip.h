@@ -705,6 +705,25 @@ int dd_rds_candidates(const int32_t* b, int64_t m, double sps, int clean, int64_
 int dd_rds_groups(const int32_t* b, int64_t m, double sps, int fix, const int64_t* list, int64_t count, uint16_t* words, int32_t* meta,
                   void* stream);
 
+/* ---- FM stereo audio from the multiplex: pilot, 38 kHz subcarrier, de-emphasis (beyond the reference) -------
+ * fmstereo.py restates every entry in NumPy.  mpx, q and table as for RDS above; phase19(j) = bits 31 .. 22 of (j * step19) mod 2^32
+ * with step19 = rint(19000 * 2^32 / R), phase38 the same of step38 = 2 step19 mod 2^32.  All shifts are arithmetic, all divisions floor.
+ * dd_fms_pilot -- P[2 k], P[2 k + 1] = (the sum over i < 256 of q[256 k + i] * table[phase19(256 k + i)]) >> 10 for k < n / 256 (a tail
+ *     shorter than a block is dropped).  |P| <= 2^27.
+ * dd_fms_carrier -- per block k < nb: S[k] = (the sum of P[j] over |j - k| <= 8, 0 <= j < nb) >> 8 (int64 sums, stored as int32 pairs),
+ *     cnt = the blocks summed; lock[k] = 1 iff |S|^2 > 0 and |S|^2 >= thr * cnt^2 (0 <= thr <= 2^48), else 0; u[2 k], u[2 k + 1] =
+ *     -((Sr^2 - Si^2) << 14) / |S|^2 and -((2 Sr Si) << 14) / |S|^2 when locked, (0, 0) when not: exp(2 i delta) in Q14, delta the
+ *     pilot's phase against the table's.  P must be as dd_fms_pilot gives it (|P| <= 2^27) for the sums to fit.
+ * dd_fms_audio -- with u of nb blocks and the block of sample j = min(j / 256, nb - 1) (nb = 0: u = 0 everywhere), (tr, ti) =
+ *     conj(table[phase38(j)]): c = (tr ui + ti ur) >> 14, c2 = (c G) >> 12 (0 <= G <= 12288), a[j] = (q[j] (2^14 + c2)) >> 8,
+ *     b[j] = (q[j] (2^14 - c2)) >> 8; out[2 o] = (the sum over i < ntaps of taps[i] a[o D + d0 - i]) >> 15, out[2 o + 1] the same of b,
+ *     for o < ceil(n / D); samples outside [0, n) count as 0.  1 <= ntaps <= 1024, 1 <= D <= 12, 0 <= d0 < ntaps; the sum of |taps|
+ *     must not exceed 2^17 (sums below 2^41, outputs below 2^26).  mpx, table, u, taps (int32) and out are device arrays. */
+int dd_fms_pilot(const double* mpx, int64_t n, uint64_t step19, const int32_t* table, int32_t* P, void* stream);
+int dd_fms_carrier(const int32_t* P, int64_t nb, int64_t thr, int32_t* S, int32_t* u, uint8_t* lock, void* stream);
+int dd_fms_audio(const double* mpx, int64_t n, uint64_t step38, const int32_t* table, const int32_t* u, int64_t nb, int G,
+                 const int32_t* taps, int ntaps, int D, int d0, int32_t* out, void* stream);
+
 /* ---- Funcube BPSK sync detection (decode_funcube.py:148-306) ------------------------------------------------------------
  * dd_funcube_mix_ramp -- dd_meteor_mix with the frequency formed per sample: th = ((w * f[k]) * k) * inv_fs, w = -2 pi,
  *     f[k] = f0 + k * delta (np.arange's fill) clipped to target from above when target > f0, from below otherwise.

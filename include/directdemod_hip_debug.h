@@ -131,6 +131,14 @@ int  dd_debug_rds_halfbit(const int32_t* b, int64_t m, double sps, int32_t* z, v
  *   n ones, with fixed[c] the block without that burst, and -1 with fixed[c] = the word where there is none.  Device arrays. */
 int  dd_debug_rds_repair(const uint32_t* words, const int32_t* offs, int64_t count, int fix, uint32_t* fixed, int32_t* status,
                          void* stream);
+/* dd_debug_fms_mix -- the two mixed signals dd_fms_audio filters (its arguments): ab[2 j] = a[j], ab[2 j + 1] = b[j] for j < n, so the
+ *   mixer and the filter can be tested apart. */
+int  dd_debug_fms_mix(const double* mpx, int64_t n, uint64_t step38, const int32_t* table, const int32_t* u, int64_t nb, int G,
+                      int32_t* ab, void* stream);
+/* dd_debug_fms_audio_route -- dd_fms_audio with the filter's arithmetic chosen: route 0 sums in int64, route 1 in float64 fused
+ *   multiply-adds; both are exact below 2^53 and give the same bits (profiles/fmstereo.txt compares their speed). */
+int  dd_debug_fms_audio_route(const double* mpx, int64_t n, uint64_t step38, const int32_t* table, const int32_t* u, int64_t nb, int G,
+                              const int32_t* taps, int ntaps, int D, int d0, int route, int32_t* out, void* stream);
 
 #ifdef __cplusplus
 }
